@@ -2,6 +2,7 @@
 """bench.py — headline benchmark of the hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hgemm|attn|attn_cfg4|attn_d512]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -34,6 +35,9 @@ labelled so).  Blocks whose per-rank shard would hold fewer workgroups than a GP
 No data-path collective exists: the only collectives are the barrier bracketing the timed region and the gather of
 per-rank timings.  W warm-up steps, then EXACTLY K timed steps between barrier + torch.cuda.synchronize() on both
 sides; time = MAX over ranks; rank 0 prints ONE JSON line.
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step (C of the HGEMM, O of the attention
+workloads) goes to DIR/<name>.npy as float32, a fixed seeded row sample where the whole would exceed 48 MB (capture_output); the inputs
+are seeded, so two builds of the project can be compared output for output.
 
 "roofline": achieved = algorithmic FLOPs per launch / average launch duration from HIP events recorded on the launch
 stream around the SAME K timed launches (lc_timer_*: inside the wall-clock bracket, so kernel time <= step time); peak = 2500 TFLOP/s dense fp16 MFMA; "kernel" comes from the
@@ -83,7 +87,10 @@ def parse(argv=None):
     ap.add_argument("--quick", action="store_true", help="headline + config-3 attention only (plumbing tests)")
     ap.add_argument("--sustain-seconds", type=float, default=2.0)
     ap.add_argument("--sweep", action="store_true", help="also print a per-variant table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy (float32)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.workload == "attn_sharded":     # round-1 name of config 4
         a.workload = "attn_cfg4"
     return a
@@ -183,6 +190,37 @@ def timed_region(w, step, steps, warmup, prewarm=PREWARM):
     timed_region.event_ms = tm.ms   # (events are recorded inside the wall-clock bracket: kernel time <= step time)
     timed_region.power = ps.result(t0, t1)
     return secs
+
+
+DUMP_BYTES = 48 << 20    # --dump-outputs: float32 bytes of all arrays of one run together (ranks included)
+DUMP_SEED = 1234
+
+
+def capture_output(args, w, name, t, share=1):
+    """--dump-outputs: float32 host copy of `t`, what the timed path returned in its last step, taken right after its timed region (outside
+    the bracket).  Whole when it fits in its share of DUMP_BYTES, else a fixed seeded sample of whole rows (last dim kept) in index order,
+    the same rows in every run.  Written by write_outputs() as DIR/<name>.npy (DIR/<name>_rank<r>.npy when N > 1)."""
+    if not args.dump_outputs:
+        return
+    rows = t.reshape(-1, t.shape[-1])
+    keep = max(1, DUMP_BYTES // (share * w.size) // (rows.shape[1] * 4))
+    if rows.shape[0] > keep:
+        idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(DUMP_SEED))[:keep].sort().values
+        rows = rows[idx.to(rows.device)]
+    capture_output.arrays[name if w.size == 1 else f"{name}_rank{w.rank}"] = rows.float().cpu().numpy()
+
+
+capture_output.arrays = {}
+
+
+def write_outputs(args):
+    if not args.dump_outputs:
+        return
+    import numpy as np
+    d = Path(args.dump_outputs)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, arr in capture_output.arrays.items():
+        np.save(d / f"{name}.npy", arr)
 
 
 def per_rank_rows(w, ms_kernel_local, tflops_local):
@@ -310,6 +348,7 @@ def bench_hgemm(w, args):
     stride = host.make_block_swizzle_stride(n, n)                # reference default: N/4 = 2048 at 8192
     step = lambda: capi.hgemm(a, bb, c, layout=lay, variant=var, stages=2, swizzle_stride=stride)  # noqa: E731
     secs = timed_region(w, step, args.steps, args.warmup)
+    capture_output(args, w, "hgemm_c", c)      # before the comparators below write c again
     secs = lcd.max_over_ranks(w, secs)
     flops = 2.0 * n * n * n
     ms_local = timed_region.event_ms / args.steps
@@ -402,7 +441,7 @@ def bench_hgemm(w, args):
     return res
 
 
-def bench_attn(w, args, cfg4=False, steps=None, warmup=None, prewarm=PREWARM):
+def bench_attn(w, args, cfg4=False, steps=None, warmup=None, prewarm=PREWARM, dump=False):
     steps = steps or args.steps
     warmup = args.warmup if warmup is None else warmup
     B, H, N, D = (32, 32, 8192, 128) if cfg4 else (4, 32, 4096, 128)
@@ -421,6 +460,8 @@ def bench_attn(w, args, cfg4=False, steps=None, warmup=None, prewarm=PREWARM):
     tag = "cfg4" if cfg4 else "cfg3"
     step = lambda: capi.attn_call(entry, q, k, v, o, 2)          # noqa: E731   the reference's entry NAME
     secs = timed_region(w, step, steps, warmup, prewarm)
+    if dump:
+        capture_output(args, w, f"attn_{tag}_o", o)
     secs = lcd.max_over_ranks(w, secs)
     flops_total = host.mha_matmul_flops(B, H, N, D)               # whole job, all ranks
     flops_local = host.mha_matmul_flops(b_loc, h_loc, N, D)
@@ -481,7 +522,7 @@ def too_small_to_shard(name, workgroups_total, w, cus=None):
     return None
 
 
-def bench_attn_d512(w, args, steps=3):
+def bench_attn_d512(w, args, steps=3, dump=False):
     """Config 5a, the reference's published FFPA shape (1,48,8192,512): fp16 through the tiling-QKV entry and bf16
     through lc_attn_fwd_bf16; the 48 heads are sharded over the ranks."""
     B, H, N, D = 1, 48, 8192, 512
@@ -504,7 +545,10 @@ def bench_attn_d512(w, args, steps=3):
             step = lambda: capi.attn_call("flash_attn_mma_stages_split_q_tiling_qkv", q, k, v, o, 2)  # noqa: E731
         else:
             step = lambda: capi.attn_fwd_bf16(q, k, v, o)  # noqa: E731
-        secs = lcd.max_over_ranks(w, timed_region(w, step, steps, 1, prewarm=2))
+        secs = timed_region(w, step, steps, 1, prewarm=2)
+        if dump:
+            capture_output(args, w, f"attn_d512_o_{name}", o, share=2)
+        secs = lcd.max_over_ranks(w, secs)
         ms_kernel = lcd.max_over_ranks(w, timed_region.event_ms / steps)
         out[name] = {"value": flops_total * steps / secs * 1e-12, "ms_per_step": secs / steps * 1e3, "steps": steps,
                      "roofline": roofline(capi.attn_kernel_name(N, D, False, dt == torch.bfloat16, bh=B * h_loc), flops_local,
@@ -872,11 +916,11 @@ def run(args):
         if not args.quick and w.size == 1:
             blocks["fp8_gemm"] = bench_fp8(w, args)
     elif args.workload == "attn":
-        main_res = bench_attn(w, args, cfg4=False)
+        main_res = bench_attn(w, args, cfg4=False, dump=True)
     elif args.workload == "attn_cfg4":
-        main_res = bench_attn(w, args, cfg4=True, prewarm=1)
+        main_res = bench_attn(w, args, cfg4=True, prewarm=1, dump=True)
     else:
-        main_res = bench_attn_d512(w, args, steps=max(3, args.steps))
+        main_res = bench_attn_d512(w, args, steps=args.steps, dump=True)
         if "skipped" in main_res:      # a shard with fewer workgroups than CUs: nothing was timed
             raise SystemExit("bench.py --workload attn_d512: " + main_res["skipped"])
         main_res.update({"ms_per_step": main_res["fp16"]["ms_per_step"], "roofline": main_res["fp16"]["roofline"]})
@@ -962,6 +1006,7 @@ def run(args):
     out["headline"] = {"hgemm_8192_tflops": out["value"] / w.size if args.workload == "hgemm" else None,
                        "hgemm_frac": out["roofline"]["frac"] if args.workload == "hgemm" else None,
                        **{f"{t}_{k}": c[k] for t, c in also.items() for k in ("tflops", "frac", "kernel_ms")}}
+    write_outputs(args)
     sys.stdout.flush()
     os.dup2(real_stdout, 1)
     os.close(real_stdout)

@@ -236,8 +236,14 @@ def test_status_strings_and_argument_errors(built):
         == capi.LC_ERR_HEADDIM
     assert lib.lc_attn_call(b"flash_attn_mma_stages_split_q_shared_qkv", one, one, one, one, 1, 1, 128, 256, 2,
                             None) == capi.LC_ERR_HEADDIM
-    # the vendor entry initialises its handle lazily (hgemm_cublas.cu:44-46); with no GPU that fails cleanly
-    assert lib.lc_hgemm_vendor_f16(one, one, one, 256, 256, 256, 0, None) in (capi.LC_ERR_VENDOR, capi.LC_ERR_DEVICE)
+    # the vendor entry checks its arguments before any HIP call ...
+    assert lib.lc_hgemm_vendor_f16(None, one, one, 256, 256, 256, 0, None) == capi.LC_ERR_ARG
+    assert lib.lc_hgemm_vendor_f16(one, one, one, 256, 256, 256, 7, None) == capi.LC_ERR_ARG
+    assert lib.lc_hgemm_vendor_f16(one, one, one, 0, 256, 256, 0, None) == capi.LC_ERR_SHAPE
+    # ... and initialises its handle lazily (hgemm_cublas.cu:44-46); with no GPU that fails cleanly.  With a GPU the dummy pointers
+    # would reach a real GEMM and fault the device, so that call is made only without one (the gpu tests run it on real buffers)
+    if not torch.cuda.is_available():
+        assert lib.lc_hgemm_vendor_f16(one, one, one, 256, 256, 256, 0, None) in (capi.LC_ERR_VENDOR, capi.LC_ERR_DEVICE)
     assert lib.lc_timer_stop(None, None) == capi.LC_ERR_ARG
     assert lib.lc_clock_probe(None, None) == capi.LC_ERR_ARG
 

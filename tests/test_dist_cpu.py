@@ -81,6 +81,7 @@ def test_self_spawn_two_ranks_gloo(tmp_path, monkeypatch):
     from leetcuda_amd import dist as lcd
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("LC_DIST_BACKEND", "gloo")     # the ranks' backend (_spawned_worker); on a GPU box spawn() would assume RCCL
     lcd.spawn(_spawned_worker, 2, (str(tmp_path),))
     res = json.loads((tmp_path / "out.json").read_text())
     assert res["size"] == 2 and res["max"] == 2.0

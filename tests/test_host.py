@@ -11,6 +11,14 @@ from leetcuda_amd import host
 
 REF = Path("/root/reference/kernels")
 
+
+def _mounted(p: Path) -> bool:
+    try:
+        return p.exists()
+    except OSError:    # a parent directory this user may not read: no reference tree
+        return False
+
+
 # kernels/hgemm/pybind/hgemm.cc:126-181 and kernels/flash-attn/pybind/flash_attn.cc:170-223, frozen here so
 # the check also runs where /root/reference is absent (the GPU box).
 HGEMM_NAMES = """hgemm_naive_f16 hgemm_sliced_k_f16 hgemm_t_8x8_sliced_k_f16x4 hgemm_t_8x8_sliced_k_f16x4_pack
@@ -44,7 +52,7 @@ def _parse_bindings(path: Path):
     return re.findall(r"TORCH_BINDING_COMMON_EXTENSION\(\s*(\w+)\s*\)", txt[txt.index("PYBIND11_MODULE"):])
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference not mounted")
+@pytest.mark.skipif(not _mounted(REF), reason="reference not mounted")
 def test_frozen_name_lists_match_reference_pybind():
     assert _parse_bindings(REF / "hgemm/pybind/hgemm.cc") == HGEMM_NAMES
     assert _parse_bindings(REF / "flash-attn/pybind/flash_attn.cc") == ATTN_NAMES
@@ -517,3 +525,33 @@ def test_bench_compact_attention_scalars_and_traffic_models():
     assert bench.attn_traffic_model(48, 8192, 1024, 64, round_robin=True) == pytest.approx(14.4955e9, rel=1e-4)   # 8 passes, round-robin
     assert bench.attn_traffic_model(48, 8192, 512, 128) == pytest.approx(2.4159e9, rel=1e-4)
     assert bench.attn_traffic_model(128, 4096, 128, 256) == 4 * 128 * 4096 * 128 * 2                            # config 3: one pass = algorithmic
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: an output that fits is written whole; a larger one as the same seeded rows (in index order) in every
+    run, all arrays of a run together within the 64 MB a dump may take."""
+    import argparse
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    import bench
+    from leetcuda_amd import dist as lcd
+    args = argparse.Namespace(dump_outputs=str(tmp_path))
+    w = lcd.World()
+    small = torch.arange(12 * 8, dtype=torch.half).view(2, 6, 8)
+    big = torch.randn(70000, 256).half()
+    bench.capture_output.arrays = {}
+    bench.capture_output(args, w, "small", small)
+    bench.capture_output(args, w, "big", big)
+    first = bench.capture_output.arrays["big"]
+    bench.capture_output(args, w, "big", big)
+    bench.write_outputs(args)
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sorted(got) == ["big", "small"] and all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["small"], small.float().view(12, 8).numpy())
+    assert np.array_equal(got["big"], first) and got["big"].shape == (bench.DUMP_BYTES // (256 * 4), 256)
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    rows = {r.tobytes(): i for i, r in enumerate(big.float().numpy())}
+    idx = [rows[r.tobytes()] for r in got["big"]]
+    assert idx == sorted(idx) and len(set(idx)) == len(idx)
+    bench.capture_output(argparse.Namespace(dump_outputs=None), w, "none", small)
+    assert "none" not in bench.capture_output.arrays
