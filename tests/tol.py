@@ -62,3 +62,10 @@ def hgemm_close(out_f32, truth_f32, K, amp=1.0, atol=None):
     err = np.abs(out_f32.astype(np.float64) - truth_f32.astype(np.float64))
     bound = HGEMM_RTOL * np.abs(truth_f32.astype(np.float64)) + (hgemm_atol(K, amp) if atol is None else atol)
     return bool((err <= bound).all()), float(err.max()), float((err - bound).max())
+
+
+def fp16_rounded_fraction(c16, truth_f32) -> float:
+    """Share of the outputs (torch fp16 tensor) that are the exact result (fp32 numpy, the oracle's) rounded once to fp16."""
+    import numpy as np
+    got = c16.detach().cpu().contiguous().numpy().view(np.uint16)
+    return float((got == np.asarray(truth_f32, np.float32).astype(np.float16).view(np.uint16)).mean())
