@@ -37,7 +37,7 @@ int set_dyn_lds(KernelT kernel, int bytes) {
   return LC_OK;
 }
 
-// Compute units of the CURRENT device (the tail-split rule of launch_mfma256 and both persistent launchers size their grids with
+// Compute units of the CURRENT device (the tail-split rule of plan_hgemm and both persistent launchers size their grids with
 // it): looked up once per device ordinal, not once per process — a later device with another CU count gets its own figure.
 inline int device_cu_count() {
   static std::mutex mu;
@@ -190,9 +190,6 @@ inline bool stream_is_capturing(hipStream_t st) {
 // Every knob is a std::atomic<int> (relaxed loads / stores through the implicit conversions): lc_tune_set from one host thread
 // while another launches is a data race on a plain int; a launch reads each knob ONCE into a local and decides from that.
 using tune_t = std::atomic<int>;
-extern tune_t g_tune_attn_ablate, g_tune_w4_abl, g_tune_hgemm_stamps;
-extern tune_t g_tune_hgemm_mid, g_tune_hgemm_mid_ns;   // one-round kernel: tile / ring depth (lc_tune_set "hgemm_mid", "hgemm_mid_ns")
-extern tune_t g_tune_attn_d512;   // D = 256 / 512 attention kernel choice (lc_tune_set "attn_d512")
 extern tune_t g_tune_attn_bigd_stagger;   // attn_bigd4: the KV walk of XCD x starts x eighths in: 0 = auto (with the round-robin map), 1 = off, 2 = on
 extern tune_t g_tune_attn_bigd_map;     // query-block map of attn_bigd4 / attn_bigd6: 0 = auto (D = 1024 round-robin over the XCDs, D = 512 XCD-contiguous), 1 = contiguous, 2 = round-robin
 extern tune_t g_tune_hgemm_persist;   // 1 (default) = hgemm_w4y_kernel as a persistent workgroup per CU when the tiles divide evenly (tu_w4.hip)
@@ -209,12 +206,8 @@ inline int stagger_arg(int kt) {
   const int step = kt / 8;
   return 1 | (step < 1 ? 1 : step > 255 ? 255 : step) << 12 | 7 << 20;
 }
-extern tune_t g_tune_w4y_sched;   // schedule of hgemm_w4y_kernel's generated loop body (all of them compute the same bits)
 
 // launchers living in their own translation units
-// tu_w4.hip: LC_HGEMM_MFMA256W4 / W4S / W4B / W4C (M, N % 256 == 0, K % 64 == 0 checked by the caller)
-int w4_effective_variant(int variant, bool b_kn, int N, int K);   // W4C / W4X / W4Y -> W4B when 32-bit DMA offsets could overflow
-// nblk > 0: launch only the first nblk blocks (hgemm_w4y_kernel only; the caller hands the remaining raster ids to the 128-tile kernel)
 // the mid-size kernel (hgemm_mid.hip, tu_mid.hip): (64 tmw) x (64 tnw) tiles, ns ring slots
 int launch_hgemm_mid(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int tnw, int ns, int pw,
                      hipStream_t st, float* part = nullptr, int ks = 1);
@@ -225,7 +218,10 @@ size_t launch_hgemm_mid_edge_sk_floats(int M, int N, int tmw, int ks);
 int launch_hgemm_mid_edge_sk(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int ks, float* part, hipStream_t st);
 int launch_hgemm_mid_rem(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int ns, int tiles_m256,
                          int tiles_n256, int pw256, int rem_base, int rem_tiles, hipStream_t st);   // the 256-tile kernel's ragged last round as 128 x 128 quadrants
-int launch_w4_family(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, bool b_kn,
+// tu_w4.hip: the 4-wave 256-tile kernels; variant = what w4_effective_variant (lc_abi.hip) left of LC_HGEMM_MFMA256W4B / W4C / W4X / W4Y,
+// sched = hgemm_w4y_kernel's TN loop schedule, stamps / abl = LC_DIAG instantiations of W4C; nblk > 0: launch only the first nblk blocks
+// (hgemm_w4y_kernel only; the caller hands the remaining raster ids to smaller tiles)
+int launch_w4_family(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, int sched, int stamps, int abl, bool b_kn,
                      int tiles_m, int tiles_n, int panel_w, int nblk, hipStream_t st);
 // tu_valu.hip: the vector-ALU ladder (hgemm_valu.hip), rung = LC_HGEMM_VALU_*
 int launch_valu_rung(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int rung, hipStream_t st);
@@ -248,8 +244,8 @@ int diag_attn_slowpath_u_d64t(unsigned* out4, int reset);
 int launch_attn_w4i(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, int sched, hipStream_t st);
 int diag_attn_slowpath_g(unsigned* out4, int reset);   // + the slow-path counters of the w4i kernels
 // tu_attn_big.hip: full-width large-head-dim kernel, D in {256, 512}, N % 128 == 0, V as [B,H,N,D]; fp16 or bf16
-int launch_attn_bigd2(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool bf16,
-                      hipStream_t st);
+int launch_attn_bigd2(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool bf16, bool bigd3,
+                      hipStream_t st);   // bigd3: attn_bigd3 instead (lc_tune_set "attn_d512" = 2)
 // tu_attn_big4.hip: D = 1024 (attn_bigd4.hip: two waves share 32 query rows, each owns 512 columns; N % 64 == 0, V as [B,H,N,D], fp16) and
 // attn_bigd2's V-transposed instantiation (D = 256, N % 128 == 0, V as [B,H,D,N], fp16)
 int launch_attn_bigd4(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int span8, hipStream_t st);   // span8: DMA spread (eighths of a phase; 0 = default)

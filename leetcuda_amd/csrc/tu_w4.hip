@@ -38,14 +38,13 @@ int launch_w4x_one(const half_t* A, const half_t* B, half_t* C, int M, int N, in
 }
 
 template <bool B_KN>
-int launch_w4_t(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, int tiles_m,
+int launch_w4_t(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, int sched, int stamps, int abl, int tiles_m,
                 int tiles_n, int pw, int nblk, hipStream_t st) {
-  variant = w4_effective_variant(variant, B_KN, N, K);
 #ifdef LC_DIAG
-  if (variant == LC_HGEMM_MFMA256W4C && g_tune_hgemm_stamps)
+  if (variant == LC_HGEMM_MFMA256W4C && stamps)
     return launch_w4_one<B_KN, true, 1>(A, B, C, M, N, K, tiles_m, tiles_n, pw, st);
-  if (variant == LC_HGEMM_MFMA256W4C && g_tune_w4_abl) {
-    switch (g_tune_w4_abl) {   // bits: 2 no DMA, 4 no wait + barrier, 8 no fragment reads
+  if (variant == LC_HGEMM_MFMA256W4C && abl) {
+    switch (abl) {   // bits: 2 no DMA, 4 no wait + barrier, 8 no fragment reads
       case 2: return launch_w4_one<B_KN, true, 2>(A, B, C, M, N, K, tiles_m, tiles_n, pw, st);
       case 4: return launch_w4_one<B_KN, true, 4>(A, B, C, M, N, K, tiles_m, tiles_n, pw, st);
       case 6: return launch_w4_one<B_KN, true, 6>(A, B, C, M, N, K, tiles_m, tiles_n, pw, st);
@@ -58,7 +57,6 @@ int launch_w4_t(const half_t* A, const half_t* B, half_t* C, int M, int N, int K
   if constexpr (!B_KN) {
     if (variant == LC_HGEMM_MFMA256W4X) return launch_w4x_one<B_KN, -1>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
     if (variant == LC_HGEMM_MFMA256W4Y) {
-      const int sched = g_tune_w4y_sched;   // read once per launch
       if (sched == 0) return launch_w4x_one<B_KN, 0>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
       if (sched == 1) return launch_w4x_one<B_KN, 1>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
 #ifdef LC_DIAG
@@ -77,24 +75,9 @@ int launch_w4_t(const half_t* A, const half_t* B, half_t* C, int M, int N, int K
 }
 }  // namespace
 
-// buffer-descriptor DMA addresses are 32-bit offsets from the wave's first row: fall back to the 64-bit global form
-// when an offset could reach 2 GiB (NN: K tiles step through the whole of B)
-int w4_effective_variant(int variant, bool b_kn, int N, int K) {
-  if (variant == LC_HGEMM_MFMA256W4X && b_kn) variant = LC_HGEMM_MFMA256W4C;   // the compiler-scheduled 16x16x32 kernel is TN only
-  if (variant == LC_HGEMM_MFMA256W4C || variant == LC_HGEMM_MFMA256W4X ||
-      variant == LC_HGEMM_MFMA256W4Y) {
-    // (K-contiguous operands: a wave's pieces reach 64 rows past its base, 232 with hgemm_w4y's 32-row piece stride)
-    const size_t rows_off = (size_t)K * 2 * (variant == LC_HGEMM_MFMA256W4Y ? 260 : 130);
-    const size_t max_off = b_kn ? (size_t)K * N * 2 + (size_t)N * 64 : rows_off;
-    if (max_off >= ((size_t)1 << 31) || rows_off >= ((size_t)1 << 31)) return LC_HGEMM_MFMA256W4B;
-  }
-  return variant;
-}
-
-int launch_w4_family(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, bool b_kn,
+int launch_w4_family(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, int sched, int stamps, int abl, bool b_kn,
                      int tiles_m, int tiles_n, int panel_w, int nblk, hipStream_t st) {
-  const int nb = (nblk > 0 && nblk < tiles_m * tiles_n && w4_effective_variant(variant, b_kn, N, K) == LC_HGEMM_MFMA256W4Y) ? nblk : -1;
-  return b_kn ? launch_w4_t<true>(A, B, C, M, N, K, variant, tiles_m, tiles_n, panel_w, nb, st)
-              : launch_w4_t<false>(A, B, C, M, N, K, variant, tiles_m, tiles_n, panel_w, nb, st);
+  return b_kn ? launch_w4_t<true>(A, B, C, M, N, K, variant, sched, stamps, abl, tiles_m, tiles_n, panel_w, nblk, st)
+              : launch_w4_t<false>(A, B, C, M, N, K, variant, sched, stamps, abl, tiles_m, tiles_n, panel_w, nblk, st);
 }
 }  // namespace lc

@@ -249,7 +249,7 @@ def test_status_strings_and_argument_errors(built):
 
 
 def test_hgemm_dispatch_covers_the_reference_legal_shapes(built):
-    """Kernel selection needs no GPU (lc_hgemm_kernel_name shares resolve_hgemm_variant with the launcher).  The reference's kernels
+    """Kernel selection needs no GPU (lc_hgemm_kernel_name reports the plan lc_hgemm_f16 launches: plan_hgemm).  The reference's kernels
     are legal on M, N multiples of 128 and K multiples of 32 (hgemm_mma_stage.cu:650,675-676): with a large 256-tileable interior those
     shapes run the flagship kernel (+ border strips / a half K-step), small grids the 128-tile kernel, anything else the edge kernel;
     the cross-check kernels keep their 256 / K % 64 contract and say so."""
