@@ -143,6 +143,8 @@ const char* lc_build_info(int* is_diag);
  *                  mask << 20 with mask < 128 (bit 27 together with any other bit is refused).  Only the fp32 accumulation order changes:
  *                  results agree with the unstaggered walk to fp16 rounding
  *                  (the K = 128 fp8 kernel shares the stagger and the persistent walk of "hgemm_persist")
+ *   "attn_causal_order" grid order of the causal merged-phase kernel: 0 = auto (longest query block first up to 8 rounds of blocks per CU,
+ *                  head-major beyond), 1 = longest block first, 2 = head-major (same bits)
  *   "attn_split"   split-KV of the merged-phase kernel (attn_w4u.hip WALK 3) for grids that do not fill the GPU: 0 = auto (a cost model
  *                  over B x H, N, D and the CU count picks 1 / 2 / 4 / 8 / 16 KV ranges per 256-row query block, lc_abi.hip attn_split_auto),
  *                  1 = off: the merged-phase kernel itself on any grid (also switches off the small-grid substitution below), 2 / 4 / 8 / 16 = that
@@ -276,7 +278,7 @@ int lc_hgemm_entry_info(const char* entry, int* layout, int* nargs);
  * flash_attn_mma_share_qkv.cu:70,772,872, flash_attn_mma_tiling_qkv.cu:75,800,881 and siblings.
  * Q,K,O: [B,H,N,D] fp16 contiguous.  V: [B,H,N,D], or [B,H,D,N] when v_transposed != 0
  * (the reference's *_swizzle_qkv share_kv/share_qkv/tiling_qk entries, flash_attn_mma.py:441-442).
- * Non-causal, scale = 1/sqrt(D), no dropout / mask / LSE output.  fp32 softmax, fp32 MFMA accumulate
+ * Non-causal (causal: lc_attn_fwd_f16_ex), scale = 1/sqrt(D), no dropout / mask / LSE output.  fp32 softmax, fp32 MFMA accumulate
  * (family / acc_f32 / stages are accepted for signature parity and select nothing; CDNA4 MFMA has no fp16-accumulate form).
  * Batch variance: the kernel — and with it the fp32 summation order, i.e. the low bits of O — depends on B x H and the CU count
  * for shapes whose grid would not fill the GPU (small grids run 128-row workgroups or the split-KV path); one (B, H, N, D) on one
@@ -284,6 +286,17 @@ int lc_hgemm_entry_info(const char* entry, int* layout, int* nargs);
  * N must be a multiple of 64; D in {32, 64, 96, 128, 256, 512, 1024} — the head dims of the reference dispatchers. */
 int lc_attn_fwd_f16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,
                     int v_transposed, int family, int acc_f32, int stages, void* stream);
+
+/* EXTENSION (the reference has no causal mask): flags select the V layout and a causal mask.
+ *   LC_ATTN_CAUSAL: query row i attends to key rows j <= i of the same (batch, head) (Q and K have the same length N).  fp16,
+ *   D in {32, 64, 96, 128}, N % 64 == 0; other head dims give LC_ERR_HEADDIM.  One kernel, no workspace (legal under graph
+ *   capture); D = 64 / 128 with N % 256 == 0 run attn_fwd_w4u_causal_kernel, the rest attn_fwd_causal_kernel.  The result does not
+ *   depend on B x H, the CU count or the grid order ("attn_causal_order").
+ *   Without LC_ATTN_CAUSAL the call is lc_attn_fwd_f16 (same plan, kernel and bits).  Unknown flag bits: LC_ERR_ARG. */
+#define LC_ATTN_CAUSAL 1       /* key j visible to query i iff j <= i */
+#define LC_ATTN_V_TRANSPOSED 2 /* V as [B,H,D,N] */
+int lc_attn_fwd_f16_ex(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,
+                       int flags, void* stream);
 
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
@@ -309,6 +322,8 @@ int lc_attn_kernel_name(int N, int D, int v_transposed, int bf16, char* buf, int
 /* the same for a launch of BH = batch x heads problems: where the choice depends on how far the grid fills the GPU (D = 256, "attn_d512"
  * above) the name is the kernel THAT launch runs; BH <= 0 = lc_attn_kernel_name (a grid that fills the GPU) */
 int lc_attn_kernel_name_bh(int BH, int N, int D, int v_transposed, int bf16, char* buf, int buflen);
+/* the kernel lc_attn_fwd_f16_ex runs for these flags (never launches; without LC_ATTN_CAUSAL: lc_attn_kernel_name_bh's answer) */
+int lc_attn_kernel_name_ex(int BH, int N, int D, int flags, char* buf, int buflen);
 /* How often the overflow slow path of the merged-phase attention kernels (attn_w4u.hip, attn_w4i.hip) ran since the last reset:
  * out4 = { executions, sum of their KV half-tile indices, executions that saw a non-finite row sum, bit pattern (fp32) of the
  * last offending row sum }.  Synchronises the device (hipMemcpyFromSymbol).  out4 may be NULL (reset only). */

@@ -217,7 +217,7 @@ def build_diag(force: bool = False) -> Path:
     tools only; not part of the drop-in library).  The ablated phase statements are generated into lib/gen/ (never tracked)."""
     LIBDIR.mkdir(parents=True, exist_ok=True)
     out = LIBDIR / "liblc_diag.so"
-    srcs = sorted((CSRC / "diag").glob("*.hip")) + [CSRC / "lc_common.h", ROOT / "include" / "lc_diag.h", CSRC / "attn_w4i.hip", CSRC / "attn_w4u.hip", CSRC / "attn_mp.h", CSRC / "attn_fwd.hip",
+    srcs = sorted((CSRC / "diag").glob("*.hip")) + [CSRC / "lc_common.h", ROOT / "include" / "lc_diag.h", CSRC / "attn_w4i.hip", CSRC / "attn_w4u.hip", CSRC / "attn_w4u_body.inc", CSRC / "attn_mp.h", CSRC / "attn_fwd.hip", CSRC / "attn_fwd_body.inc",
                                                      CSRC / "hgemm_mid.hip", ROOT / "tools" / "gen_attn_w4i.py"]
     dg = _digest(srcs)
     if not force and _fresh(out, "diag", dg):

@@ -21,6 +21,7 @@ HGEMM_EDGE = 15  # the vectorised edge kernel (hgemm_edge.hip): any M, N; K % 8 
 HGEMM_RAGGED = 16  # ragged M / N, K % 32 == 0, N % 8 == 0: the tiled kernels, clamped 128 x 128 tiles of the mid-size kernel on what they do not divide
 HGEMM_KPAD = 17    # K % 32 != 0 on a large problem: zero-padded operand copies in the workspace + the tuned kernels
 ATTN_SPLIT_Q, ATTN_SHARED_QKV, ATTN_SHARED_KV, ATTN_TILING_QK, ATTN_TILING_QKV, ATTN_SPLIT_KV = range(6)
+ATTN_CAUSAL, ATTN_V_TRANSPOSED = 1, 2   # lc_attn_fwd_f16_ex / lc_attn_kernel_name_ex flags
 
 # every symbol include/lc_abi.h declares: name -> (restype, argtypes)
 _vp, _i, _cp, _fp, _ip = C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_int)
@@ -49,6 +50,7 @@ SYMBOLS = {
     "lc_hgemm_entry_info": (_i, [_cp, _ip, _ip]),
     "lc_attn_fwd_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_fwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lc_attn_fwd_f16_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -58,6 +60,7 @@ SYMBOLS = {
     "lc_hgemm_kernel_name": (_i, [_i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_kernel_name": (_i, [_i, _i, _i, _i, _cp, _i]),
     "lc_attn_kernel_name_bh": (_i, [_i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_kernel_name_ex": (_i, [_i, _i, _i, _i, _cp, _i]),
     "lc_attn_slowpath_stats": (_i, [C.POINTER(C.c_uint), _i]),
     "lc_timer_start": (_i, [_vp, C.POINTER(_vp)]),
     "lc_timer_stop": (_i, [_vp, _fp]),
@@ -345,11 +348,16 @@ def hgemm_entries():
 
 
 # ---- attention --------------------------------------------------------------------------------------
-def attn_fwd(q, k, v, o, v_transposed=False, family=ATTN_SPLIT_Q, acc_f32=False, stages=2):
+def attn_fwd(q, k, v, o, v_transposed=False, family=ATTN_SPLIT_Q, acc_f32=False, stages=2, causal=False):
+    """causal=True: row i attends to keys j <= i (lc_attn_fwd_f16_ex; fp16, D <= 128; family / acc_f32 / stages select nothing)."""
     import torch
     _need_gpu(q, k, v, o)
     assert q.dtype == k.dtype == v.dtype == o.dtype == torch.half
     B, H, N, D = _attn_dims(q, k, v, o, v_transposed)
+    if causal:
+        flags = ATTN_CAUSAL | (ATTN_V_TRANSPOSED if v_transposed else 0)
+        check(load().lc_attn_fwd_f16_ex(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, N, D, flags, _stream()), "lc_attn_fwd_f16_ex")
+        return o
     check(load().lc_attn_fwd_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, N, D, int(v_transposed), family,
                                  int(acc_f32), stages, _stream()), "lc_attn_fwd_f16")
     return o
@@ -428,10 +436,15 @@ def attn_slowpath_stats(reset=True):
     return [out[0], out[1], out[2], struct.unpack("f", struct.pack("I", out[3]))[0]]
 
 
-def attn_kernel_name(N, D, v_transposed=False, bf16=False, bh=None) -> str:
+def attn_kernel_name(N, D, v_transposed=False, bf16=False, bh=None, causal=False) -> str:
     """The kernel the dispatcher picks for sequence length N and head dim D; bh = batch x heads of the launch (None: a grid that fills
-    the GPU — the choice depends on it for D = 256 only)."""
+    the GPU — the choice depends on it for D = 256 only); causal=True: the kernel of attn_fwd(..., causal=True)."""
     buf = C.create_string_buffer(128)
+    if causal:
+        assert not bf16, "causal attention is fp16 only"
+        flags = ATTN_CAUSAL | (ATTN_V_TRANSPOSED if v_transposed else 0)
+        check(load().lc_attn_kernel_name_ex(int(bh) if bh else -1, N, D, flags, buf, 128), "lc_attn_kernel_name_ex")
+        return buf.value.decode()
     check(load().lc_attn_kernel_name_bh(int(bh) if bh else -1, N, D, int(v_transposed), int(bf16), buf, 128), "lc_attn_kernel_name_bh")
     return buf.value.decode()
 

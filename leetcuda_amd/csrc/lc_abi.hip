@@ -46,6 +46,7 @@ tune_t g_tune_attn_w4i_sched{1};              // schedule of attn_fwd_w4i_kernel
 tune_t g_tune_attn_nw{0};                    // attention kernel for D <= 128: 0 = auto, 513 / 515 / 517 / 514 / 8 / 4 / 2 (choose_attn_nw, lc_abi.h)
 tune_t g_tune_attn_d1024{0};                 // attn_bigd4's DMA spread in eighths of a phase: 0 = default (8), 2 / 4 / 6 (A/B knob)
 tune_t g_tune_attn_walk{0};                  // block walk of the merged-phase kernel under attn_nw = 0: 0 = auto by N, 1 / 2 / 3 = WALK 0 / 1 / 2
+tune_t g_tune_attn_causal_order{0};          // grid order of the causal merged-phase kernel: 0 = auto (choose_attn_causal), 1 = longest query block first, 2 = head-major (xcd_remap; same bits)
 tune_t g_tune_attn_split{0};                 // split-KV of the merged-phase kernel on grids that do not fill the GPU: 0 = auto (attn_split_auto), 1 = off, 2 / 4 / 8 / 16 = that many KV ranges per query block
 tune_t g_tune_hgemm_auto{LC_HGEMM_MFMA256W4Y};   // what LC_HGEMM_AUTO launches for large 256-tileable shapes (lc_tune_set "hgemm_auto")
 tune_t g_tune_hgemm_splitk{0};                 // split-K of the 128-tile blocks that serve border strips / the ragged last wave: 0 = auto (launch_mfma256), 1 = off, 2 .. 8 = that factor
@@ -70,14 +71,14 @@ tune_t g_tune_hgemm_raster{0};                 // block -> C tile map: 0 = auto 
 struct Knobs {
   int rule_cus, hgemm_auto, hgemm_tail, hgemm_tail_tile, hgemm_splitk, hgemm_128w, hgemm_mid, hgemm_mid_ns, hgemm_mid_splitk, hgemm_ragged,
       hgemm_ragged_tile, hgemm_ragged_fork, hgemm_kpad, hgemm_raster, w4y_sched, hgemm_stamps, w4_abl;
-  int attn_nw, attn_walk, attn_split, attn_calib, attn_d512, attn_d1024, attn_w4i_sched, attn_ablate;
+  int attn_nw, attn_walk, attn_split, attn_calib, attn_d512, attn_d1024, attn_w4i_sched, attn_ablate, attn_causal_order;
 };
 Knobs read_knobs() {
   return Knobs{g_tune_rule_cus, g_tune_hgemm_auto, g_tune_hgemm_tail, g_tune_hgemm_tail_tile, g_tune_hgemm_splitk, g_tune_hgemm_128w,
                g_tune_hgemm_mid, g_tune_hgemm_mid_ns, g_tune_hgemm_mid_splitk, g_tune_hgemm_ragged, g_tune_hgemm_ragged_tile,
                g_tune_hgemm_ragged_fork, g_tune_hgemm_kpad, g_tune_hgemm_raster, g_tune_w4y_sched, g_tune_hgemm_stamps, g_tune_w4_abl,
                g_tune_attn_nw, g_tune_attn_walk, g_tune_attn_split, g_tune_attn_calib, g_tune_attn_d512, g_tune_attn_d1024,
-               g_tune_attn_w4i_sched, g_tune_attn_ablate};
+               g_tune_attn_w4i_sched, g_tune_attn_ablate, g_tune_attn_causal_order};
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -577,10 +578,12 @@ void format_hgemm(const HgemmPlan& p, int M, int N, bool b_kn, char* buf, int bu
 //             merged-phase kernel for D = 96 / 32) [514];  LOCKSTEP  attn_fwd.hip with nw waves [8 / 4 / 2];  the rest: D >= 256 (use_bigd*)
 // [512] (round 2's attn_w4n) is an alias of [513]: attn_w4u<128, false, 0> IS that kernel; 256 / 260 / 516 were retired in round 4 with
 // attn_w4m.hip / attn_w8g.hip.
-enum class AKern { W4U, W4I, LOCKSTEP, BIGD4, BIGD6, BIGD7, BIGD2, BIGD3, COLSPLIT };
+// Causal calls (lc_attn_fwd_f16_ex, choose_attn_causal): W4U_CAUSAL  attn_fwd_w4u_causal_kernel<D, VT> (D = 64 / 128, N % 256 == 0; one block
+// per workgroup, order = "attn_causal_order");  LOCKSTEP_CAUSAL  attn_fwd_causal_kernel<D, nw, VT> (everything else with D <= 128).
+enum class AKern { W4U, W4I, LOCKSTEP, BIGD4, BIGD6, BIGD7, BIGD2, BIGD3, COLSPLIT, W4U_CAUSAL, LOCKSTEP_CAUSAL };
 struct AttnPlan {   // walk / nsplit: W4U; sched: W4I ("attn_w4i_sched"); nw: LOCKSTEP / COLSPLIT waves; span8: BIGD4's DMA spread in eighths
   AKern kern;         // of a phase ("attn_d1024"; 0 = the default, 8); abl: LOCKSTEP's LC_DIAG ablation ("attn_ablate"; D = 128, V as [B,H,N,D])
-  int walk, nsplit, sched, nw, span8, abl;
+  int walk, nsplit, sched, nw, span8, abl, order;   // order: W4U_CAUSAL's grid order
 };
 int attn_walk_auto(const Knobs& k, int N, int D) {
   // auto (lc_tune_set "attn_walk": 0 = this rule; measured, profiles/r3k, profiles/r4c_attn_walks.log, r5p_attn_walks.log): up to N = 4096 the
@@ -670,6 +673,27 @@ AttnPlan choose_attn_nw(const Knobs& k, int D, bool vt, int N, long bh) {
   return lockstep(2);
 }
 
+// causal, D <= 128: the causal merged-phase kernel for D = 64 / 128, N % 256 == 0 unless "attn_nw" = 8 / 4 / 2 forces the lock-step kernel
+// (the independent cross-check); everything else: the causal lock-step kernel with the waves the non-causal rule gives.  Neither splits KV
+// or switches kernels by grid size, so a causal result does not depend on B x H or the CU count.  Grid order of the merged-phase kernel
+// (p.order: 0 = longest block first, 1 = head-major; same bits): longest first up to 8 rounds of blocks per CU — the dispatcher then
+// fills the tail with short blocks: (4,32,4096,128) 1042 vs 977 TFLOP/s, (1,48,8192,64) 983 vs 851 —, head-major beyond, where the K / V
+// of the heads in flight no longer fit L2: (8,32,8192,128), 32 rounds, 1143 vs 954; config 4 1140 vs 926.  bh < 0: no
+// launch, no order.
+AttnPlan choose_attn_causal(const Knobs& k, int D, int N, long bh) {
+  AttnPlan p{};
+  const int want = k.attn_nw;
+  if ((D == 128 || D == 64) && N % 256 == 0 && want != 8 && want != 4 && want != 2) {
+    p.kern = AKern::W4U_CAUSAL;
+    const int o = k.attn_causal_order;
+    p.order = o == 1 ? 0 : o == 2 ? 1 : (bh > 0 && bh * (N / 256) > 8L * rule_cus(k)) ? 1 : 0;
+    return p;
+  }
+  p.kern = AKern::LOCKSTEP_CAUSAL;
+  p.nw = N % 256 == 0 && (want == 0 || want >= 8) ? 8 : N % 128 == 0 && (want == 0 || want >= 4) ? 4 : 2;
+  return p;
+}
+
 // D = 256 / 512 with N % 128 == 0: the full-width kernel (attn_bigd2.hip; V as [B,H,N,D], or — D = 256, the reach of the reference's
 // *_swizzle_qkv entries — as [B,H,D,N]) unless lc_tune_set "attn_d512" = 1 asks for round 1's column-split kernel (kept as the
 // independently written cross-check; it also serves N % 128 != 0 and D = 512 with V transposed).  D = 1024 with N % 64 == 0: the pair
@@ -702,14 +726,15 @@ bool use_bigd7(const Knobs& kn, int D, bool vt, int N, long bh) {
   return 16 * c7 <= 10 * c2;
 }
 
-// ONE decision per attention call (lc_attn_fwd_f16 / _bf16 launch it, lc_attn_kernel_name_bh reports it; bf16 launches have V as [B,H,N,D]).
-// Returns LC_OK or LC_ERR_HEADDIM.
-int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, AttnPlan* p) {
+// ONE decision per attention call (lc_attn_fwd_f16 / _bf16 / _f16_ex launch it, lc_attn_kernel_name_bh / _ex report it; bf16 launches have
+// V as [B,H,N,D]; causal: fp16, D <= 128).  Returns LC_OK or LC_ERR_HEADDIM.
+int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, bool causal, AttnPlan* p) {
   if (D == 32 || D == 64 || D == 96 || D == 128) {
     if (bf16) return LC_ERR_HEADDIM;
-    *p = choose_attn_nw(k, D, vt, N, bh);
+    *p = causal ? choose_attn_causal(k, D, N, bh) : choose_attn_nw(k, D, vt, N, bh);
     return LC_OK;
   }
+  if (causal) return LC_ERR_HEADDIM;
   *p = AttnPlan{};
   p->span8 = k.attn_d1024;
   p->nw = N % 128 == 0 ? 4 : 2;
@@ -945,6 +970,22 @@ int launch_lockstep(const AttnPlan& p, const half_t* Q, const half_t* K, const h
   if (p.nw == 4) return launch_attn<D, 4, VT>(Q, K, V, O, B, H, N, st);
   return launch_attn<D, 2, VT>(Q, K, V, O, B, H, N, st);
 }
+template <int D, int NW, bool VT>
+int launch_attn_causal(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st) {
+  auto kern = attn_fwd_causal_kernel<D, NW, VT>;
+  constexpr int lds = attn_lds_bytes<D, VT>();
+  if (int rc = set_dyn_lds(kern, lds)) return rc;
+  const int nqb = N / (NW * 32);
+  const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)nqb * B * H)), dim3(NW * 64), lds, st, Q, K, V, O, N, nqb, sl2);
+  return check_launch();
+}
+template <int D, bool VT>
+int launch_lockstep_causal(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st) {
+  if (p.nw == 8) return launch_attn_causal<D, 8, VT>(Q, K, V, O, B, H, N, st);
+  if (p.nw == 4) return launch_attn_causal<D, 4, VT>(Q, K, V, O, B, H, N, st);
+  return launch_attn_causal<D, 2, VT>(Q, K, V, O, B, H, N, st);
+}
 
 template <int D, int NW, bool VT, bool BF16 = false>
 int launch_attn_bigd(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N,
@@ -990,6 +1031,14 @@ int launch_attn_plan(const AttnPlan& p, const half_t* Q, const half_t* K, const 
       return D == 256   ? launch_colsplit<256, VT>(p, bf16, Q, K, V, O, B, H, N, st)
              : D == 512 ? launch_colsplit<512, VT>(p, bf16, Q, K, V, O, B, H, N, st)
                         : launch_colsplit<1024, VT>(p, bf16, Q, K, V, O, B, H, N, st);
+    case AKern::W4U_CAUSAL:
+      if (D == 128) return VT ? launch_attn_w4u_causal_d128t(Q, K, V, O, B, H, N, p.order, st) : launch_attn_w4u_causal_d128(Q, K, V, O, B, H, N, p.order, st);
+      return VT ? launch_attn_w4u_causal_d64t(Q, K, V, O, B, H, N, p.order, st) : launch_attn_w4u_causal_d64(Q, K, V, O, B, H, N, p.order, st);
+    case AKern::LOCKSTEP_CAUSAL:
+      return D == 32   ? launch_lockstep_causal<32, VT>(p, Q, K, V, O, B, H, N, st)
+             : D == 64 ? launch_lockstep_causal<64, VT>(p, Q, K, V, O, B, H, N, st)
+             : D == 96 ? launch_lockstep_causal<96, VT>(p, Q, K, V, O, B, H, N, st)
+                       : launch_lockstep_causal<128, VT>(p, Q, K, V, O, B, H, N, st);
   }
   return LC_ERR_HEADDIM;
 }
@@ -1060,7 +1109,7 @@ int lc_attn_kernel_name_bh(int BH, int N, int D, int v_transposed, int bf16, cha
   if (!buf || buflen < 8 || N <= 0 || N % KVB != 0) return LC_ERR_ARG;
   if (D > 0 && (size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;   // (mirrors lc_attn_fwd_f16)
   AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, v_transposed != 0, bf16 != 0, &p)) return rc;
+  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, v_transposed != 0, bf16 != 0, false, &p)) return rc;
   const char* vt = v_transposed ? "true" : "false";
   const char* bf = bf16 ? "true" : "false";
   switch (p.kern) {
@@ -1075,7 +1124,24 @@ int lc_attn_kernel_name_bh(int BH, int N, int D, int v_transposed, int bf16, cha
     case AKern::BIGD2: snprintf(buf, buflen, "attn_fwd_bigd2_kernel<%d,%s,%s>", D, v_transposed ? "false" : bf, vt); break;   // (V transposed: fp16 only)
     case AKern::BIGD3: snprintf(buf, buflen, "attn_fwd_bigd3_kernel<%d,%s>", D, bf); break;
     case AKern::COLSPLIT: snprintf(buf, buflen, "attn_fwd_bigd_kernel<%d,%d,%d,%s,%s>", D, D > 256 ? 256 : D, p.nw, vt, bf); break;
+    case AKern::W4U_CAUSAL: snprintf(buf, buflen, "attn_fwd_w4u_causal_kernel<%d,%s>", D, vt); break;
+    case AKern::LOCKSTEP_CAUSAL: snprintf(buf, buflen, "attn_fwd_causal_kernel<%d,%d,%s>", D, p.nw, vt); break;
   }
+  return LC_OK;
+}
+
+int lc_attn_kernel_name_ex(int BH, int N, int D, int flags, char* buf, int buflen) {
+  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
+  const int vt = (flags & LC_ATTN_V_TRANSPOSED) != 0;
+  if (!(flags & LC_ATTN_CAUSAL)) return lc_attn_kernel_name_bh(BH, N, D, vt, 0, buf, buflen);
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  if (N <= 0 || N % KVB != 0) return LC_ERR_SHAPE;   // (the codes lc_attn_fwd_f16_ex returns)
+  if (D > 0 && (size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;
+  AttnPlan p;
+  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, vt != 0, false, true, &p)) return rc;
+  const char* vts = vt ? "true" : "false";
+  if (p.kern == AKern::W4U_CAUSAL) snprintf(buf, buflen, "attn_fwd_w4u_causal_kernel<%d,%s>", D, vts);
+  else snprintf(buf, buflen, "attn_fwd_causal_kernel<%d,%d,%s>", D, p.nw, vts);
   return LC_OK;
 }
 
@@ -1118,6 +1184,7 @@ const Knob kKnobs[] = {
     {"attn_nw", &g_tune_attn_nw, 0, ok_attn_nw, false},
     {"attn_walk", &g_tune_attn_walk, 0, ok_03, false},
     {"attn_split", &g_tune_attn_split, 0, ok_split, false},
+    {"attn_causal_order", &g_tune_attn_causal_order, 0, ok_02, false},
     {"attn_bigd_map", &g_tune_attn_bigd_map, 0, ok_02, false},
     {"attn_bigd_stagger", &g_tune_attn_bigd_stagger, 0, ok_02, false},
     {"attn_d1024", &g_tune_attn_d1024, 0, ok_span8, false},
@@ -1298,11 +1365,31 @@ int lc_attn_fwd_f16(const void* Q, const void* K, const void* V, void* O, int B,
   if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return LC_ERR_SHAPE;
   if (int rc = launch_guard()) return rc;
   AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, v_transposed != 0, false, &p)) return rc;
+  if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, v_transposed != 0, false, false, &p)) return rc;
   auto q = static_cast<const half_t*>(Q), k = static_cast<const half_t*>(K), v = static_cast<const half_t*>(V);
   hipStream_t st = static_cast<hipStream_t>(stream);
   return v_transposed ? launch_attn_plan<true>(p, q, k, v, static_cast<half_t*>(O), B, H, N, D, false, st)
                       : launch_attn_plan<false>(p, q, k, v, static_cast<half_t*>(O), B, H, N, D, false, st);
+}
+
+int lc_attn_fwd_f16_ex(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, int flags, void* stream) {
+  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
+  const int vt = (flags & LC_ATTN_V_TRANSPOSED) != 0;
+  if (!(flags & LC_ATTN_CAUSAL)) return lc_attn_fwd_f16(Q, K, V, O, B, H, N, D, vt, LC_ATTN_SPLIT_Q, 0, 2, stream);
+  // (the argument checks of lc_attn_fwd_f16)
+  if (!Q || !K || !V || !O) return LC_ERR_ARG;
+  if (B <= 0 || H <= 0 || N <= 0 || D <= 0) return LC_ERR_SHAPE;
+  if (N % KVB != 0) return LC_ERR_SHAPE;
+  if ((size_t)B * H * (size_t)(N / 64) > 0x7fffffffull) return LC_ERR_SHAPE;
+  if ((size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;
+  if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return LC_ERR_SHAPE;
+  if (int rc = launch_guard()) return rc;
+  AttnPlan p;
+  if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, vt != 0, false, true, &p)) return rc;
+  auto q = static_cast<const half_t*>(Q), k = static_cast<const half_t*>(K), v = static_cast<const half_t*>(V);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return vt ? launch_attn_plan<true>(p, q, k, v, static_cast<half_t*>(O), B, H, N, D, false, st)
+            : launch_attn_plan<false>(p, q, k, v, static_cast<half_t*>(O), B, H, N, D, false, st);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,
@@ -1314,7 +1401,7 @@ int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B
   if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return LC_ERR_SHAPE;
   if (int rc = launch_guard()) return rc;
   AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, false, true, &p)) return rc;
+  if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, false, true, false, &p)) return rc;
   // (raw 16-bit lanes; the kernel flavour decodes bf16)
   return launch_attn_plan<false>(p, static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V),
                                  static_cast<half_t*>(O), B, H, N, D, true, static_cast<hipStream_t>(stream));

@@ -235,6 +235,11 @@ int launch_attn_w4u_d128(const half_t* Q, const half_t* K, const half_t* V, half
 int launch_attn_w4u_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);   // V as [B,H,D,N]
 int launch_attn_w4u_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);
 int launch_attn_w4u_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);    // V as [B,H,D,N]
+// causal (N % 256 == 0; attn_fwd_w4u_causal_kernel): order 0 = grid longest block first, 1 = head-major (lc_abi.hip choose_attn_causal)
+int launch_attn_w4u_causal_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
+int launch_attn_w4u_causal_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
+int launch_attn_w4u_causal_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
+int launch_attn_w4u_causal_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
 int diag_attn_slowpath_u_d128(unsigned* out4, int reset);   // slow-path counters of each unit's kernels (host copy; resets when asked)
 int diag_attn_slowpath_u_d128t(unsigned* out4, int reset);
 int diag_attn_slowpath_u_d64(unsigned* out4, int reset);

@@ -77,6 +77,18 @@ int W4U_CAT(launch_attn_w4u_, W4U_TAG)(const half_t* Q, const half_t* K, const h
   if (walk == 1) return launch_w4u_walk<1>(Q, K, V, O, B, H, N, ncu, nblk, st);
   return launch_w4u_walk<2>(Q, K, V, O, B, H, N, ncu, nblk, st);
 }
+// causal (N % 256 == 0): one 256-row query block per workgroup, walking KV tiles 0 .. 4 b + 3; order 0 = longest block first, 1 = head-major
+int W4U_CAT(launch_attn_w4u_causal_, W4U_TAG)(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order,
+                                              hipStream_t st) {
+  constexpr int D = W4U_D;
+  const size_t nblk = (size_t)(N / 256) * B * H;
+  if (nblk > (size_t)INT_MAX) return LC_ERR_SHAPE;
+  const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
+  auto kern = attn_fwd_w4u_causal_kernel<D, W4U_VT>;
+  if (int rc = set_dyn_lds(kern, W4U<D>::LDS)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), W4U<D>::LDS, st, Q, K, V, O, N, N / 256, sl2, (int)nblk, order);
+  return check_launch();
+}
 // slow-path counters of THIS unit's kernels, added onto out4[0..2] (out4[3]: last offender, taken when this unit has one)
 int W4U_CAT(diag_attn_slowpath_u_, W4U_TAG)(unsigned* out4, int reset) {
   unsigned mine[4] = {0, 0, 0, 0};

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:bf16][:zero][:vt][:nw=K][:walk=K][:split=K][:d512=K][:sched=K]   (vt = V handed over as [B,H,D,N]; knobs = lc_tune_set keys attn_nw / attn_walk / attn_split / attn_d512 / attn_w4i_sched)
+   spec = B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+          causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
+          instead of this library (context only); knobs = lc_tune_set keys attn_nw / attn_walk / attn_split / attn_d512 / attn_w4i_sched /
+          attn_causal_order)
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
-cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs)."""
+cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
+causal: half of that, the flash-attn convention) and the median time per call."""
 import sys
 from pathlib import Path
 
@@ -26,7 +30,8 @@ import os  # noqa: E402
 if os.environ.get("LC_AB_LIB"):    # A/B of two builds on one box: point the ctypes view at another copy of the library
     capi.LIB_PATH = Path(os.environ["LC_AB_LIB"]).resolve()
 capi.load()
-KNOBS = {"bigd_stagger": "attn_bigd_stagger", "bigd_map": "attn_bigd_map", "nw": "attn_nw", "walk": "attn_walk", "d512": "attn_d512", "d1024": "attn_d1024", "sched": "attn_w4i_sched", "split": "attn_split"}
+KNOBS = {"bigd_stagger": "attn_bigd_stagger", "bigd_map": "attn_bigd_map", "nw": "attn_nw", "walk": "attn_walk", "d512": "attn_d512", "d1024": "attn_d1024", "sched": "attn_w4i_sched", "split": "attn_split",
+         "order": "attn_causal_order"}
 cache = {}
 
 
@@ -45,7 +50,7 @@ def tensors(B, H, N, D, bf16, zero):
 def run(spec):
     shape, *opts = spec.split(":")
     B, H, N, D = (int(x) for x in shape.split(","))
-    bf16, zero, vt = "bf16" in opts, "zero" in opts, "vt" in opts
+    bf16, zero, vt, causal, sdpa = "bf16" in opts, "zero" in opts, "vt" in opts, "causal" in opts, "sdpa" in opts
     knobs = {KNOBS[o.split("=")[0]]: int(o.split("=")[1]) for o in opts if "=" in o}
     q, k, v, o = tensors(B, H, N, D, bf16, zero)
     if vt:
@@ -53,8 +58,13 @@ def run(spec):
     for kk, vv in knobs.items():
         capi.tune(kk, vv)
     try:
-        name = capi.attn_kernel_name(N, D, vt, bf16, bh=B * H)
-        step = (lambda: capi.attn_fwd_bf16(q, k, v, o)) if bf16 else (lambda: capi.attn_fwd(q, k, v, o, v_transposed=vt))
+        if sdpa:
+            name = "torch sdpa" + (" is_causal" if causal else "")
+            vv = v.transpose(-2, -1) if vt else v
+            step = lambda: torch.nn.functional.scaled_dot_product_attention(q, k, vv, is_causal=causal)  # noqa: E731
+        else:
+            name = capi.attn_kernel_name(N, D, vt, bf16, bh=B * H, causal=causal)
+            step = (lambda: capi.attn_fwd_bf16(q, k, v, o)) if bf16 else (lambda: capi.attn_fwd(q, k, v, o, v_transposed=vt, causal=causal))
         for _ in range(3):
             step()
         torch.cuda.synchronize()
@@ -74,15 +84,19 @@ def run(spec):
     finally:
         for kk in knobs:
             capi.tune(kk, capi.tune_items()[kk][1])      # back to the library default
-    return name, host.mha_matmul_flops(B, H, N, D) / ms * 1e-9, ms
+    return name, host.mha_matmul_flops(B, H, N, D) * (0.5 if causal else 1.0) / ms * 1e-9, ms
 
 
 res = {s: [] for s in args}
+times = {s: [] for s in args}
 names = {}
 for r in range(rounds):
     for s in args:
         names[s], tf, ms = run(s)
         res[s].append(tf)
+        times[s].append(ms)
+if any("causal" in s.split(":") for s in args):
+    print("(causal TFLOP/s count half of 4 B H N^2 D: the flash-attn convention)", flush=True)
 for s in args:
-    v = sorted(res[s])
-    print(f"RATE {s:34s} {names[s]:44s} median {v[len(v) // 2]:7.1f}  best {v[-1]:7.1f}  worst {v[0]:7.1f} TFLOP/s", flush=True)
+    v, t = sorted(res[s]), sorted(times[s])
+    print(f"RATE {s:34s} {names[s]:44s} median {v[len(v) // 2]:7.1f}  best {v[-1]:7.1f}  worst {v[0]:7.1f} TFLOP/s  {t[len(t) // 2] * 1e3:9.1f} us", flush=True)
