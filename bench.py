@@ -2,7 +2,7 @@
 """bench.py — headline benchmark of the hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hgemm|attn|attn_cfg4|attn_d512]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--quick] [--no-attention] [--no-cpu-baseline] [--sweep]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,8 +15,8 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
 
   hgemm (default)   one C[8192,8192] = A·B fp16 GEMM per rank (BASELINE config 2), TN storage for B
                     (the layout of the reference's fastest kernel, hgemm_mma_stage_tn_cute.cu).  `value` is THIS workload at
-                    every N (HGEMM does not shard in north_star: "replicas only" -> weak scaling); the attention half of the
-                    metric rides in the same keys at every N: blocks "attention" (config 3) / "attention_cfg4" (config 4, strong
+                    every N (HGEMM does not shard in north_star: "replicas only" -> weak scaling); with --full the attention half
+                    of the metric rides in the same keys at every N: blocks "attention" (config 3) / "attention_cfg4" (config 4, strong
                     scaling over the ranks) and the flat scalars roofline.attn_cfg3_* / roofline.attn_cfg4_* (+ cpu_baseline.attn_*),
                     which survive the driver's parse of the line.
   attn              FlashAttention-2 forward B=4,H=32,S=4096,D=128 (config 3); N > 1: the 128 (batch,head)
@@ -24,7 +24,11 @@ A "step" is one pass of the hot path over one batch of synthetic input already r
   attn_cfg4         config 4: B=32,H=32,S=8192,D=128 through the shared-QKV entry, batch-sharded over N ranks -> "strong".
   attn_d512         config 5a: (1,48,8192,512) through the tiling-QKV entry (fp16) and lc_attn_fwd_bf16; heads sharded.
 
-The default run reports HGEMM as `value` and carries, in the same JSON line: "vendor_tflops" (same-run hipBLASLt TN /
+A plain run does only what its headline needs: set-up, the W warm-up and K timed steps, --dump-outputs and the line, whose
+"roofline" and "per_rank" rows come from those same K launches.  Everything else runs with --full only; --quick, --no-attention,
+--no-cpu-baseline and --sweep choose among it.  With --full every workload adds "cpu_baseline", attn_cfg4 its output "checksum",
+and the default workload carries, in the same JSON line: "calibration" (the split-KV rule's constants measured on this device,
+before the headline's timed region), "vendor_tflops" (same-run hipBLASLt TN /
 NN = the reference's cuBLAS comparator), "uniform_tflops" (the same kernel on uniform[-1,1) operands, the fill the
 programming guide quotes), "sustained" (>= 2 s of back-to-back launches with the effective shader clock),
 "attention" (config 3), "attention_cfg4" (config 4, aggregate over ranks), "attention_d512" (config 5a), "attention_d256"
@@ -82,15 +86,19 @@ def parse(argv=None):
     ap.add_argument("--layout", default="tn", choices=["tn", "nn"])
     ap.add_argument("--variant", default="auto", choices=sorted(VARIANT))
     ap.add_argument("--mnk", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-attention", action="store_true", help="skip the attention blocks of the default line")
-    ap.add_argument("--quick", action="store_true", help="headline + config-3 attention only (plumbing tests)")
-    ap.add_argument("--sustain-seconds", type=float, default=2.0)
-    ap.add_argument("--sweep", action="store_true", help="also print a per-variant table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: comparators, calibration, other shapes and precisions, CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-attention", action="store_true", help="(--full) skip the attention blocks of the default line")
+    ap.add_argument("--quick", action="store_true", help="(--full) headline + config-3 attention only (plumbing tests)")
+    ap.add_argument("--sustain-seconds", type=float, default=2.0, help="(--full) length of the HGEMM `sustained` figure")
+    ap.add_argument("--sweep", action="store_true", help="(--full) also print a per-variant table to stderr")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy (float32)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.sweep and not a.full:
+        ap.error("--sweep is part of a --full run")
     if a.workload == "attn_sharded":     # round-1 name of config 4
         a.workload = "attn_cfg4"
     return a
@@ -371,7 +379,7 @@ def bench_hgemm(w, args):
             "note": "L2-compulsory bytes of 256x256 tiles under the XCD-aware raster (every A/B panel once per XCD wave of "
                     "4x8 tiles + C once); the PMC figure equals it: no wasted re-reads, 4.3x algorithmic is this tile "
                     "size's floor with a 4 MiB L2 per XCD"}
-    if w.rank == 0 and w.size == 1 and not args.quick:
+    if args.full and w.rank == 0 and w.size == 1 and not args.quick:
         # same-run comparator: hipBLASLt behind the reference's cuBLAS entry points (config 2: "rocprof vs rocBLAS")
         # Both sides as >= 1 s of back-to-back launches: at 8192^3 either kernel sits at the board's power cap, and a 20-launch
         # burst right behind another kernel inherits that kernel's clock (round-2 finding: short bursts put hipBLASLt 10 %
@@ -469,7 +477,7 @@ def bench_attn(w, args, cfg4=False, steps=None, warmup=None, prewarm=PREWARM, du
     ranks = per_rank_rows(w, ms_local, flops_local / (ms_local * 1e-3) * 1e-12)
     ms_kernel = max(r["kernel_ms"] for r in ranks)
     checksum = None
-    if cfg4:
+    if cfg4 and args.full:
         # sum of the fp16 BIT PATTERNS of O as integers: exact, additive over shards (|sum| < 2^46: exact in the fp64 timing gather too)
         loc = sum(int(o[b].view(torch.int16).sum(dtype=torch.int64).item()) for b in range(b_loc))
         checksum = int(sum(r[0] for r in lcd.gather_row(w, [float(loc)]).tolist()))
@@ -888,22 +896,24 @@ def run(args):
     capi.load()
     capi.require_production()        # a LC_DIAG=1 library can produce WRONG results
     capi.device_check()
-    # the split-KV launch rule's constants measured on THIS device (a few milliseconds, outside every timed region); config 3 / 4 fill the
-    # GPU and never split — the published small shapes of bench blocks / the reference's own sweep do
-    try:
-        calibration = capi.tune_calibrate()
-    except Exception as e:   # never fatal: the built-in constants stay
-        calibration = {"adopted": False, "error": repr(e)}
+    calibration = None
+    if args.full:
+        # the split-KV launch rule's constants measured on THIS device (a few milliseconds, outside every timed region); config 3 / 4 fill
+        # the GPU and never split — the published small shapes of bench blocks / the reference's own sweep do
+        try:
+            calibration = capi.tune_calibrate()
+        except Exception as e:   # never fatal: the built-in constants stay
+            calibration = {"adopted": False, "error": repr(e)}
 
     blocks = {}
     if args.workload == "hgemm":
         # `value` is ONE workload at every N (round-4 advisor / verdict): the HGEMM 8192^3 replicas ("replicas only": HGEMM does not
-        # shard in north_star) -> weak scaling, value(N) / (N value(1)) is a meaningful efficiency.  The attention half of BASELINE's
-        # metric rides in the SAME keys at every N: blocks "attention" (config 3) and "attention_cfg4" (config 4, strong scaling: total
-        # work fixed, (batch, head) problems sharded over the ranks), and — because the driver's parsed record keeps only the scalar
-        # fields of `roofline` / `cpu_baseline` — as flat roofline.attn_cfg3_* / roofline.attn_cfg4_* scalars (compact_attn below).
+        # shard in north_star) -> weak scaling, value(N) / (N value(1)) is a meaningful efficiency.  With --full the attention half of
+        # BASELINE's metric rides in the SAME keys at every N: blocks "attention" (config 3) and "attention_cfg4" (config 4, strong
+        # scaling: total work fixed, (batch, head) problems sharded over the ranks), and — because the driver's parsed record keeps only
+        # the scalar fields of `roofline` / `cpu_baseline` — as flat roofline.attn_cfg3_* / roofline.attn_cfg4_* scalars (compact_attn below).
         main_res = bench_hgemm(w, args)
-        if not args.no_attention:
+        if args.full and not args.no_attention:
             blocks["attention"] = bench_attn(w, args, cfg4=False, steps=max(5, args.steps // 5), warmup=1)
             if not args.quick:
                 blocks["attention_cfg4"] = bench_attn(w, args, cfg4=True, steps=3, warmup=1, prewarm=1)
@@ -913,7 +923,7 @@ def run(args):
                 blocks["attention_d256"] = bench_attn_d256(w, args)
                 blocks["attention_d1024"] = bench_attn_d1024(w, args)
                 blocks["attention_d64"] = bench_attn_d64(w, args)
-        if not args.quick and w.size == 1:
+        if args.full and not args.quick and w.size == 1:
             blocks["fp8_gemm"] = bench_fp8(w, args)
     elif args.workload == "attn":
         main_res = bench_attn(w, args, cfg4=False, dump=True)
@@ -944,8 +954,9 @@ def run(args):
         "frac_of_peak": main_res["value"] / (PEAK * w.size),
         "roofline": main_res["roofline"],
         "library": capi.build_info()[0],
-        "calibration": calibration,
     }
+    if calibration is not None:
+        out["calibration"] = calibration
     for key in ("vendor_tflops", "uniform_tflops", "sustained", "fp8_tflops", "fp16", "bf16", "n_ranks", "per_rank", "headline_note", "checksum"):
         if key in main_res:
             out[key] = main_res[key]
@@ -989,7 +1000,7 @@ def run(args):
     if also:
         head["also"] = also
     out["roofline"] = head
-    if w.rank == 0 and not args.no_cpu_baseline and not args.quick:
+    if args.full and w.rank == 0 and not args.no_cpu_baseline and not args.quick:
         # N = 1: the full baseline (bounded samples, ~20 s).  N > 1 (round-4 verdict): rank 0 still reports one, on a smaller budget —
         # the other ranks are done and wait in shutdown, nothing of this is inside a timed region.
         budget = 12.0 if w.size == 1 else 4.0

@@ -26,7 +26,7 @@ def _run(args, env_extra=None, timeout=900):
 
 
 def test_bench_single_gpu_quick_line():
-    out = _run(["--steps", "5", "--warmup", "2", "--quick"])
+    out = _run(["--full", "--steps", "5", "--warmup", "2", "--quick"])
     assert out["n_gpus"] == 1 and out["steps"] == 5 and out["unit"] == "TFLOP/s" and out["higher_is_better"] is True
     assert out["metric"].startswith("achieved fp16 TFLOPS vs MI355X MFMA peak")
     r = out["roofline"]
@@ -38,6 +38,21 @@ def test_bench_single_gpu_quick_line():
     assert out["attention"]["roofline"]["kernel"].startswith("attn_fwd_")
     assert out["roofline"]["attn_cfg3_tflops"] == out["attention"]["value"] and out["roofline"]["attn_cfg3_n_ranks"] == 1
     assert "LC_DIAG=0" in out["library"]
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """Without --full a run times its steps and prints the headline from them: no comparator, calibration, other workload or CPU
+    baseline runs, and none appears in the line."""
+    out = _run(["--steps", "5", "--warmup", "2"])
+    assert out["n_gpus"] == 1 and out["steps"] == 5 and out["warmup"] == 2 and out["unit"] == "TFLOP/s" and out["higher_is_better"] is True
+    assert out["metric"].startswith("achieved fp16 TFLOPS vs MI355X MFMA peak") and out["dtype"] == "f16 (fp32 MFMA accumulate)"
+    assert out["value"] == pytest.approx(2 * 8192 ** 3 / (out["ms_per_step"] * 1e-3) * 1e-12, rel=1e-6)
+    r = out["roofline"]
+    assert r["kernel"].startswith("hgemm_w4y_kernel<false,") and 0 < r["kernel_ms"] <= out["ms_per_step"] * 1.02
+    for key in ("calibration", "vendor_tflops", "uniform_tflops", "sustained", "attention", "attention_cfg4", "projected_scaling",
+                "attention_d512", "fp8_gemm", "cpu_baseline"):
+        assert key not in out, key
+    assert list(out)[-1] == "headline"
 
 
 def test_bench_dump_outputs_hold_the_last_step(tmp_path):
@@ -98,7 +113,7 @@ def test_bench_default_workload_keeps_one_headline_workload_at_every_n():
     """Round-4 advisor (medium) + verdict (weak #4): `value` used to be HGEMM at N = 1 and config 4 at N > 1, so value(N) / (N value(1))
     compared two workloads.  Now `value` is the HGEMM 8192^3 replicas at every N (weak scaling) and config 3 / config 4 ride in the same
     keys at every N — blocks and flat roofline.attn_* scalars; rank 0 reports a cpu_baseline at N > 1 too."""
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"LC_DIST_BACKEND": "gloo"}, timeout=1500)
+    out = _run(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1"], {"LC_DIST_BACKEND": "gloo"}, timeout=1500)
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 3
     assert "HGEMM M=N=K=8192" in out["config"]["workload"] and out["roofline"]["kernel"].startswith("hgemm_w4y_kernel")
     assert out["value"] == pytest.approx(2 * 2 * 8192 ** 3 / (out["ms_per_step"] * 1e-3) * 1e-12, rel=1e-6)      # two replicas
@@ -119,7 +134,7 @@ def test_bench_default_line_carries_the_vendor_comparator_first():
     """Round-5 verdict (weak #4): the one same-node comparator behind the HGEMM claim must sit where the driver's parse of `roofline` keeps it —
     right behind the contract's six fields — incl. the four extra points of the reference's default sweep (1024 / 2048 / 2816 / 3072: the sizes
     where other kernels than the 8192^3 one run); the mid-size kernel must be the one that serves 2048 and 2816 on a 256-CU device."""
-    out = _run(["--steps", "5", "--warmup", "2", "--no-attention", "--no-cpu-baseline"], timeout=900)
+    out = _run(["--full", "--steps", "5", "--warmup", "2", "--no-attention", "--no-cpu-baseline"], timeout=900)
     r = out["roofline"]
     assert list(r)[:12] == ["bound", "achieved", "peak", "unit", "frac", "traffic", "vendor_tn_ratio", "vendor_nn_ratio", "vendor_tn_ratio_1024",
                             "vendor_tn_ratio_2048", "vendor_tn_ratio_2816", "vendor_tn_ratio_3072"]
@@ -134,7 +149,7 @@ def test_bench_default_line_carries_the_vendor_comparator_first():
 def test_bench_projected_scaling_block_at_one_gpu():
     """until an 8-GPU node exists, the W-rank shard shapes of config 4 are timed one after the other on one GPU and
     reported as PROJECTED, separately from anything measured."""
-    out = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"], timeout=1500)
+    out = _run(["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], timeout=1500)
     ps = out["projected_scaling"]
     assert "PROJECTED" in ps["label"] and set(ps["ranks"]) == {"1", "2", "4", "8"}
     assert ps["ranks"]["8"]["shard"] == [4, 32, 8192, 128] and ps["ranks"]["2"]["shard"] == [16, 32, 8192, 128]
@@ -160,7 +175,7 @@ def test_bench_default_line_at_eight_ranks_on_one_gpu():
     n = torch.cuda.device_count()
     if n < 8:
         pytest.skip(f"needs 8 GPUs (one per rank), found {n}")
-    out = _run(["--gpus", "8", "--steps", "2", "--warmup", "1"], {"LC_DIST_BACKEND": "gloo"}, timeout=2400)
+    out = _run(["--full", "--gpus", "8", "--steps", "2", "--warmup", "1"], {"LC_DIST_BACKEND": "gloo"}, timeout=2400)
     assert out["n_gpus"] == 8 and out["scaling"] == "weak" and "HGEMM M=N=K=8192" in out["config"]["workload"]
     r = out["roofline"]
     assert list(r)[:6] == ["bound", "achieved", "peak", "unit", "frac", "traffic"]
@@ -174,5 +189,5 @@ def test_bench_default_line_at_eight_ranks_on_one_gpu():
     assert sorted(x["rank"] for x in ranks) == list(range(8)) and all(x["kernel_ms"] > 0 and (x["sclk_ghz"] is None or 0.3 < x["sclk_ghz"] < 3.0) for x in ranks)
     assert len(out["per_rank"]["ranks"]) == 8
     assert isinstance(out["cpu_baseline"], dict) and out["cpu_baseline"]["value"] > 0
-    one = _run(["--workload", "attn_cfg4", "--steps", "2", "--warmup", "1", "--quick"], timeout=1500)
+    one = _run(["--full", "--workload", "attn_cfg4", "--steps", "2", "--warmup", "1", "--quick"], timeout=1500)
     assert one["n_gpus"] == 1 and one["checksum"] == c4["checksum"] == r["attn_cfg4_checksum"] != 0

@@ -555,3 +555,16 @@ def test_bench_dump_sample_is_fixed_and_bounded(tmp_path):
     assert idx == sorted(idx) and len(set(idx)) == len(idx)
     bench.capture_output(argparse.Namespace(dump_outputs=None), w, "none", small)
     assert "none" not in bench.capture_output.arrays
+
+
+def test_bench_full_is_off_by_default_and_sweep_needs_it():
+    """bench.py measures only its headline unless --full is given.  --sweep asks for more work, so without --full it is refused
+    rather than ignored."""
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    import bench
+    assert not bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full
+    assert bench.parse(["--full", "--quick"]).full
+    assert bench.parse(["--full", "--sweep"]).sweep
+    with pytest.raises(SystemExit):
+        bench.parse(["--sweep"])

@@ -69,8 +69,8 @@ def main(tag: str):
                         "median_us": v2[len(v2) // 2], **meta[k]}
         (out / f"{tag}_kernel_stats.json").write_text(json.dumps(stats, indent=1))
         lines = [f"# rocprofv3 --kernel-trace --stats — {tag}", "",
-                 "command: see profiles/README.md (rounds r02p / r03z: `rocprofv3 --kernel-trace --stats -- python bench.py "
-                 "--steps 20 --warmup 2 --no-cpu-baseline`, i.e. the bench command itself)", "",
+                 "command: see profiles/README.md (tools/profile_round.sh: `rocprofv3 --kernel-trace --stats -- python bench.py "
+                 "--full --steps 20 --warmup 2 --no-cpu-baseline`, i.e. the bench command itself)", "",
                  "| kernel | calls | avg µs | median µs | min µs | max µs | VGPR | LDS B | grid |", "|---|---|---|---|---|---|---|---|---|"]
         for k, s in sorted(stats.items(), key=lambda kv: -kv[1]["avg_us"]):
             lines.append(f"| `{k}` | {s['calls']} | {s['avg_us']:.1f} | {s['median_us']:.1f} | {s['min_us']:.1f} | "
