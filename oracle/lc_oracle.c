@@ -223,9 +223,11 @@ static inline float v_at(const float* v, int n, int d, int N, int D, int vt) {
   return vt ? v[(size_t)d * N + n] : v[(size_t)n * D + d];
 }
 
-/* Nq query rows against N keys per (b,h) problem (Nq == N for the plain entry points). */
+/* Nq query rows against N keys per (b,h) problem (Nq == N for the plain entry points).  causal (Nq == N): row i sees keys
+ * 0 .. min(i + diag_offset, N - 1) only — the masked keys are skipped, not computed, and the visible ones are summed in the
+ * same order as a non-causal call on keys 0 .. i would sum them; a row that sees no key is all zeros. */
 static void attn_exact_impl(const uint16_t* Q, const uint16_t* K, const uint16_t* V, void* O, int B,
-                            int H, int Nq, int N, int D, int vt, int out_f32) {
+                            int H, int Nq, int N, int D, int vt, int out_f32, int causal, int diag_offset) {
   const size_t per = (size_t)N * D;
   const size_t perq = (size_t)Nq * D;
   const double scale = 1.0 / sqrt((double)D); /* split_q.cu:79 */
@@ -246,8 +248,13 @@ static void attn_exact_impl(const uint16_t* Q, const uint16_t* K, const uint16_t
         const float* qb = q + bh * perq + (size_t)i * D;
         const float* kb = k + bh * per;
         const float* vb = v + bh * per;
+        int nk = N; /* keys 0 .. nk - 1 are visible */
+        if (causal) {
+          const long last = (long)i + diag_offset;
+          nk = last < 0 ? 0 : last >= N ? N : (int)last + 1;
+        }
         double mx = -INFINITY;
-        for (int j = 0; j < N; ++j) {
+        for (int j = 0; j < nk; ++j) {
           double acc = 0.0;
           const float* kr = kb + (size_t)j * D;
           for (int d = 0; d < D; ++d) acc += (double)qb[d] * (double)kr[d];
@@ -256,7 +263,7 @@ static void attn_exact_impl(const uint16_t* Q, const uint16_t* K, const uint16_t
         }
         double l = 0.0;
         for (int d = 0; d < D; ++d) o[d] = 0.0;
-        for (int j = 0; j < N; ++j) {
+        for (int j = 0; j < nk; ++j) {
           const double p = exp(s[j] - mx);
           l += p;
           if (!vt) {
@@ -267,7 +274,7 @@ static void attn_exact_impl(const uint16_t* Q, const uint16_t* K, const uint16_t
           }
         }
         for (int d = 0; d < D; ++d) {
-          const double r = o[d] / l;
+          const double r = nk > 0 ? o[d] / l : 0.0;
           if (out_f32)
             ((float*)O)[bh * perq + (size_t)i * D + d] = (float)r;
           else
@@ -283,21 +290,27 @@ static void attn_exact_impl(const uint16_t* Q, const uint16_t* K, const uint16_t
 
 void lc_oracle_attn_exact(const uint16_t* Q, const uint16_t* K, const uint16_t* V, uint16_t* O, int B,
                           int H, int N, int D, int v_transposed) {
-  attn_exact_impl(Q, K, V, O, B, H, N, N, D, v_transposed, 0);
+  attn_exact_impl(Q, K, V, O, B, H, N, N, D, v_transposed, 0, 0, 0);
 }
 void lc_oracle_attn_exact_f32(const uint16_t* Q, const uint16_t* K, const uint16_t* V, float* O, int B,
                               int H, int N, int D, int v_transposed) {
-  attn_exact_impl(Q, K, V, O, B, H, N, N, D, v_transposed, 1);
+  attn_exact_impl(Q, K, V, O, B, H, N, N, D, v_transposed, 1, 0, 0);
 }
 void lc_oracle_attn_exact_f32_rows(const uint16_t* Qrows, const uint16_t* K, const uint16_t* V, float* O,
                                    int BH, int Nq, int N, int D, int v_transposed) {
-  attn_exact_impl(Qrows, K, V, O, BH, 1, Nq, N, D, v_transposed, 1);
+  attn_exact_impl(Qrows, K, V, O, BH, 1, Nq, N, D, v_transposed, 1, 0, 0);
+}
+
+/* dense causal attention: row i over keys j <= i + diag_offset (clipped to [0, N - 1]); 0 is the kernels' definition */
+void lc_oracle_attn_causal_exact_f32(const uint16_t* Q, const uint16_t* K, const uint16_t* V, float* O, int B, int H, int N,
+                                     int D, int v_transposed, int diag_offset) {
+  attn_exact_impl(Q, K, V, O, B, H, N, N, D, v_transposed, 1, 1, diag_offset);
 }
 
 void lc_oracle_attn_exact_f32_bf16(const uint16_t* Q, const uint16_t* K, const uint16_t* V, float* O, int B,
                                    int H, int N, int D) {
   g_decode_bf16 = 1;
-  attn_exact_impl(Q, K, V, O, B, H, N, N, D, 0, 1);
+  attn_exact_impl(Q, K, V, O, B, H, N, N, D, 0, 1, 0, 0);
   g_decode_bf16 = 0;
 }
 
@@ -305,7 +318,7 @@ void lc_oracle_attn_exact_f32_bf16(const uint16_t* Q, const uint16_t* K, const u
 void lc_oracle_attn_exact_f32_rows_bf16(const uint16_t* Qrows, const uint16_t* K, const uint16_t* V, float* O,
                                         int BH, int Nq, int N, int D) {
   g_decode_bf16 = 1;
-  attn_exact_impl(Qrows, K, V, O, BH, 1, Nq, N, D, 0, 1);
+  attn_exact_impl(Qrows, K, V, O, BH, 1, Nq, N, D, 0, 1, 0, 0);
   g_decode_bf16 = 0;
 }
 

@@ -27,6 +27,8 @@ class Oracle:
             f.restype, f.argtypes = None, [_u16, _u16, _u16, out, _i, _i, _i, _i, _i]
         lib.lc_oracle_attn_exact_f32_rows.restype = None
         lib.lc_oracle_attn_exact_f32_rows.argtypes = [_u16, _u16, _u16, _f32, _i, _i, _i, _i, _i]
+        lib.lc_oracle_attn_causal_exact_f32.restype = None
+        lib.lc_oracle_attn_causal_exact_f32.argtypes = [_u16, _u16, _u16, _f32, _i, _i, _i, _i, _i, _i]
         lib.lc_oracle_attn_refnum.restype = None
         lib.lc_oracle_attn_refnum.argtypes = [_u16, _u16, _u16, _u16, _i, _i, _i, _i, _i, _i]
         lib.lc_oracle_hgemm_flops.restype, lib.lc_oracle_hgemm_flops.argtypes = C.c_double, [_i, _i, _i]
@@ -97,6 +99,13 @@ class Oracle:
         else:
             self.lib.lc_oracle_attn_refnum(q, k, v, o, B, H, N, D, Bc, int(o_f32))
         return o.view(np.float16)
+
+    def attn_causal(self, q, k, v, B, H, N, D, vt=False, diag_offset=0):
+        """Dense causal attention in fp64 -> fp32 [B,H,N,D]: row i over keys j <= i + diag_offset (0: the kernels' definition;
+        -1 / +1: an off-by-one mask, for tests of the tests).  v is [B,H,N,D], or [B,H,D,N] when vt."""
+        o = np.empty((B, H, N, D), np.float32)
+        self.lib.lc_oracle_attn_causal_exact_f32(self.u16(q), self.u16(k), self.u16(v), o, B, H, N, D, int(vt), int(diag_offset))
+        return o
 
     def attn_bf16(self, q, k, v, B, H, N, D):
         """torch.bfloat16 tensors -> fp32 exact attention."""

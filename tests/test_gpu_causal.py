@@ -1,5 +1,5 @@
-"""GPU tests of causal attention (lc_attn_fwd_f16_ex with LC_ATTN_CAUSAL): parity with the C oracle row by row (causal row i is the
-oracle's row over keys 0 .. i), masking that no value behind the diagonal can reach, the two kernels against each other, batch and
+"""GPU tests of causal attention (lc_attn_fwd_f16_ex with LC_ATTN_CAUSAL): parity with the dense C oracle on EVERY row (causal row i is
+the oracle's row over keys 0 .. i, held to the bound of a sequence of i + 1 keys), masking that no value behind the diagonal can reach, the two kernels against each other, batch and
 grid-order invariance, the overflow slow path under the mask and the launch conditions (graph capture, another stream)."""
 
 import numpy as np
@@ -52,6 +52,31 @@ def _rows(N):
     return sorted(r for r in rs if 0 <= r < N)
 
 
+def report_worst_row(excess, kernel, err=None):
+    """Where a dense check failed: excess (and err) are [BH, N, D]; names the worst row, its 256-row block, its wave there (64 rows in
+    the merged-phase kernel, 32 in the lock-step one) and row % 16, the row's place in an MFMA operand."""
+    h, i, d = (int(x) for x in np.unravel_index(np.argmax(excess), excess.shape))
+    per = 64 if "w4u" in kernel else 32
+    bad = np.flatnonzero((excess > 0).any(axis=(0, 2)))
+    return (f"{kernel}: worst at head {h} row {i} (block {i // 256}, wave {i % 256 // per} of {per} rows, row % 16 = {i % 16}) col {d}: "
+            f"excess {excess[h, i, d]:.3e}" + ("" if err is None else f", |err| {err[h, i, d]:.3e}")
+            + f"; {bad.size} rows over the bound, first {bad[:8].tolist()}")
+
+
+def _check_dense(oracle, q, k, v, o, kernel):
+    """EVERY row of every head against the dense causal oracle; row i under the bound of a sequence of i + 1 keys (tol.attn_close(N = i + 1),
+    what _check_rows applies to the rows it samples)"""
+    B, H, N, D = q.shape
+    truth = oracle.attn_causal(q, k, v, B, H, N, D).reshape(B * H, N, D).astype(np.float64)
+    out = o.reshape(B * H, N, D).float().cpu().numpy()
+    assert np.isfinite(out).all(), report_worst_row(np.where(np.isfinite(out), 0.0, 1.0), kernel)
+    err = np.abs(out.astype(np.float64) - truth)
+    atol = np.array([tol.attn_max_abs(i + 1) for i in range(N)]).reshape(1, N, 1)
+    excess = err - (atol + tol.ATTN_RTOL_F16 * np.abs(truth))
+    assert (excess <= 0).all(), report_worst_row(excess, kernel, err)
+    return float(err.max())
+
+
 def _check_rows(oracle, q, k, v, o, rows, atol=None):
     B, H, N, D = q.shape
     BH = B * H
@@ -74,11 +99,11 @@ def _check_rows(oracle, q, k, v, o, rows, atol=None):
 @pytest.mark.parametrize("D", [32, 64, 96, 128])
 def test_causal_vs_oracle(oracle, D, vt, N):
     capi = _capi()
-    B, H = 1, 2
+    B, H = 1, 3      # (three heads: a slip in the head index of a block cannot cancel between two)
     assert _name(capi, N, D, vt, B * H) == _want(N, D, vt)
     q, k, v = _inputs(B, H, N, D, seed=D * 7919 + N + vt)
     o = _run(capi, q, k, v, vt)
-    _check_rows(oracle, q, k, v, o, _rows(N))
+    _check_dense(oracle, q, k, v, o, _want(N, D, vt))
     # row 0 sees key 0 only: O[0] = V[0] within one fp16 ulp
     o0, v0 = o[:, :, 0].float(), v[:, :, 0].float()
     assert ((o0 - v0).abs() <= v0.abs() * 2.0 ** -10 + 2.0 ** -24).all()
@@ -144,7 +169,7 @@ def test_merged_phase_agrees_with_the_lockstep_cross_check(oracle, D, vt):
     for nw, o in outs.items():
         ok, err, excess = tol.attn_close(o.float().cpu().numpy(), merged.float().cpu().numpy(), 256, rtol=2.0 ** -9)
         assert ok, (nw, err, excess)
-    _check_rows(oracle, q, k, v, outs[2], [0, 1, 255, 256, 1000, N - 1])
+    _check_dense(oracle, q, k, v, outs[2], f"attn_fwd_causal_kernel<{D},2,{'true' if vt else 'false'}>")
 
 
 @pytest.mark.parametrize("D,N", [(128, 1024), (64, 2048), (96, 512), (128, 320)])
@@ -176,6 +201,39 @@ def test_both_grid_orders_give_the_same_bits(D):
     assert torch.equal(outs[1][0], a) and torch.equal(outs[2][0], a)
     assert torch.equal(outs[1][1], outs[2][1])
     assert (a.float() - outs[1][1].float()).abs().max().item() < 1e-3
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_the_auto_rule_reaches_head_major_order_with_the_same_bits(oracle, D):
+    """66 heads x 8 blocks = 528 blocks: more than 8 rounds of a 64-CU device ("rule_cus" = 64), so the auto rule launches head-major —
+    the branch the forced knob value 2 reaches otherwise —, and fewer than 8 rounds of the 256-CU device itself, so auto is longest-first
+    there.  Both, and both forced orders, give one set of bits; a head of the large launch is the same head launched alone; one head is
+    compared densely with the oracle."""
+    capi = _capi()
+    B, H, N = 2, 33, 2048
+    assert B * H * (N // 256) > 8 * 64
+    q, k, v = _inputs(B, H, N, D, seed=606 + D)
+    assert capi.tune_get("attn_causal_order") == (0, 0) and capi.tune_get("rule_cus") == (0, 0)
+    assert _name(capi, N, D, False, B * H) == _want(N, D, False)
+    own = _run(capi, q, k, v)
+    capi.tune("rule_cus", 64)
+    try:
+        assert _name(capi, N, D, False, B * H) == _want(N, D, False)
+        auto64 = _run(capi, q, k, v)
+    finally:
+        capi.tune("rule_cus", 0)
+    forced = {}
+    for order in (1, 2):
+        capi.tune("attn_causal_order", order)
+        try:
+            forced[order] = _run(capi, q, k, v)
+        finally:
+            capi.tune("attn_causal_order", 0)
+    assert torch.equal(auto64, own) and torch.equal(forced[1], own) and torch.equal(forced[2], own)
+    for b, h in ((0, 0), (1, 16), (1, 32)):
+        one = _run(capi, *(x[b:b + 1, h:h + 1].contiguous() for x in (q, k, v)))
+        assert torch.equal(one[0, 0], auto64[b, h]), (b, h)
+    _check_dense(oracle, *(x[1:2, 32:33].contiguous() for x in (q, k, v, auto64)), _want(N, D, False))
 
 
 @pytest.mark.parametrize("D,N", [(128, 1024), (64, 4096), (96, 768), (32, 320)])

@@ -480,3 +480,28 @@ def test_d1024_full_width(oracle, N):
     capi.attn_call("flash_attn_mma_stages_split_q_tiling_qkv", q, k, vc, o, 2)
     torch.cuda.synchronize()
     assert (o.float() - 0.875).abs().max().item() < 1e-3
+
+
+@pytest.mark.parametrize("B,H,N,D", [(4, 32, 4096, 128), (1, 48, 8192, 64)])
+def test_causal_full_size(oracle, B, H, N, D):
+    """The causal merged-phase kernel at the two shapes its timings are quoted for.  Rows from EVERY 256-row
+    block — the first and the last row of each of its four 64-row waves plus two seeded random rows — of 4 seeded (batch, head) pairs,
+    the first and the last among them; row i against the oracle on keys 0 .. i under the bound of a sequence of i + 1 keys."""
+    from tests.test_gpu_causal import _check_rows
+    capi = _capi()
+    assert capi.attn_kernel_name(N, D, bh=B * H, causal=True) == f"attn_fwd_w4u_causal_kernel<{D},false>"
+    g = torch.Generator(device="cuda").manual_seed(B * 1000 + H + N + D)
+    q, k, v = (torch.randn(B, H, N, D, device="cuda", generator=g).half() for _ in range(3))
+    o = torch.full_like(q, float("nan"))
+    capi.attn_fwd(q, k, v, o, causal=True)
+    torch.cuda.synchronize()
+    assert torch.isfinite(o).all()
+    rng = np.random.default_rng(N + D)
+    heads = sorted({0, B * H - 1} | set(rng.choice(np.arange(1, B * H - 1), 2, replace=False).tolist()))
+    rows = set()
+    for b0 in range(0, N, 256):
+        rows |= {b0 + 64 * w + e for w in range(4) for e in (0, 63)}
+        rows |= set((b0 + rng.choice(256, 2, replace=False)).tolist())
+    assert len(heads) == 4 and all(any(b0 <= r < b0 + 256 for r in rows) for b0 in range(0, N, 256))
+    sel = [x.reshape(1, B * H, N, D)[:, heads].contiguous() for x in (q, k, v, o)]
+    _check_rows(oracle, *sel, sorted(rows))

@@ -550,6 +550,15 @@ def _attn_families():
         out.append((f"bigd-d{D}", D, False, 1, 2, 256, {}, ("start", "attn_fwd_bigd")))
     for D in (256, 512):
         out.append((f"bf16-d{D}", D, False, 1, 2, 256, {}, ("start", "attn_fwd_bigd")))
+    # causal (lc_attn_fwd_f16_ex): the merged-phase kernel, and the lock-step kernel with 8, 4 and 2 waves
+    for D in (64, 128):
+        for vt in (False, True):
+            out.append((f"causal-w4u-d{D}-{'vt' if vt else 'v'}", D, vt, 1, 2, 1024, {}, ("eq", f"attn_fwd_w4u_causal_kernel<{D},{str(vt).lower()}>")))
+    for D in (32, 64, 96, 128):
+        for nw, N, knobs in ((8, 512, {"attn_nw": 8}), (4, 384, {}), (2, 320, {})):
+            for vt in (False, True):
+                out.append((f"causal-lockstep{nw}-d{D}-{'vt' if vt else 'v'}", D, vt, 1, 2, N, knobs,
+                            ("eq", f"attn_fwd_causal_kernel<{D},{nw},{str(vt).lower()}>")))
     return out
 
 
@@ -559,8 +568,9 @@ ATTN_FAMILIES = _attn_families()
 def _attn_run(capi, fam, q, k, v):
     fid, D, vt, B, H, N, knobs, want = fam
     o = torch.full_like(q, float("nan"))
+    causal = fid.startswith("causal")
     with _knobs(capi, knobs):
-        name = capi.attn_kernel_name(N, D, vt, bf16=fid.startswith("bf16"), bh=B * H)
+        name = capi.attn_kernel_name(N, D, vt, bf16=fid.startswith("bf16"), bh=B * H, causal=causal)
         kind, txt = want
         assert (name == txt) if kind == "eq" else name.startswith(txt), (fid, name)
         if fid.startswith("bf16"):
@@ -568,7 +578,7 @@ def _attn_run(capi, fam, q, k, v):
         elif fid.startswith("bigd"):
             capi.attn_call("flash_attn_mma_stages_split_q_tiling_qkv", q, k, v, o, 2)
         else:
-            capi.attn_fwd(q, k, v.transpose(-2, -1).contiguous() if vt else v, o, v_transposed=vt)
+            capi.attn_fwd(q, k, v.transpose(-2, -1).contiguous() if vt else v, o, v_transposed=vt, causal=causal)
     torch.cuda.synchronize()
     return o
 
@@ -576,7 +586,8 @@ def _attn_run(capi, fam, q, k, v):
 @pytest.mark.parametrize("fam", ATTN_FAMILIES, ids=[f[0] for f in ATTN_FAMILIES])
 def test_attention_v_scaling_commutes(fam):
     """V with magnitudes in [2^-6, 8] and one sign per column d: every partial and final O is a convex combination bounded away from 0, so
-    O(Q, K, 2^e V) == 2^e O(Q, K, V) bit for bit for e = -8, +6, +12 (|V| up to 32768: an unnormalised fp16 intermediate of O would overflow)."""
+    O(Q, K, 2^e V) == 2^e O(Q, K, V) bit for bit for e = -8, +6, +12 (|V| up to 32768: an unnormalised fp16 intermediate of O would overflow).
+    The causal families keep the premise: a masked row is a convex combination of fewer same-signed values (row 0: of one)."""
     capi = _capi()
     fid, D, vt, B, H, N, knobs, want = fam
     dt = torch.bfloat16 if fid.startswith("bf16") else torch.half
@@ -603,7 +614,10 @@ def test_attention_subnormal_output(oracle, fam):
     k = torch.randn(B, H, N, D, device="cuda", generator=g).half()
     v = (torch.randn(B, H, N, D, device="cuda", generator=g) * 2.0 ** -20).half()
     o = _attn_run(capi, fam, q, k, v)
-    truth = oracle.attn(q, k, v, B, H, N, D, mode="f32").astype(np.float64)
+    if fid.startswith("causal"):
+        truth = oracle.attn_causal(q, k, v, B, H, N, D).astype(np.float64)
+    else:
+        truth = oracle.attn(q, k, v, B, H, N, D, mode="f32").astype(np.float64)
     out = o.float().cpu().numpy().astype(np.float64)
     assert (np.abs(truth) < 2.0 ** -14).all()
     err = np.abs(out - truth)

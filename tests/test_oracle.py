@@ -182,3 +182,56 @@ def test_bf16_attention_oracle_vs_torch(oracle):
     got = oracle.attn_bf16(q, k, v, B, H, N, D)
     att = torch.softmax(q.double() @ k.double().transpose(-2, -1) / (D ** 0.5), dim=-1) @ v.double()
     np.testing.assert_allclose(got, att.float().numpy(), rtol=2e-6, atol=2e-6)
+
+
+def _causal_inputs(BH, N, D, seed):
+    torch.manual_seed(seed)
+    return [torch.randn(1, BH, N, D, dtype=torch.half) for _ in range(3)]
+
+
+@pytest.mark.parametrize("vt", [False, True], ids=["v_nd", "v_dn"])
+@pytest.mark.parametrize("D,N", [(32, 70), (64, 129), (128, 200)])
+def test_causal_oracle_row_i_is_attn_rows_on_keys_0_to_i(oracle, D, N, vt):
+    """Exact fp32 equality, not 1 ulp: the dense function walks the visible keys in the order attn_rows walks keys 0 .. i, with the
+    same fp64 operations, so the GPU tests that check sampled rows through attn_rows and those that check every row through
+    attn_causal use one definition."""
+    BH = 2
+    q, k, v = _causal_inputs(BH, N, D, seed=D + N)
+    dense = oracle.attn_causal(q, k, v.transpose(-2, -1).contiguous() if vt else v, 1, BH, N, D, vt=vt)
+    for i in range(N):
+        vi = v[0, :, :i + 1]
+        row = oracle.attn_rows(q[0, :, i:i + 1].contiguous(), k[0, :, :i + 1].contiguous(),
+                               vi.transpose(-2, -1).contiguous() if vt else vi.contiguous(), BH, 1, i + 1, D, vt=vt)
+        assert np.array_equal(dense[0, :, i:i + 1].view(np.uint32), row.view(np.uint32)), i
+
+
+@pytest.mark.parametrize("D,N", [(32, 65), (64, 256), (96, 100), (128, 320)])
+def test_causal_oracle_vs_torch_sdpa_fp64(oracle, D, N):
+    B, H = 2, 2
+    torch.manual_seed(D * N)
+    q, k, v = (torch.randn(B, H, N, D, dtype=torch.half) for _ in range(3))
+    want = torch.nn.functional.scaled_dot_product_attention(q.double(), k.double(), v.double(), is_causal=True).numpy()
+    got = oracle.attn_causal(q, k, v, B, H, N, D)
+    assert np.abs(got.astype(np.float64) - want).max() <= 1e-6
+    assert np.array_equal(got, oracle.attn_causal(q, k, v.transpose(-2, -1).contiguous(), B, H, N, D, vt=True))
+    # the last row sees every key: the non-causal oracle's last row, bit for bit
+    assert np.array_equal(got[:, :, N - 1], oracle.attn(q, k, v, B, H, N, D, mode="f32")[:, :, N - 1])
+
+
+def test_causal_oracle_diag_offsets(oracle):
+    """offset -1: row i is offset 0's row i - 1 computed with Q_i, and row 0 (no visible key) is zeros; offset +1 clips at the last
+    key; both against fp64 torch with an explicit mask."""
+    B, H, N, D = 1, 2, 96, 64
+    torch.manual_seed(3)
+    q, k, v = (torch.randn(B, H, N, D, dtype=torch.half) for _ in range(3))
+    i, j = torch.arange(N).view(N, 1), torch.arange(N).view(1, N)
+    s = q.double() @ k.double().transpose(-2, -1) / math.sqrt(D)
+    for off in (-1, 0, 1, 5, -7, N, -N):
+        vis = j <= i + off
+        p = torch.softmax(s.masked_fill(~vis, -math.inf), dim=-1)
+        p = torch.where(vis.any(-1, keepdim=True), p, torch.zeros_like(p))   # (a row of -inf alone: softmax gives NaN)
+        want = (p @ v.double()).numpy()
+        got = oracle.attn_causal(q, k, v, B, H, N, D, diag_offset=off)
+        assert np.abs(got.astype(np.float64) - want).max() <= 1e-6, off
+        blind = ~vis.any(-1).numpy()
+        assert (got[:, :, blind] == 0).all() and blind.sum() == max(0, min(N, -off))
