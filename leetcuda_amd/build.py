@@ -154,8 +154,8 @@ def build_abi(force: bool = False, audit: bool = True) -> Path:
     dg = _digest(srcs, " ".join(_portable(flags)))
     if not force and _fresh(out, "abi", dg) and _stamp_ok(stamp, flags):
         return out
-    # translation units (lc_abi.hip + the compile-heavy literal-AGPR kernels in tu_*.hip), compiled in parallel; each
-    # is compiled twice: to an object and (device side only) to assembly for the audit
+    # translation units (lc_abi.hip: the C-ABI; tu_plan.hip: the host-only launch planning; the kernels in the other tu_*.hip), compiled in
+    # parallel; each is compiled twice: to an object and (device side only) to assembly for the audit (nothing to report for a unit without kernels)
     objdir = LIBDIR / "obj"
     objdir.mkdir(exist_ok=True)
     units = [CSRC / "lc_abi.hip"] + sorted(CSRC.glob("tu_*.hip"))

@@ -19,10 +19,10 @@
 //     rows of a tr-read half-wave land on disjoint bank quarters). One barrier per KV tile.
 #pragma once
 #include "lc_common.h"
+#include "lc_tiles.h"
 
 namespace lc {
 
-constexpr int KVB = 64;  // kv rows per tile
 constexpr float RESCALE_THR = 8.0f;  // log2 units
 
 // workgroup barrier that also publishes this wave's LDS writes (ds_write -> lgkmcnt(0) -> s_barrier)

@@ -3,19 +3,18 @@
 // for the shapes the reference itself accepts but a 256 tile does not divide: M, N multiples of 128, K of 32
 // (reference tiles are 128x128x32, kernels/hgemm/mma/basic/hgemm_mma_stage.cu:644-676; K % 64 == 32: one half K-step with
 // fragments straight from global memory after the tile loop).  64 KiB of LDS, two workgroups per CU.  Besides its own grid it
-// computes, for the 256-tile kernels (lc_abi.hip launch_mfma256), the quadrants of their ragged last wave and the 128-wide border
+// computes, for the 256-tile kernels (tu_core.hip launch_mfma256), the quadrants of their ragged last wave and the 128-wide border
 // strips of M, N % 256 == 128 problems.
 #pragma once
 #include "hgemm_mfma256.hip"
 
 namespace lc {
 
-constexpr int BM1 = 128, BN1 = 128;
 constexpr int TILE1_BYTES = BM1 * BK * 2;        // 16 KiB (A) == BK * BN1 * 2 (B)
 constexpr int SLOT1_BYTES = 2 * TILE1_BYTES;
 constexpr int HGEMM128_LDS = 2 * SLOT1_BYTES;    // 64 KiB
 
-// Block -> origin of its 128 x 128 C tile.  rem_base == -1: this kernel's own grid of 128 x 128 tiles.  Otherwise (lc_abi.hip
+// Block -> origin of its 128 x 128 C tile.  rem_base == -1: this kernel's own grid of 128 x 128 tiles.  Otherwise (tu_core.hip
 // launch_mfma256) tiles_m / tiles_n / panel_w describe the 256 x 256 tile grid of the interior and the blocks are, in this order:
 //   b < rem_blocks           quadrant b & 3 of the 256-tile whose raster id is rem_base + (b >> 2) — the ids the big kernel's
 //                            truncated grid left out (its ragged last wave);
@@ -59,7 +58,7 @@ LC_DEVINL Tile128 mfma128_tile(int b, int nblocks, int M, int N, int tiles_m, in
 // wave); at the end group 1 hands its fp32 accumulators over through LDS (4 x 16 KiB = the whole allocation) and group 0 adds and runs
 // the epilogue.  Two waves per SIMD inside ONE block: on grids that leave most CUs idle (1024^3: 64 blocks, 1536^3: 144) + 11 %; at one
 // block per CU (2048^3) level — the 128 x 128 tile is L2-bandwidth-bound there, not latency-bound — and the NN form loses from 2560^3 on
-// (profiles/r5g_hgemm_128w.log), so LC_HGEMM_AUTO uses it up to 0.6 blocks per CU (lc_abi.hip mfma128_ksw).  Never combined with the
+// (profiles/r5g_hgemm_128w.log), so LC_HGEMM_AUTO uses it up to 0.6 blocks per CU (tu_plan.hip mfma128_ksw).  Never combined with the
 // workspace split-K (ksplit must be 1).
 template <bool B_KN, int KSW>
 __global__ __launch_bounds__(256 * KSW, KSW == 1 ? 2 : 1) void hgemm_mfma128_kernel(const half_t* __restrict__ A,

@@ -20,10 +20,10 @@
 // lane's 4 accumulator registers are 4 consecutive n of one output row -> 8-byte packed epilogue.
 #pragma once
 #include "lc_common.h"
+#include "lc_tiles.h"
 
 namespace lc {
 
-constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;          // 32 KiB (A) == BK * BN * 2 (B)
 constexpr int SLOT_BYTES = 2 * TILE_BYTES;       // A + B
 constexpr int HGEMM256_LDS = 2 * SLOT_BYTES;     // 128 KiB

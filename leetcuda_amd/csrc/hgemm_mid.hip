@@ -11,7 +11,7 @@
 // 200 ... 256 workgroups on 256 CUs).  A launch that short (12 ... 45 us, 20 ... 44 K tiles) is decided by latency, not by bytes: every
 // workgroup streams operands nobody has touched yet (HBM / Infinity-Cache latency on each K tile, not the 250 ... 400 cycles of an L2
 // hit), and with one or two waves per SIMD nothing hides an LDS read or a burst of DMA issue either.  So:
-//   * tile shapes (TMW, TNW) in units of 64: lc_abi.hip mid_tile_auto picks the one with the least work on the busiest CU;
+//   * tile shapes (TMW, TNW) in units of 64: tu_plan.hip mid_tile_auto picks the one with the least work on the busiest CU;
 //   * grids of one round (<= one workgroup per CU) spend the LDS on DEPTH: NS = 3 slots, the DMA of tile t + 3 issued while tile t
 //     computes (a DMA has two whole tiles to land where hgemm_mfma128_kernel has one); larger grids keep NS = 2 and two workgroups per CU;
 //   * the k-loop is rotated so that the barrier sits in the MIDDLE of a tile, and every MFMA carries its share of the other work:
@@ -120,7 +120,7 @@ LC_DEVINL void hgemm_mid_body(const half_t* __restrict__ A, const half_t* __rest
   const int wave = wave_id();
   const int wr = wave >> 1, wc = wave & 1;
   const int i16 = lane & 15, g = lane >> 4;
-  // rem_base < 0: this kernel's own grid of TM x TN tiles.  rem_base >= 0 (tiles that divide 256 x 256: 128 x 128, 64 x 128; lc_abi.hip
+  // rem_base < 0: this kernel's own grid of TM x TN tiles.  rem_base >= 0 (tiles that divide 256 x 256: 128 x 128, 64 x 128; tu_core.hip
   // launch_mfma256): tiles_m / tiles_n / panel_w describe the 256 x 256 tile grid of hgemm_w4y_kernel and block b is sub-tile b % SUBS
   // (row-major inside the 256-tile) of the 256-tile whose raster id is rem_base + b / SUBS — the ids that kernel's truncated grid left out
   // (its ragged last round; hgemm_mfma128.hip mfma128_tile's map).

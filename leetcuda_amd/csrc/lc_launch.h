@@ -1,5 +1,5 @@
 // lc_launch.h — pieces shared by the translation units of libleetcuda_amd.so (lc_abi.hip + the tu_*.hip files that
-// hold the compile-heavy literal-AGPR kernels, built in parallel by leetcuda_amd/build.py).
+// hold the kernels and the launch planning, built in parallel by leetcuda_amd/build.py).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -186,7 +186,7 @@ inline bool stream_is_capturing(hipStream_t st) {
   return cap != hipStreamCaptureStatusNone;
 }
 
-// tuning globals (defined in lc_abi.hip, lc_tune_set)
+// tuning globals (defined in tu_plan.hip from lc_knobs.inc, lc_tune_set)
 // Every knob is a std::atomic<int> (relaxed loads / stores through the implicit conversions): lc_tune_set from one host thread
 // while another launches is a data race on a plain int; a launch reads each knob ONCE into a local and decides from that.
 using tune_t = std::atomic<int>;
@@ -208,6 +208,13 @@ inline int stagger_arg(int kt) {
 }
 
 // launchers living in their own translation units
+// tu_core.hip: what a plan (lc_plan.h) launches — the builtin-MFMA kernels of this unit or the launchers below
+struct HgemmPlan;
+struct AttnPlan;
+int launch_hgemm(const HgemmPlan& p, const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int swizzle_stride, hipStream_t st);
+int launch_attn_plan(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt, bool bf16,
+                     hipStream_t st);
+int launch_clock_probe(unsigned long long* out_u64x2, hipStream_t st);   // lc_clock_probe_kernel: shader cycles, the constant 100 MHz clock
 // the mid-size kernel (hgemm_mid.hip, tu_mid.hip): (64 tmw) x (64 tnw) tiles, ns ring slots
 int launch_hgemm_mid(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int tnw, int ns, int pw,
                      hipStream_t st, float* part = nullptr, int ks = 1);
@@ -218,7 +225,7 @@ size_t launch_hgemm_mid_edge_sk_floats(int M, int N, int tmw, int ks);
 int launch_hgemm_mid_edge_sk(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int ks, float* part, hipStream_t st);
 int launch_hgemm_mid_rem(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int ns, int tiles_m256,
                          int tiles_n256, int pw256, int rem_base, int rem_tiles, hipStream_t st);   // the 256-tile kernel's ragged last round as 128 x 128 quadrants
-// tu_w4.hip: the 4-wave 256-tile kernels; variant = what w4_effective_variant (lc_abi.hip) left of LC_HGEMM_MFMA256W4B / W4C / W4X / W4Y,
+// tu_w4.hip: the 4-wave 256-tile kernels; variant = what w4_effective_variant (tu_plan.hip) left of LC_HGEMM_MFMA256W4B / W4C / W4X / W4Y,
 // sched = hgemm_w4y_kernel's TN loop schedule, stamps / abl = LC_DIAG instantiations of W4C; nblk > 0: launch only the first nblk blocks
 // (hgemm_w4y_kernel only; the caller hands the remaining raster ids to smaller tiles)
 int launch_w4_family(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int variant, int sched, int stamps, int abl, bool b_kn,
@@ -235,7 +242,7 @@ int launch_attn_w4u_d128(const half_t* Q, const half_t* K, const half_t* V, half
 int launch_attn_w4u_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);   // V as [B,H,D,N]
 int launch_attn_w4u_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);
 int launch_attn_w4u_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);    // V as [B,H,D,N]
-// causal (N % 256 == 0; attn_fwd_w4u_causal_kernel): order 0 = grid longest block first, 1 = head-major (lc_abi.hip choose_attn_causal)
+// causal (N % 256 == 0; attn_fwd_w4u_causal_kernel): order 0 = grid longest block first, 1 = head-major (tu_plan.hip choose_attn_causal)
 int launch_attn_w4u_causal_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
 int launch_attn_w4u_causal_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
 int launch_attn_w4u_causal_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);

@@ -1,0 +1,116 @@
+// lc_plan.h — the host-side launch planning of libleetcuda_amd.so (tu_plan.hip): the knob snapshot and registry, the reference entry-name
+// tables, and ONE plan per HGEMM / attention call that the launchers (tu_core.hip) run and the name calls (lc_abi.hip) report.  No kernel source.
+#pragma once
+#include "lc_launch.h"
+#include "lc_tiles.h"
+
+namespace lc {
+
+// every knob's storage (lc_knobs.inc; lc_launch.h declares the four that launchers of other units read)
+#define LC_KNOB(name, dflt, valid, diag) extern tune_t g_tune_##name;
+#include "lc_knobs.inc"
+
+// The knobs that decide which kernel runs, read ONCE per call: the planners (plan_hgemm, plan_attn) and every rule they use take this
+// snapshot, so a concurrent lc_tune_set cannot pair one decision with another.  (hgemm_persist, hgemm_stagger, attn_bigd_map and
+// attn_bigd_stagger steer only the inside of a kernel, no name reports them: their launchers read them.)
+struct Knobs {
+#define LC_KNOB(name, dflt, valid, diag)
+#define LC_KNOB_SNAP(name, dflt, valid, diag) int name;
+#include "lc_knobs.inc"
+};
+Knobs read_knobs();
+
+// the knob registry: ONE table for lc_tune_set / lc_tune_get (key, variable, default, validity of a value)
+struct Knob {
+  const char* key;
+  tune_t* var;
+  int dflt;
+  bool (*valid)(int);
+  bool diag;   // diagnosis key (include/lc_diag.h): results may be WRONG; a production library rejects it
+};
+extern const Knob kKnobs[];
+extern const int kNumKnobs;
+const Knob* find_knob(const char* key);   // nullptr: no such key (or a diagnosis key in a production library)
+
+// reference entry tables
+struct HgemmEntry {
+  const char* name;
+  int layout;   // lc_layout
+  int nargs;    // 0, 3 or 6
+  int variant;  // lc_hgemm_variant, -1 = vendor, -2 = handle init, -3 = handle destroy
+};
+struct AttnEntry {
+  const char* name;
+  int family, vt, acc_f32, maxd_s2, maxd_s1, nargs;
+};
+extern const HgemmEntry kHgemmEntries[];
+extern const AttnEntry kAttnEntries[];
+extern const int kNumHgemmEntries, kNumAttnEntries;
+const HgemmEntry* find_hgemm(const char* name);
+const AttnEntry* find_attn(const char* name);
+
+bool is_w4_variant(int v);
+bool is_tile256_variant(int v);
+bool is_valu_variant(int v);
+bool is_hgemm_variant(int v);
+
+int panel_tiles(int raster, int swizzle_stride, int tiles_n, int tile_n, size_t operand_bytes);
+int rule_cus(const Knobs& k);
+// Constants of the split-KV cost model (attn_split_auto) measured on THIS device by lc_tune_calibrate (round 6; round-5 verdict weak #13:
+// they were fitted once, on one box's clocks); one record per device ordinal, valid != 0 once measured.
+struct AttnCalib {
+  std::atomic<int> valid{0};
+  float tau128 = 0.f, tau64 = 0.f, x0 = 0.f, bytes_per_us = 0.f;
+};
+extern AttnCalib g_attn_calib[64];
+constexpr double kSplitFixedUs = 5.0, kSplitBytesPerUs = 2.6e6;   // the built-in x0 and bw of that model (tu_plan.hip attn_split_auto)
+
+struct MidTile { int tmw, tnw, ns, ks; long wgs; };   // ks > 1: split-K, needs ks x M x N floats of workspace (launch_mid; none under graph capture)
+struct RaggedPlan { int kind, Mi, Ni, ns, tmw, tnw, ks; };   // ks > 1: split-K (kind 2, 64 / 128 x 128 tiles; needs the workspace: none under graph capture)
+struct TailSplit { int nblk, R, tmw, ns; };   // nblk = -1: one launch of all T tiles
+
+// ONE decision per HGEMM call: plan_hgemm makes it from one knob snapshot, lc_hgemm_f16 launches it and lc_hgemm_kernel_name reports it.
+// A launch differs from its plan only where the plan cannot know; this is the complete list:
+//   - the stream is being captured: no workspace (split-K of the 128-tile border blocks, of the mid-size and of the ragged kernel: one K range;
+//     LC_HGEMM_KPAD: hgemm_edge_kernel), no fork (the border on the caller's stream)
+//   - the workspace lease fails (the same fallbacks; LC_HGEMM_KPAD's padded problem holds the lease, so its plan runs workspace-free, unforked)
+//   - the fork's side stream cannot be made: both launches on the caller's stream
+//   (attention: the same for split-KV; and a persistent w4u walk with no more blocks than CUs runs walk 0, the dynamic queue on a CU count
+//   that is not a multiple of 8 or under capture the static walk — tu_attn_w4u_impl.h)
+enum class HFam { VALU, TILE256, MFMA128, MID, RAGGED, KPAD, EDGE, GENERIC };
+struct HgemmPlan {
+  Knobs k;                  // the snapshot (launch: panel_tiles, LC_HGEMM_KPAD's plan of the padded problem)
+  HFam fam;
+  int variant;              // VALU: the rung; TILE256: the 256-tile family after LC_HGEMM_AUTO
+  int w4, sched;            // TILE256 / RAGGED kind 1: w4_effective_variant (0: not a 4-wave family), hgemm_w4y_kernel's schedule
+  MidTile mid;              // MID
+  RaggedPlan rag;           // RAGGED
+  int Kp;                   // KPAD: the padded K
+  int tiles_m, tiles_n;     // TILE256 / RAGGED kind 1: the 256 x 256 tiles of the (interior) grid ...
+  TailSplit tail;           // ... and their ragged last round
+  int nright, nbottom;      // TILE256: 128-wide border strips in 128 x 128 blocks; all blocks of the 128-tile launch (strips + tail quadrants),
+  int nb128, ks, ksw;       // their split-K factor and the kernel's waves (ksw: also MFMA128)
+  bool fork;                // RAGGED kind 1: the border launch on the side stream
+};
+int plan_hgemm(const Knobs& k, int M, int N, int K, bool b_kn, int variant, bool al, HgemmPlan* out);
+void format_hgemm(const HgemmPlan& p, int M, int N, bool b_kn, char* buf, int buflen);
+
+// Which attention kernel serves a problem (plan_attn; D <= 128: choose_attn_nw, with the lc_tune_set "attn_nw" value of each in brackets):
+//   W4U       attn_fwd_w4u_kernel<D, VT, WALK> (attn_w4u.hip: D = 64 / 128, N % 256 == 0, V as [B,H,N,D] or — the three *_swizzle_qkv entries —
+//             [B,H,D,N]): WALK 0 one 256-row query block per workgroup [513], 1 persistent workgroup per CU, static walk [515], 2 persistent,
+//             dynamic per-XCD block queue [517], 3 split-KV: nsplit KV ranges per query block + the combine kernel [auto only]
+//   W4I       the same design with each phase as one generated asm statement (attn_w4i.hip: D = 32 / 64 / 96 / 128, V as [B,H,N,D]; the only
+//             merged-phase kernel for D = 96 / 32) [514];  LOCKSTEP  attn_fwd.hip with nw waves [8 / 4 / 2];  the rest: D >= 256 (use_bigd*)
+// [512] (round 2's attn_w4n) is an alias of [513]: attn_w4u<128, false, 0> IS that kernel; 256 / 260 / 516 were retired in round 4 with
+// attn_w4m.hip / attn_w8g.hip.
+// Causal calls (lc_attn_fwd_f16_ex, choose_attn_causal): W4U_CAUSAL  attn_fwd_w4u_causal_kernel<D, VT> (D = 64 / 128, N % 256 == 0; one block
+// per workgroup, order = "attn_causal_order");  LOCKSTEP_CAUSAL  attn_fwd_causal_kernel<D, nw, VT> (everything else with D <= 128).
+enum class AKern { W4U, W4I, LOCKSTEP, BIGD4, BIGD6, BIGD7, BIGD2, BIGD3, COLSPLIT, W4U_CAUSAL, LOCKSTEP_CAUSAL };
+struct AttnPlan {   // walk / nsplit: W4U; sched: W4I ("attn_w4i_sched"); nw: LOCKSTEP / COLSPLIT waves; span8: BIGD4's DMA spread in eighths
+  AKern kern;         // of a phase ("attn_d1024"; 0 = the default, 8); abl: LOCKSTEP's LC_DIAG ablation ("attn_ablate"; D = 128, V as [B,H,N,D])
+  int walk, nsplit, sched, nw, span8, abl, order;   // order: W4U_CAUSAL's grid order
+};
+int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, bool causal, AttnPlan* p);
+void format_attn(const AttnPlan& p, int D, bool vt, bool bf16, char* buf, int buflen);
+
+}  // namespace lc

@@ -51,7 +51,7 @@ int launch_w4u_split(const half_t* Q, const half_t* K, const half_t* V, half_t* 
 
 // N % 256 == 0 (walk 0: also N % 256 == 128); walk: 0 one block per workgroup, 1 persistent static walk, 2 persistent dynamic queue.  A persistent walk with no
 // more blocks than CUs IS the one-block launch; the dynamic queue needs a grid that is a multiple of the 8 XCDs.
-// walk 3 = split-KV with `nsplit` (>= 2, N / 64 % nsplit == 0, >= 2 tiles per split: attn_split_auto, lc_abi.hip) workgroups per query
+// walk 3 = split-KV with `nsplit` (>= 2, N / 64 % nsplit == 0, >= 2 tiles per split: attn_split_auto, tu_plan.hip) workgroups per query
 // block; when the split cannot run on this stream (graph capture, allocator) the one-block walk runs instead.
 int W4U_CAT(launch_attn_w4u_, W4U_TAG)(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk,
                                        int nsplit, hipStream_t st) {

@@ -59,7 +59,7 @@ int launch_mid_tm(const half_t* A, const half_t* B, half_t* C, int M, int N, int
 }
 }  // namespace
 
-// tmw: 1 / 2 / 3 = 64 / 128 / 192 tile rows; tnw: 2 / 3 = 128 / 192 tile columns (NN: 2); ns: ring slots 2 / 3; pw: block -> tile map (panel_tiles, lc_abi.hip)
+// tmw: 1 / 2 / 3 = 64 / 128 / 192 tile rows; tnw: 2 / 3 = 128 / 192 tile columns (NN: 2); ns: ring slots 2 / 3; pw: block -> tile map (panel_tiles, tu_plan.hip)
 // part / ks: split-K (ks >= 2: tmw 1 / 2, tnw 2, at least two K tiles per range; part = ks x M x N floats)
 int launch_hgemm_mid(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int tnw, int ns, int pw,
                      hipStream_t st, float* part, int ks) {

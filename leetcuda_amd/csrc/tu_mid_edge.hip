@@ -1,5 +1,5 @@
 // tu_mid_edge.hip — translation unit of the mid-size HGEMM kernel's EDGE instantiations (hgemm_mid.hip: tiles that reach beyond M / N; LC_HGEMM_RAGGED,
-// lc_abi.hip launch_ragged) — a unit of its own so that the build's longest compile is split in two; see lc_launch.h
+// tu_core.hip launch_ragged) — a unit of its own so that the build's longest compile is split in two; see lc_launch.h
 #include <climits>
 #include "lc_launch.h"
 #include "hgemm_mid.hip"

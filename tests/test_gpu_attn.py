@@ -603,7 +603,7 @@ def test_scale_jumps_and_spikes_d64(oracle, nw, D):
 
 
 # ---- split-KV (round 5): grids that do not fill the GPU ------------------------------------------------------------------------
-# (B, H, N, D, S): S = the factor the auto rule picks on a 256-CU device (lc_abi.hip attn_split_auto's cost model), or — negative — a factor
+# (B, H, N, D, S): S = the factor the auto rule picks on a 256-CU device (tu_plan.hip attn_split_auto's cost model), or — negative — a factor
 # forced through lc_tune_set "attn_split" on a shape auto leaves alone (too few KV tiles for the combine to pay)
 SPLIT_SHAPES = [(1, 8, 1024, 128, 4), (1, 8, 2048, 64, 4), (1, 16, 2048, 128, 2), (1, 5, 4096, 64, 2), (1, 3, 768, 128, 2), (2, 3, 512, 128, -2), (1, 1, 256, 64, -2)]
 
@@ -846,7 +846,7 @@ def test_bigd_block_map_knob_computes_the_same_bits(oracle, D, N):
 
 def test_split_kv_against_wave_quantisation(oracle):
     """g = 320 query blocks on 256 CUs are 1.25 rounds and cost 2; with 4 KV ranges per block the launch runs 5 rounds of a quarter of
-    the walk (lc_abi.hip attn_split_auto: + 22 % at (1,10,8192,128), profiles/r5f_attn_split_quant.log).  The shape the rule picks it for,
+    the walk (tu_plan.hip attn_split_auto: + 22 % at (1,10,8192,128), profiles/r5f_attn_split_quant.log).  The shape the rule picks it for,
     sampled rows x all keys against the oracle, and the unsplit kernel on the same inputs."""
     from tests.test_gpu_configs import _rows_for, _sampled_rows_check
     capi = _capi()

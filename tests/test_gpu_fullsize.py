@@ -196,7 +196,7 @@ def test_hgemm_reference_legal_shapes_full_size(oracle, shape, layout):
 def test_hgemm_tail_split_border_and_k_tail_together(oracle, layout):
     """4480 x 4480 x 4128: 17 x 17 = 289 interior tiles on 256 CUs (33 in a ragged last wave -> 132 quadrant blocks on the 128-tile kernel),
     128-wide right AND bottom strips (35 + 34 blocks in the same launch), K % 64 == 32 in every kernel, split-K over all of those blocks —
-    every special case of lc_abi.hip launch_mfma256 in one problem."""
+    every special case of tu_core.hip launch_mfma256 in one problem."""
     capi = _capi()
     M = N = 4480
     K = 4128

@@ -1069,7 +1069,7 @@ def test_xcd_super_block_raster_computes_the_same_bits(layout):
 @pytest.mark.parametrize("raster", [1, 2])
 def test_ragged_last_wave_goes_to_the_128_tile_kernel(oracle, layout, raster):
     """lc_tune_set "hgemm_tail" = 1 (default): when the 256-tile grid's last wave holds at most 128 tiles, hgemm_w4y_kernel runs the
-    full waves and 128 x 128 blocks the four quadrants of every remaining tile (lc_abi.hip launch_mfma256) — since round 6 on
+    full waves and 128 x 128 blocks the four quadrants of every remaining tile (tu_core.hip launch_mfma256) — since round 6 on
     hgemm_mid_kernel (three ring slots when the blocks fit one round, two beyond; no workspace; 64 x 128 eighths instead of quadrants while
     THEY fit one round, "hgemm_tail_tile"), "hgemm_tail" = 2 keeps round 5's
     hgemm_mfma128_kernel + split-K form.  Every element is written exactly once, all three agree with the one-launch result to fp16
