@@ -298,6 +298,24 @@ int lc_attn_fwd_f16(const void* Q, const void* K, const void* V, void* O, int B,
 int lc_attn_fwd_f16_ex(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,
                        int flags, void* stream);
 
+/* EXTENSION (the reference has one head count): grouped-query / multi-query attention.  Q, O: [B,H,N,D]; K: [B,Hkv,N,D]; V: [B,Hkv,N,D],
+ * or [B,Hkv,D,N] with LC_ATTN_V_TRANSPOSED; G = H / Hkv.  Query head h of batch b attends to K / V head h / G of batch b (the
+ * repeat_interleave convention of torch SDPA enable_gqa and flash-attn) — the result is, bit for bit, what lc_attn_fwd_f16_ex returns
+ * on K and V expanded G times along the head axis, without the copy.  flags, scale, causal mask and softmax as lc_attn_fwd_f16_ex.
+ *   Hkv == H: the call IS lc_attn_fwd_f16_ex (same plan, kernel and bits; every head dim that entry takes).
+ *   Hkv <  H: fp16, D in {32, 64, 96, 128}, N % 64 == 0, causal or not, both V layouts; D >= 256 gives LC_ERR_HEADDIM (no grouped-query
+ *   kernels for the large head dims yet).  Hkv < 1, Hkv > H or H % Hkv != 0: LC_ERR_SHAPE.  Checks in lc_attn_fwd_f16_ex's order
+ *   (flags / null pointer: LC_ERR_ARG, then shape, then head dim), all before any device work.
+ *   The plan is the one lc_attn_fwd_f16_ex makes for the same (B x H, N, D, flags) — kernel family, walk, split-KV factor, waves, causal
+ *   grid order; nothing is decided by Hkv — and the kernel is that plan's kernel under the name with `_kernel` replaced by
+ *   `_gqa_kernel` (attn_fwd_w4u_gqa_kernel<128,false,1>, attn_fwd_w4u_causal_gqa_kernel<64,true>, attn_fwd_w4i_gqa_kernel<96,1>,
+ *   attn_fwd_gqa_kernel<...>, attn_fwd_causal_gqa_kernel<...>): the batch-variance note above and every lc_tune_set knob apply unchanged.
+ * lc_attn_kernel_name_gqa(BH = B x H query heads or <= 0, G, ...) never launches; G == 1: lc_attn_kernel_name_ex's answer; G < 1 or
+ * BH > 0 with BH % G != 0: LC_ERR_SHAPE. */
+int lc_attn_fwd_f16_gqa(const void* Q, const void* K, const void* V, void* O, int B, int H, int Hkv, int N, int D,
+                        int flags, void* stream);
+int lc_attn_kernel_name_gqa(int BH, int G, int N, int D, int flags, char* buf, int buflen);
+
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -51,6 +51,7 @@ SYMBOLS = {
     "lc_attn_fwd_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_fwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "lc_attn_fwd_f16_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "lc_attn_fwd_f16_gqa": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -61,6 +62,7 @@ SYMBOLS = {
     "lc_attn_kernel_name": (_i, [_i, _i, _i, _i, _cp, _i]),
     "lc_attn_kernel_name_bh": (_i, [_i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_kernel_name_ex": (_i, [_i, _i, _i, _i, _cp, _i]),
+    "lc_attn_kernel_name_gqa": (_i, [_i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_slowpath_stats": (_i, [C.POINTER(C.c_uint), _i]),
     "lc_timer_start": (_i, [_vp, C.POINTER(_vp)]),
     "lc_timer_stop": (_i, [_vp, _fp]),
@@ -363,6 +365,32 @@ def attn_fwd(q, k, v, o, v_transposed=False, family=ATTN_SPLIT_Q, acc_f32=False,
     return o
 
 
+def _attn_dims_gqa(q, k, v, o, v_transposed=False):
+    """q, o [B,H,N,D]; k [B,Hkv,N,D]; v [B,Hkv,N,D] or [B,Hkv,D,N]; H % Hkv == 0.  Returns B, H, Hkv, N, D."""
+    if q.dim() != 4 or k.dim() != 4:
+        _shape_err("4-D [B,H,N,D] / [B,Hkv,N,D] tensors expected")
+    B, H, N, D = q.shape
+    Hkv = k.shape[1]
+    vshape = (B, Hkv, D, N) if v_transposed else (B, Hkv, N, D)
+    if tuple(k.shape) != (B, Hkv, N, D) or tuple(o.shape) != (B, H, N, D) or tuple(v.shape) != vshape:
+        _shape_err(f"q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} o {tuple(o.shape)}")
+    if Hkv < 1 or Hkv > H or H % Hkv != 0:
+        _shape_err(f"{H} query heads on {Hkv} K/V heads")
+    return B, H, Hkv, N, D
+
+
+def attn_fwd_gqa(q, k, v, o, v_transposed=False, causal=False):
+    """Grouped-query / multi-query forward (lc_attn_fwd_f16_gqa): q, o [B,H,N,D], k / v with Hkv = k.shape[1] heads, H % Hkv == 0;
+    query head h reads K / V head h // (H // Hkv).  fp16, D <= 128 when Hkv < H; Hkv == H is attn_fwd(..., causal=causal)'s call."""
+    import torch
+    _need_gpu(q, k, v, o)
+    assert q.dtype == k.dtype == v.dtype == o.dtype == torch.half
+    B, H, Hkv, N, D = _attn_dims_gqa(q, k, v, o, v_transposed)
+    flags = (ATTN_CAUSAL if causal else 0) | (ATTN_V_TRANSPOSED if v_transposed else 0)
+    check(load().lc_attn_fwd_f16_gqa(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, Hkv, N, D, flags, _stream()), "lc_attn_fwd_f16_gqa")
+    return o
+
+
 def attn_fwd_bf16(q, k, v, o):
     """bfloat16 forward for D in {256, 512} (BASELINE config 5 extension)."""
     import torch
@@ -436,10 +464,16 @@ def attn_slowpath_stats(reset=True):
     return [out[0], out[1], out[2], struct.unpack("f", struct.pack("I", out[3]))[0]]
 
 
-def attn_kernel_name(N, D, v_transposed=False, bf16=False, bh=None, causal=False) -> str:
+def attn_kernel_name(N, D, v_transposed=False, bf16=False, bh=None, causal=False, group=1) -> str:
     """The kernel the dispatcher picks for sequence length N and head dim D; bh = batch x heads of the launch (None: a grid that fills
-    the GPU — the choice depends on it for D = 256 only); causal=True: the kernel of attn_fwd(..., causal=True)."""
+    the GPU — the choice depends on it for D = 256 only); causal=True: the kernel of attn_fwd(..., causal=True); group = H / Hkv > 1:
+    the kernel of attn_fwd_gqa (bh counts QUERY heads)."""
     buf = C.create_string_buffer(128)
+    if group != 1:
+        assert not bf16, "grouped-query attention is fp16 only"
+        flags = (ATTN_CAUSAL if causal else 0) | (ATTN_V_TRANSPOSED if v_transposed else 0)
+        check(load().lc_attn_kernel_name_gqa(int(bh) if bh else -1, int(group), N, D, flags, buf, 128), "lc_attn_kernel_name_gqa")
+        return buf.value.decode()
     if causal:
         assert not bf16, "causal attention is fp16 only"
         flags = ATTN_CAUSAL | (ATTN_V_TRANSPOSED if v_transposed else 0)

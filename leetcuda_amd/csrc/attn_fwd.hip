@@ -50,6 +50,7 @@ constexpr int attn_lds_bytes() {
 // rank 0 = the head's last query block); a block walks the tiles up to its last row only, and the tiles that reach past a wave's
 // first row replace the masked scores by −inf before the row max.  The online softmax is guarded so that a row segment masked
 // whole (a tile past the row, while the running max is still −inf) never forms −inf − (−inf).
+#define LC_ATTN_KVH(bh) (bh)   // K / V head of query head bh: its own (grouped-query forms: attn_fwd_gqa.hip)
 template <int D, int NW, bool VT, int ABL = 0>
 __global__ __launch_bounds__(NW * 64, (NW >= 4 ? 2 : 1)) void attn_fwd_kernel(
     const half_t* __restrict__ Q, const half_t* __restrict__ K, const half_t* __restrict__ V,
@@ -67,6 +68,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 4 ? 2 : 1)) void attn_fwd_causal_ke
   constexpr int ABL = 0;
 #include "attn_fwd_body.inc"
 }
+#undef LC_ATTN_KVH
 
 
 // (The round-1 four-cluster role-split kernel, attn_fwd_c4_kernel — 8 waves, K/V by LDS-DMA, 0.95-1.04 PFLOP/s at config 3 —

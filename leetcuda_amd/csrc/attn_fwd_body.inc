@@ -1,6 +1,7 @@
 // attn_fwd_body.inc — the body of attn_fwd_kernel and attn_fwd_causal_kernel (attn_fwd.hip), included INSIDE each kernel (the
 // non-causal kernel keeps its instruction stream: a shared __device__ function changed hipcc's scheduling of it).  The includer defines
-// D, NW, VT, ABL and the kernel arguments, plus `constexpr bool CAUSAL`.
+// D, NW, VT, ABL and the kernel arguments, plus `constexpr bool CAUSAL` and the macro LC_ATTN_KVH(bh): the K / V head that query head bh
+// reads (bh itself in attn_fwd.hip, bh / group size in the grouped-query kernels of attn_fwd_gqa.hip).
   using C = AttnCfg<D>;
   constexpr int NT = NW * 64;
   constexpr int DT = D / 32;   // 32-wide d tiles of Oᵀ
@@ -33,8 +34,9 @@
     q0 = (id - (int)bh * nqb) * (NW * 32) + wave * 32;
   }
   const half_t* Qb = Q + bh * (size_t)N * D;
-  const half_t* Kb = K + bh * (size_t)N * D;
-  const half_t* Vb = V + bh * (size_t)N * D;
+  const size_t kvh = LC_ATTN_KVH(bh);
+  const half_t* Kb = K + kvh * (size_t)N * D;
+  const half_t* Vb = V + kvh * (size_t)N * D;
   half_t* Ob = O + bh * (size_t)N * D;
 
   // ---- Q fragments (B operand of Sᵀ = K·Qᵀ): lane holds Q[q0 + l32][16*s + 8*hi .. +8]

@@ -77,6 +77,7 @@ static __device__ unsigned long long g_w4u_stamps[32];
 // before they are exponentiated, before the overflow guard's row max and (block 0) before the prologue's row max.  `order` 0: grid
 // enumerated longest block first (ids v = rank B H + head, rank 0 = the head's last query block), 1: head-major through xcd_remap as
 // the non-causal kernel.  Order changes no row's arithmetic.
+#define W4U_KVH(bh) (bh)   // K / V head of query head bh: its own (grouped-query forms: attn_w4u_gqa.hip)
 template <int D, bool VT, int WALK>
 __global__ __launch_bounds__(256) void attn_fwd_w4u_kernel(
     const half_t* __restrict__ Q, const half_t* __restrict__ K, const half_t* __restrict__ V,
@@ -97,6 +98,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w4u_causal_kernel(
   float* const lse = nullptr;
 #include "attn_w4u_body.inc"
 }
+#undef W4U_KVH
 
 // ---- split-KV combine: O[row] = sum_s w_s O_s[row] / sum_s w_s, w_s = 2^(L_s[row] - max_s L_s[row]).  One thread per 8 output
 // columns (16 B in per split, 16 B out); rows = B H N.  HBM-bound and tiny next to the attention itself: nsplit + 1 rows of D halves.

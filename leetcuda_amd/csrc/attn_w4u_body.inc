@@ -1,6 +1,8 @@
 // attn_w4u_body.inc — the body of attn_fwd_w4u_kernel and attn_fwd_w4u_causal_kernel (attn_w4u.hip), included INSIDE each kernel (the
 // non-causal kernel keeps its instruction stream: a shared __device__ function changed hipcc's scheduling of it).  The includer defines
-// D, VT, WALK and the kernel arguments as template parameters / names, plus `constexpr bool CAUSAL` and `order`.
+// D, VT, WALK and the kernel arguments as template parameters / names, plus `constexpr bool CAUSAL` and `order`, and the macro
+// W4U_KVH(bh): the K / V head that query head bh (flat index into [B H]) reads — bh itself in attn_w4u.hip, bh / group size in the
+// grouped-query kernels (attn_w4u_gqa.hip).  It is evaluated once per 256-row block, never inside the tile loop.
   static_assert(D == 64 || D == 128, "merged-phase attention kernel: D = 64 or 128 (D = 96 / 32: attn_w4i.hip)");
   static_assert(WALK >= 0 && WALK <= 3, "WALK: 0 one block per workgroup, 1 static persistent walk, 2 dynamic queue, 3 split-KV");
   static_assert(!CAUSAL || WALK == 0, "causal: one block per workgroup");
@@ -95,7 +97,8 @@
 
   // DMA of one K / V piece of the tile this period stages: descriptor + tile index chosen once per tile period (make_rsrc
   // reads the chosen base through readfirstlane: a descriptor hipcc cannot prove wave-uniform gets a waterfall loop per piece)
-  buf_rsrc_t dk = make_rsrc(K + bh * head_elems + k_base), dv = make_rsrc(V + bh * head_elems + v_base);
+  size_t kvh = W4U_KVH(bh);   // the K / V head of this block (wave-uniform, as bh)
+  buf_rsrc_t dk = make_rsrc(K + kvh * head_elems + k_base), dv = make_rsrc(V + kvh * head_elems + v_base);
   unsigned d_so = 0;
   char* d_slot = smem;
   unsigned d_sov = 0;   // (V: te * V_TILE_STRIDE — 128 B per tile when V is [D][N])
@@ -167,12 +170,13 @@
     const bool has_next = PERSIST && vbn < nblk;
     int q0n;
     const size_t bhn = head_of(has_next ? vbn : vb, q0n);
+    const size_t kvhn = W4U_KVH(bhn);   // (the next block's tiles 0 / 1 come from ITS K / V head: the same one or a later one, inside [B Hkv])
     const size_t nbh = SPLIT ? (size_t)(nblk / (nqb * nsplit)) : 0;          // B H (SPLIT: partial s of head bh = slab s nbh + bh)
     half_t* Ob = O + ((size_t)sp * nbh + bh) * head_elems;
     // tile t2 >= T of this block = tile t2 − T of the next one (no next block: the last tile again, into a dead slot)
     auto set_dma_tile = [&](int t2) {
       const bool own = t2 < T;
-      const size_t h = own ? bh : bhn;
+      const size_t h = own ? kvh : kvhn;
       dk = make_rsrc(K + h * head_elems + k_base);
       dv = make_rsrc(V + h * head_elems + v_base);
       const int te = own ? t2 : (has_next ? t2 - T : T - 1);
@@ -575,6 +579,7 @@
     if (!has_next) break;
     vb = vbn;
     bh = bhn;
+    kvh = kvhn;
     q0 = q0n;
   }
   if constexpr (WALK == 2) {

@@ -45,10 +45,13 @@ int check_attn_args(const void* Q, const void* K, const void* V, const void* O, 
 }
 
 // one attention call on checked arguments (lc_attn_fwd_f16 / _f16_ex / _bf16; bf16: raw 16-bit lanes, the kernel flavour decodes them)
-int attn_fwd(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, bool vt, bool bf16, bool causal, void* stream) {
+// gqa > 1 (lc_attn_fwd_f16_gqa): K / V hold H / gqa heads; the plan is the one of the MHA call, its kernels' `_gqa` twins run
+int attn_fwd(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, bool vt, bool bf16, bool causal, void* stream,
+             int gqa = 1) {
   if (int rc = launch_guard()) return rc;
   AttnPlan p;
   if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, vt, bf16, causal, &p)) return rc;
+  p.gqa = gqa;
   return launch_attn_plan(p, static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V), static_cast<half_t*>(O), B, H, N,
                           D, vt, bf16, static_cast<hipStream_t>(stream));
 }
@@ -135,6 +138,22 @@ int lc_attn_kernel_name_ex(int BH, int N, int D, int flags, char* buf, int bufle
   AttnPlan p;
   if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, vt != 0, false, true, &p)) return rc;
   format_attn(p, D, vt != 0, false, buf, buflen);
+  return LC_OK;
+}
+
+int lc_attn_kernel_name_gqa(int BH, int G, int N, int D, int flags, char* buf, int buflen) {
+  if (G == 1) return lc_attn_kernel_name_ex(BH, N, D, flags, buf, buflen);
+  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  if (G < 1 || (BH > 0 && BH % G != 0)) return LC_ERR_SHAPE;
+  if (N <= 0 || N % KVB != 0) return LC_ERR_SHAPE;   // (the codes lc_attn_fwd_f16_gqa returns)
+  if (D > 0 && (size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;
+  if (D != 32 && D != 64 && D != 96 && D != 128) return LC_ERR_HEADDIM;
+  const bool vt = (flags & LC_ATTN_V_TRANSPOSED) != 0;
+  AttnPlan p;
+  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, vt, false, (flags & LC_ATTN_CAUSAL) != 0, &p)) return rc;
+  p.gqa = G;
+  format_attn(p, D, vt, false, buf, buflen);
   return LC_OK;
 }
 
@@ -280,6 +299,16 @@ int lc_attn_fwd_f16_ex(const void* Q, const void* K, const void* V, void* O, int
   if (!(flags & LC_ATTN_CAUSAL)) return lc_attn_fwd_f16(Q, K, V, O, B, H, N, D, vt, LC_ATTN_SPLIT_Q, 0, 2, stream);
   if (int rc = check_attn_args(Q, K, V, O, B, H, N, D, 1)) return rc;
   return attn_fwd(Q, K, V, O, B, H, N, D, vt != 0, false, true, stream);
+}
+
+int lc_attn_fwd_f16_gqa(const void* Q, const void* K, const void* V, void* O, int B, int H, int Hkv, int N, int D, int flags, void* stream) {
+  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
+  if (Hkv == H) return lc_attn_fwd_f16_ex(Q, K, V, O, B, H, N, D, flags, stream);   // G = 1 IS that call: same plan, kernel and bits
+  if (!Q || !K || !V || !O) return LC_ERR_ARG;
+  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
+  if (int rc = check_attn_args(Q, K, V, O, B, H, N, D, 1)) return rc;
+  if (D != 32 && D != 64 && D != 96 && D != 128) return LC_ERR_HEADDIM;   // (D >= 256: no grouped-query kernels yet)
+  return attn_fwd(Q, K, V, O, B, H, N, D, (flags & LC_ATTN_V_TRANSPOSED) != 0, false, (flags & LC_ATTN_CAUSAL) != 0, stream, H / Hkv);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,
@@ -474,6 +503,11 @@ extern "C" int lc_attn_slowpath_stats(unsigned* out4, int reset) {
   if (int rc = lc::diag_attn_slowpath_u_d128(out4, reset)) return rc;
   if (int rc = lc::diag_attn_slowpath_u_d128t(out4, reset)) return rc;
   if (int rc = lc::diag_attn_slowpath_u_d64(out4, reset)) return rc;
-  return lc::diag_attn_slowpath_u_d64t(out4, reset);
+  if (int rc = lc::diag_attn_slowpath_u_d64t(out4, reset)) return rc;
+  if (int rc = lc::diag_attn_slowpath_g_gqa(out4, reset)) return rc;   // ... and of the grouped-query units
+  if (int rc = lc::diag_attn_slowpath_u_gqa_d128(out4, reset)) return rc;
+  if (int rc = lc::diag_attn_slowpath_u_gqa_d128t(out4, reset)) return rc;
+  if (int rc = lc::diag_attn_slowpath_u_gqa_d64(out4, reset)) return rc;
+  return lc::diag_attn_slowpath_u_gqa_d64t(out4, reset);
 }
 

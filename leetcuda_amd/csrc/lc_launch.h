@@ -214,6 +214,9 @@ struct AttnPlan;
 int launch_hgemm(const HgemmPlan& p, const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int swizzle_stride, hipStream_t st);
 int launch_attn_plan(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt, bool bf16,
                      hipStream_t st);
+// tu_attn_gqa.hip: a plan with AttnPlan::gqa > 1 (lc_attn_fwd_f16_gqa; K / V hold H / gqa heads): the `_gqa` twin of the plan's kernel
+int launch_attn_plan_gqa(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt,
+                         hipStream_t st);
 int launch_clock_probe(unsigned long long* out_u64x2, hipStream_t st);   // lc_clock_probe_kernel: shader cycles, the constant 100 MHz clock
 // the mid-size kernel (hgemm_mid.hip, tu_mid.hip): (64 tmw) x (64 tnw) tiles, ns ring slots
 int launch_hgemm_mid(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int tnw, int ns, int pw,
@@ -251,10 +254,27 @@ int diag_attn_slowpath_u_d128(unsigned* out4, int reset);   // slow-path counter
 int diag_attn_slowpath_u_d128t(unsigned* out4, int reset);
 int diag_attn_slowpath_u_d64(unsigned* out4, int reset);
 int diag_attn_slowpath_u_d64t(unsigned* out4, int reset);
+// tu_attn_w4u_gqa_{d128,d128t,d64,d64t}.hip: the grouped-query forms (attn_w4u_gqa.hip; K / V hold H / kvg heads, query head h reads K / V head
+// h / kvg): the launchers above with the group size as one more argument; every walk, fallback and the split-KV workspace as above
+int launch_attn_w4u_gqa_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
+int launch_attn_w4u_gqa_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
+int launch_attn_w4u_gqa_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
+int launch_attn_w4u_gqa_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
+int launch_attn_w4u_causal_gqa_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
+int launch_attn_w4u_causal_gqa_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
+int launch_attn_w4u_causal_gqa_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
+int launch_attn_w4u_causal_gqa_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
+int diag_attn_slowpath_u_gqa_d128(unsigned* out4, int reset);
+int diag_attn_slowpath_u_gqa_d128t(unsigned* out4, int reset);
+int diag_attn_slowpath_u_gqa_d64(unsigned* out4, int reset);
+int diag_attn_slowpath_u_gqa_d64t(unsigned* out4, int reset);
 // tu_attn_w4i.hip: the generated merged-phase kernel (attn_w4i.hip: a phase = one generated asm statement): D in {32, 64, 96, 128},
 // N % 256 == 0, V as [B,H,N,D]; the only merged-phase kernel for D = 96 / 32
 int launch_attn_w4i(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, int sched, hipStream_t st);
 int diag_attn_slowpath_g(unsigned* out4, int reset);   // + the slow-path counters of the w4i kernels
+// tu_attn_w4i_gqa.hip: its grouped-query form attn_fwd_w4i_gqa_kernel<D, SCHED> (K / V hold H / kvg heads)
+int launch_attn_w4i_gqa(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, int sched, int kvg, hipStream_t st);
+int diag_attn_slowpath_g_gqa(unsigned* out4, int reset);
 // tu_attn_big.hip: full-width large-head-dim kernel, D in {256, 512}, N % 128 == 0, V as [B,H,N,D]; fp16 or bf16
 int launch_attn_bigd2(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool bf16, bool bigd3,
                       hipStream_t st);   // bigd3: attn_bigd3 instead (lc_tune_set "attn_d512" = 2)

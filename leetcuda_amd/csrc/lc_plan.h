@@ -109,7 +109,8 @@ enum class AKern { W4U, W4I, LOCKSTEP, BIGD4, BIGD6, BIGD7, BIGD2, BIGD3, COLSPL
 struct AttnPlan {   // walk / nsplit: W4U; sched: W4I ("attn_w4i_sched"); nw: LOCKSTEP / COLSPLIT waves; span8: BIGD4's DMA spread in eighths
   AKern kern;         // of a phase ("attn_d1024"; 0 = the default, 8); abl: LOCKSTEP's LC_DIAG ablation ("attn_ablate"; D = 128, V as [B,H,N,D])
   int walk, nsplit, sched, nw, span8, abl, order;   // order: W4U_CAUSAL's grid order
-};
+  int gqa;            // group size H / Hkv of a grouped-query call (lc_attn_fwd_f16_gqa sets it AFTER plan_attn: the planner never sees Hkv);
+};                    // > 1: the `_gqa` twin of the plan's kernel runs (tu_attn_gqa.hip) and format_attn names it; 0 / 1: the kernels above
 int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, bool causal, AttnPlan* p);
 void format_attn(const AttnPlan& p, int D, bool vt, bool bf16, char* buf, int buflen);
 

@@ -323,6 +323,7 @@ int launch_attn_plan_vt(const AttnPlan& p, const half_t* Q, const half_t* K, con
 
 int launch_attn_plan(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt, bool bf16,
                      hipStream_t st) {
+  if (p.gqa > 1) return bf16 ? LC_ERR_HEADDIM : launch_attn_plan_gqa(p, Q, K, V, O, B, H, N, D, vt, st);   // (K / V hold H / p.gqa heads)
   return vt ? launch_attn_plan_vt<true>(p, Q, K, V, O, B, H, N, D, bf16, st) : launch_attn_plan_vt<false>(p, Q, K, V, O, B, H, N, D, bf16, st);
 }
 

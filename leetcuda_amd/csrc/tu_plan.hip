@@ -695,6 +695,14 @@ void format_attn(const AttnPlan& p, int D, bool v_transposed, bool bf16, char* b
     case AKern::W4U_CAUSAL: snprintf(buf, buflen, "attn_fwd_w4u_causal_kernel<%d,%s>", D, vt); break;
     case AKern::LOCKSTEP_CAUSAL: snprintf(buf, buflen, "attn_fwd_causal_kernel<%d,%d,%s>", D, p.nw, vt); break;
   }
+  if (p.gqa > 1) {   // the grouped-query twin: "_kernel<" -> "_gqa_kernel<", same template arguments
+    char* at = strstr(buf, "_kernel<");
+    const size_t len = strlen(buf);
+    if (at && len + 4 < (size_t)buflen) {
+      memmove(at + 4, at, len - (size_t)(at - buf) + 1);
+      memcpy(at, "_gqa", 4);
+    }
+  }
 }
 
 }  // namespace lc

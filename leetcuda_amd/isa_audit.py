@@ -51,7 +51,7 @@ from pathlib import Path
 # kernel-name regex -> AGPR ranges owned by the kernel's asm statements (inclusive)
 OWNED_AGPRS = [
     (re.compile(r"hgemm_w4b_kernel|hgemm_w4x_kernel|hgemm_w4y_kernel|gemm_fp8_w4_kernel|gemm_fp8_w4k_kernel"), [(0, 255)]),
-    (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
+    (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
 ]
 
 # kernel-name regex -> literal arch VGPR range owned by the kernel's asm (inclusive)
@@ -62,6 +62,11 @@ OWNED_VGPRS = [
     (re.compile(r"attn_fwd_w4i_kernelILi64E"), (88, 255)),
     (re.compile(r"attn_fwd_w4i_kernelILi96E"), (72, 255)),
     (re.compile(r"attn_fwd_w4i_kernelILi128E"), (64, 255)),
+    # ... and its grouped-query twins (tu_attn_w4i_gqa.hip): the same register maps
+    (re.compile(r"attn_fwd_w4i_gqa_kernelILi32E"), (104, 255)),
+    (re.compile(r"attn_fwd_w4i_gqa_kernelILi64E"), (88, 255)),
+    (re.compile(r"attn_fwd_w4i_gqa_kernelILi96E"), (72, 255)),
+    (re.compile(r"attn_fwd_w4i_gqa_kernelILi128E"), (64, 255)),
 ]
 
 VALU_TO_MFMA_STATES = 2

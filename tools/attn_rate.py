@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+   spec = B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
           causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
-          instead of this library (context only); knobs = lc_tune_set keys attn_nw / attn_walk / attn_split / attn_d512 / attn_w4i_sched /
-          attn_causal_order)
+          instead of this library (context only); kvh = K: grouped-query attention, K / V tensors with K heads through lc_attn_fwd_f16_gqa
+          (FLOPs counted as for the H query heads); kvh = K with expand: what a caller without that entry does — repeat_interleave K and V
+          to H heads in every step, then the MHA call; kvh = K with expanded: the MHA call on K / V expanded once, outside the timing
+          (the same values through the MHA kernel: the reference for the GQA kernel's time); knobs = lc_tune_set keys attn_nw / attn_walk / attn_split / attn_d512 /
+          attn_w4i_sched / attn_causal_order)
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
 cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
 causal: half of that, the flash-attn convention) and the median time per call."""
@@ -35,8 +38,8 @@ KNOBS = {"bigd_stagger": "attn_bigd_stagger", "bigd_map": "attn_bigd_map", "nw":
 cache = {}
 
 
-def tensors(B, H, N, D, bf16, zero):
-    key = (B, H, N, D, bf16, zero)
+def tensors(B, H, N, D, bf16, zero, kvh=0):
+    key = (B, H, N, D, bf16, zero, kvh)
     if key not in cache:
         cache.clear()                                   # one shape resident at a time
         torch.manual_seed(0)
@@ -44,6 +47,9 @@ def tensors(B, H, N, D, bf16, zero):
         mk = (lambda: torch.zeros(B, H, N, D, device="cuda", dtype=dt)) if zero else \
              (lambda: torch.randn(B, H, N, D, device="cuda").to(dt))
         cache[key] = (mk(), mk(), mk(), torch.zeros(B, H, N, D, device="cuda", dtype=dt))
+        if kvh:                                         # K / V [B, kvh, N, D]: the first kvh heads of the same random data
+            q, k, v, o = cache[key]
+            cache[key] = (q, k[:, :kvh].contiguous(), v[:, :kvh].contiguous(), o)
     return cache[key]
 
 
@@ -51,8 +57,12 @@ def run(spec):
     shape, *opts = spec.split(":")
     B, H, N, D = (int(x) for x in shape.split(","))
     bf16, zero, vt, causal, sdpa = "bf16" in opts, "zero" in opts, "vt" in opts, "causal" in opts, "sdpa" in opts
-    knobs = {KNOBS[o.split("=")[0]]: int(o.split("=")[1]) for o in opts if "=" in o}
-    q, k, v, o = tensors(B, H, N, D, bf16, zero)
+    kvh = next((int(o.split("=")[1]) for o in opts if o.startswith("kvh=")), 0)
+    expand = "expand" in opts
+    if kvh and (bf16 or sdpa or H % kvh != 0):
+        raise SystemExit(f"{spec}: kvh needs fp16, this library and H % kvh == 0")
+    knobs = {KNOBS[o.split("=")[0]]: int(o.split("=")[1]) for o in opts if "=" in o and not o.startswith("kvh=")}
+    q, k, v, o = tensors(B, H, N, D, bf16, zero, kvh)
     if vt:
         v = v.transpose(-2, -1).contiguous()
     for kk, vv in knobs.items():
@@ -62,6 +72,17 @@ def run(spec):
             name = "torch sdpa" + (" is_causal" if causal else "")
             vv = v.transpose(-2, -1) if vt else v
             step = lambda: torch.nn.functional.scaled_dot_product_attention(q, k, vv, is_causal=causal)  # noqa: E731
+        elif kvh and expand:
+            g = H // kvh
+            name = "expand + " + capi.attn_kernel_name(N, D, vt, bh=B * H, causal=causal)
+            step = lambda: capi.attn_fwd(q, k.repeat_interleave(g, dim=1), v.repeat_interleave(g, dim=1), o, v_transposed=vt, causal=causal)  # noqa: E731
+        elif kvh and "expanded" in opts:
+            ke, ve = k.repeat_interleave(H // kvh, dim=1).contiguous(), v.repeat_interleave(H // kvh, dim=1).contiguous()
+            name = capi.attn_kernel_name(N, D, vt, bh=B * H, causal=causal)
+            step = lambda: capi.attn_fwd(q, ke, ve, o, v_transposed=vt, causal=causal)  # noqa: E731
+        elif kvh:
+            name = capi.attn_kernel_name(N, D, vt, bh=B * H, causal=causal, group=H // kvh)
+            step = lambda: capi.attn_fwd_gqa(q, k, v, o, v_transposed=vt, causal=causal)  # noqa: E731
         else:
             name = capi.attn_kernel_name(N, D, vt, bf16, bh=B * H, causal=causal)
             step = (lambda: capi.attn_fwd_bf16(q, k, v, o)) if bf16 else (lambda: capi.attn_fwd(q, k, v, o, v_transposed=vt, causal=causal))
