@@ -18,7 +18,7 @@ LC_KNOB_SNAP(attn_d1024, 0, ok_span8, false)              // attn_bigd4's DMA sp
 LC_KNOB_SNAP(attn_w4i_sched, 1, ok_01, false)             // schedule of attn_fwd_w4i_kernel's generated phase statements (tools/gen_attn_w4i.py NSCHED; same bits)
 LC_KNOB(fp8_mx, 3, ok_03, false)                          // fp8 GEMM: 3 = MX K=128 MFMA, generated loop (gemm_fp8_w4k.hip); 1 = MX K=64, 4-wave kernel; 2 = MX K=64, 8-wave kernel; 0 = plain K=16 MFMA
 LC_KNOB_SNAP(attn_d512, 0, ok_04, false)                  // D = 256 / 512 / 1024: 0 = auto, 1 = column-split kernel, 2 = attn_bigd3, 3 = D = 256 / 512 on the other MFMA shape than auto (attn_bigd2 <-> attn_bigd7 / attn_bigd6), 4 = auto but attn_bigd7 on any grid
-LC_KNOB_SNAP(w4y_sched, 2, ok_w4y_sched, false)           // hgemm_w4y_kernel loop schedule 0..2 (lc_tune_set "w4y_sched"; same bits; 2 since round 6: + 0.4 ... 4 % at 8704 ... 12800, level at 8192, profiles/r6i_hgemm_knob_sched_ab.log)
+LC_KNOB_SNAP(w4y_sched, 2, ok_w4y_sched, false)           // hgemm_w4y_kernel loop schedule 0..2 (lc_tune_set "w4y_sched"; same bits; 0 / 1: k-step outer; 2 (default): the pair loop, hgemm_w4y_loop_pair.inc — both k-steps of an accumulator block back to back, the DMA pieces spread evenly — fewer joules per MFMA at the power cap, profiles/mfma_pair_probe.log, profiles/hgemm_pair_ab.log)
 LC_KNOB(hgemm_persist, 1, ok_01, false)                   // 1 (default) = hgemm_w4y_kernel as a persistent workgroup per CU when the tiles divide evenly (lc_tune_set "hgemm_persist")
 LC_KNOB(hgemm_stagger, 0, ok_stagger, false)              // K-loop stagger of hgemm_w4y_kernel (lc_tune_set "hgemm_stagger"): 0 = auto (by XCD), 1 << 27 = off, else cx | cm << 4 | cn << 8 | step << 12 | mask << 20
 LC_KNOB_SNAP(hgemm_tail, 1, ok_04, false)                 // 1 = hand the ragged last wave of the 256-tile kernel to 128 x 128 blocks (launch_mfma256: the mid-size kernel; 2 = round 5's 128-tile kernel + split-K), 0 = one launch

@@ -38,7 +38,7 @@ bool ok_split(int v) { return v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || 
 bool ok_span8(int v) { return v == 0 || v == 2 || v == 4 || v == 6; }
 bool ok_w4y_sched(int v) {
 #ifdef LC_DIAG
-  return v >= 0 && v <= 5;   // 3..5: ablations (results WRONG)
+  return v >= 0 && v <= 6;   // 3..5: ablations (results WRONG); 6: the pair loop's k-step-outer twin (hgemm_w4y_loop2.inc)
 #else
   return v >= 0 && v <= 2;
 #endif

@@ -63,6 +63,7 @@ int launch_w4_t(const half_t* A, const half_t* B, half_t* C, int M, int N, int K
       if (sched == 3) return launch_w4x_one<B_KN, 3>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
       if (sched == 4) return launch_w4x_one<B_KN, 4>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
       if (sched == 5) return launch_w4x_one<B_KN, 5>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
+      if (sched == 6) return launch_w4x_one<B_KN, 6>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);   // k-step-outer twin of the pair loop (correct results)
 #endif
       return launch_w4x_one<B_KN, 2>(A, B, C, M, N, K, tiles_m, tiles_n, pw, nblk, st);
     }

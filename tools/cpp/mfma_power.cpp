@@ -9,6 +9,14 @@
 //               wave tile scaled to this tile: 0.75 KiB per 32x32x16 MFMA) — the energy price of the operand reads.
 //   + 4: LDS-DMA stream (8 x 1 KiB per slab and wave: the L2 -> LDS rate of a 256 x 256 x 64 GEMM tile);
 //   + 8: the LDS reads ROTATE through the LDS area, so every k-step brings data the registers did not hold before.
+// Order of the 16x16x32 stream (same slab, fragments and FLOPs; does accumulator or source-operand reuse between
+// consecutive MFMAs change the joules?):
+//   + 128: PAIRS — k-step innermost: MFMA(ks 0) then MFMA(ks 1) back to back on the same a[4b:4b+3], A row stationary
+//          over its 8 pairs.  With bit 2 the fragments of the next slab land in a second register bank (both k-steps
+//          of a block are consumed together, so nothing can be refilled behind a k-step).
+//   + 256: ROUND-ROBIN — k-step outer like the plain order, but neither source operand repeats between consecutive
+//          MFMAs (the plain order keeps the A fragment for 8).
+//   + 512 (with 128): CHAINS OF 4 — every pair issued twice (twice the FLOPs per slab; no GEMM can use it, trend only).
 // Same FLOPs and operand bytes per slab in all modes, so the TFLOP/s ratio is the energy-per-FLOP ratio of the
 // instruction mix once the chip sits at its power limit (a kernel's throughput there is set by joules
 // per FLOP, not by issue slots).  Data: N(0,1) fp16 ("randn") or zeros (--zero) — zero operands toggle nothing.
@@ -95,7 +103,11 @@ __global__ __launch_bounds__(256) void mfma_power_kernel(const half8* __restrict
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   constexpr bool SHAPE16 = (MODE & 1) != 0, RD = (MODE & 2) != 0, DMA = (MODE & 4) != 0, ROT = (MODE & 8) != 0,
-                 SWAP = (MODE & 16) != 0, ALT = (MODE & 32) != 0, EPI = (MODE & 64) != 0;
+                 SWAP = (MODE & 16) != 0, ALT = (MODE & 32) != 0, EPI = (MODE & 64) != 0, PAIR = (MODE & 128) != 0,
+                 RR = (MODE & 256) != 0, CH4 = (MODE & 512) != 0;
+  static_assert(!(PAIR || RR || CH4) || SHAPE16, "the order bits are for the 16x16x32 stream");
+  static_assert(!CH4 || PAIR, "chains of 4 are doubled pairs");
+  static_assert(!(PAIR && RR), "one order at a time");
   unsigned long long t0 = 0, r0 = 0;
   if (blockIdx.x == 0 && tid == 0) {
     t0 = __builtin_readcyclecounter();
@@ -119,6 +131,49 @@ __global__ __launch_bounds__(256) void mfma_power_kernel(const half8* __restrict
   const char* gp = gsrc + (size_t)(blockIdx.x % nstreams) * region_bytes + wave * 8192 + lane * 16;
   size_t goff = 0;
   static_for<256>([&](auto r) { acc_zero<decltype(r)::value>(); });
+  // PAIR order, one slab: blocks (i, j) row by row, both k-steps of a block back to back.  (ca, cb) hold this slab's
+  // fragments; with RD the next slab's 24 fragments are read into (na, nb), one ds_read_b128 behind each of the first 24
+  // pairs (the plain order's one read per 2 MFMAs), and retire behind the last pair.
+  auto pair_slab = [&](half8(&ca)[8], half8(&cb)[16], half8(&na)[8], half8(&nb)[16], int it) {
+    const uint32_t la = la0 + (ROT ? (uint32_t)((it + 1) & 7) * 4096u : 0u), la2 = la + 65536;
+    static_for<32>([&](auto c) {
+      constexpr int b = decltype(c)::value, i = b >> 3, j = b & 7;
+      static_for<CH4 ? 2 : 1>([&](auto) {
+        mfma16<4 * b>(ca[i], cb[j]);
+        mfma16<4 * b>(ca[4 + i], cb[8 + j]);
+      });
+      if constexpr (RD && b < 24) {
+        if constexpr (b < 8) na[b] = lds_read_asm<b * 4096>(la);
+        else nb[b - 8] = lds_read_asm<(b & 15) * 4096>(b < 16 ? la : la2);
+      }
+      if constexpr (DMA && (b & 3) == 3) {   // one piece per 8 MFMAs = 8 per slab
+        constexpr int p = b >> 2;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gp + goff + p * 1024),
+                                         (__attribute__((address_space(3))) void*)(ring + wave * 8192 + p * 1024), 16, 0, 0);
+      }
+    });
+    if constexpr (RD) {
+      lds_wait(na[0], na[1], na[2], na[3], na[4], na[5]);
+      lds_wait(na[6], na[7], nb[0], nb[1], nb[2], nb[3]);
+      lds_wait(nb[4], nb[5], nb[6], nb[7], nb[8], nb[9]);
+      lds_wait(nb[10], nb[11], nb[12], nb[13], nb[14], nb[15]);
+    }
+    if constexpr (DMA) {
+      goff += 32768;
+      if (goff >= region_bytes) goff = 0;
+    }
+  };
+  if constexpr (PAIR) {
+    if constexpr (RD) {   // two register banks, alternating by slab parity (iters is even)
+      half8 ga[8], gb[16];
+      for (int it = 0; it < iters; it += 2) {
+        pair_slab(fa, fb, ga, gb, it);
+        pair_slab(ga, gb, fa, fb, it + 1);
+      }
+    } else {
+      for (int it = 0; it < iters; ++it) pair_slab(fa, fb, fa, fb, it);
+    }
+  } else
   for (int it = 0; it < iters; ++it) {
     const uint32_t la = la0 + (ROT ? (uint32_t)(it & 7) * 4096u : 0u), la2 = la + 65536;
     if constexpr (!SHAPE16) {
@@ -150,7 +205,8 @@ __global__ __launch_bounds__(256) void mfma_power_kernel(const half8* __restrict
           static_for<8>([&](auto j) { fb[8 * kn + decltype(j)::value] = lds_read_asm<((8 + 8 * kn + decltype(j)::value) & 15) * 4096>(((8 + 8 * kn + decltype(j)::value) < 16) ? la : la2); });
         }
         static_for<32>([&](auto c) {
-          constexpr int i = decltype(c)::value >> 3, j = decltype(c)::value & 7;
+          constexpr int cc = decltype(c)::value;   // RR: (i, j) = (c & 3, (c + c / 8) & 7) walks all 32 blocks, both change every step
+          constexpr int i = RR ? (cc & 3) : (cc >> 3), j = RR ? ((cc + (cc >> 3)) & 7) : (cc & 7);
           mfma16<4 * (8 * i + j)>(fa[4 * ks + i], fb[8 * ks + j]);
           if constexpr (DMA && (decltype(c)::value & 7) == 7) {   // 4 pieces per k-step = 8 per slab
             constexpr int p = 4 * ks + (decltype(c)::value >> 3);
@@ -204,7 +260,7 @@ Res run(const half8* src, const char* gsrc, size_t region, int nstreams, float* 
   CK(hipEventDestroy(e1));
   unsigned long long h[2];
   CK(hipMemcpy(h, clk, sizeof(h), hipMemcpyDeviceToHost));
-  const double flops = 2.0 * 64 * 128 * 64 * 4 * (double)grid * iters * launches * ((MODE & 32) ? 2 : 1);   // per wave: one slab per iteration
+  const double flops = 2.0 * 64 * 128 * 64 * 4 * (double)grid * iters * launches * ((MODE & (32 | 512)) ? 2 : 1);   // per wave: one slab per iteration
   return {flops / (ms * 1e-3) * 1e-12, (double)h[0] / (double)h[1] * 0.1};
 }
 
@@ -216,7 +272,7 @@ static double now_s() {
 
 int main(int argc, char** argv) {
   bool zero = false, bits = false;
-  int iters = 2000;
+  int iters = 2000;   // even: the pair modes unroll two slabs
   double seconds = 1.5;
   const char* modes = "0,1,2,3,10,11,4,14,15";
   int grid_mult = 1;   // workgroups per CU per launch (a GEMM launches tiles / CUs of them, one after the other)
@@ -260,7 +316,8 @@ int main(int argc, char** argv) {
   printf("mfma_power: %s, %d CUs x 4 waves, %d slabs per launch, %.1f s per mode, %s data\n", prop.gcnArchName, grid, iters, seconds,
          bits ? "random-bit" : zero ? "zero" : "randn");
   printf("DMA source: %d streams x %zu KiB; grid = %d workgroups\n", nstreams, region >> 10, grid);
-  printf("mode bits: 1 = 16x16x32 (else 32x32x16), 2 = fragments re-read from LDS, 8 = ... from rotating LDS offsets, 4 = LDS-DMA stream\n");
+  printf("mode bits: 1 = 16x16x32 (else 32x32x16), 2 = fragments re-read from LDS, 8 = ... from rotating LDS offsets, 4 = LDS-DMA stream; "
+         "16x16x32 order: 128 = k-step pairs per block, 256 = round-robin (no operand repeats), 128 + 512 = chains of 4\n");
   std::string ms(modes);
   size_t pos = 0;
   while (pos < ms.size()) {
@@ -272,7 +329,7 @@ int main(int argc, char** argv) {
 #define CASE(M)                                                                                        \
   case M: {                                                                                            \
     const Res q = run<M>(src, gsrc, region, nstreams, out, clk, iters, 40, grid);                                \
-    const double per = 2.0 * 64 * 128 * 64 * 4 * (double)grid * iters * ((M & 32) ? 2 : 1) / (q.tflops * 1e12);             \
+    const double per = 2.0 * 64 * 128 * 64 * 4 * (double)grid * iters * ((M & (32 | 512)) ? 2 : 1) / (q.tflops * 1e12);             \
     const int launches = (int)(seconds / per / 1.5) + 1;                                               \
     t0 = now_s();                                                                                      \
     r = run<M>(src, gsrc, region, nstreams, out, clk, iters, launches, grid);                                    \
@@ -280,10 +337,12 @@ int main(int argc, char** argv) {
   } break;
     switch (m) {
       CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(10) CASE(11) CASE(14) CASE(15) CASE(16) CASE(32) CASE(48) CASE(26) CASE(30) CASE(64) CASE(96)
+      CASE(129) CASE(257) CASE(641) CASE(139) CASE(267) CASE(143) CASE(271)
       default: printf("mode %d: not instantiated\n", m); continue;
     }
-    printf("MODE %2d [%s%s%s%s%s%s] %7.1f TFLOP/s @ %.2f GHz  t0=%.3f t1=%.3f\n", m, (m & 1) ? "16x16x32" : "32x32x16",
-           (m & 8) ? " +LDS(rot)" : (m & 2) ? " +LDS" : "", (m & 4) ? " +DMA" : "", (m & 16) ? " SrcB-shared" : "", (m & 32) ? " 256acc" : "", (m & 64) ? " +epilogue" : "", r.tflops, r.ghz, t0, t1);
+    printf("MODE %2d [%s%s%s%s%s%s%s] %7.1f TFLOP/s @ %.2f GHz  t0=%.3f t1=%.3f\n", m, (m & 1) ? "16x16x32" : "32x32x16",
+           (m & 8) ? " +LDS(rot)" : (m & 2) ? " +LDS" : "", (m & 4) ? " +DMA" : "", (m & 16) ? " SrcB-shared" : "", (m & 32) ? " 256acc" : "", (m & 64) ? " +epilogue" : "",
+           (m & 512) ? " chains-of-4" : (m & 128) ? " pairs" : (m & 256) ? " round-robin" : "", r.tflops, r.ghz, t0, t1);
     fflush(stdout);
   }
   return 0;

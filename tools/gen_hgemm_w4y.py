@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Emit leetcuda_amd/csrc/hgemm_w4y_loop.inc: the whole K loop of hgemm_w4y_kernel (hgemm_w4y.hip) as ONE asm statement.
+"""Emit leetcuda_amd/csrc/hgemm_w4y_loop{0,1,2,_pair,_nn}.inc: the whole K loop of hgemm_w4y_kernel (hgemm_w4y.hip) as ONE asm statement.
 
 Why a generator: with one wave per SIMD and 16-cycle MFMAs (v_mfma_f32_16x16x32_f16) every instruction hipcc adds between
 two MFMAs (an s_nop at each asm-statement boundary, its own s_waitcnt placement, SALU address arithmetic per DMA piece)
@@ -17,6 +17,9 @@ MFMA-busy where a hand-ordered stream of the same work reaches > 90 %.  This scr
   A DMA piece = s_add m0 / s_add soffset behind one MFMA, buffer_load_dwordx4 ... offen lds behind the next (an M0 write
   needs one wait state before the LDS-DMA that uses it).
 Ring, swizzles, piece order and the vmcnt(8) count are those of hgemm_w4b_kernel (hgemm_w4.hip).
+The above is bodies 0 / 1 / 2 (k-step outer) and the NN loop.  The TN default (the kernel's SCHED 2) is the PAIR loop: the DMA placement
+of body 2 with the two k-steps of every accumulator block issued back to back (the second MFMA's SrcC is the first one's result: fewer
+joules at the power cap), B in two register banks, unrolled over two K tiles: see "the pair loop" below.
 
 usage: tools/gen_hgemm_w4y.py [--check]     (--check: exit 1 if the committed .inc differs from what would be generated)
        tools/gen_hgemm_w4y.py --diag DIR   (LC_DIAG builds only: write the ablation loops 3..5 — results WRONG by design, never
@@ -185,6 +188,149 @@ def gen_body(sched):
     return L
 
 
+# ---- the pair loop (hgemm_w4y_loop_pair.inc, the kernel's SCHED 2): both k-steps of an accumulator block back to back ---------------
+# Why (profiles/mfma_pair_probe.log): at the power cap a 16x16x32 MFMA whose SrcC is the result of the MFMA in front of it costs
+# fewer joules — the stream of dependent pairs runs 5.7 % faster than the k-step-outer order on random data (10 % faster than an
+# order in which no operand repeats; chains of 4: 12 %), and draws 679 W instead of 754 W at equal rate on zero data.  The products,
+# the order per accumulator (k-step 0, then k-step 1) and so the bits are those of bodies 0 / 1 / 2.
+#   MFMA m of a K tile: block row i = m >> 4 (A fragments stationary over a row of 8 blocks), column j = (m >> 1) & 7, k-step m & 1.
+#   Both k-steps of a block are consumed together, so nothing can be refilled behind a k-step.  Literal VGPRs v60..v255:
+#     A(ks, i) = v[64 + 32 ks + 4 i ..]                one copy, row i refilled behind its last reader
+#     B(bank, ks, j) = v[128 + 64 bank + 32 ks + 4 j ..]  two banks, tile t in bank t & 1: the body is unrolled over two K tiles and
+#                                                      leaves after either half (the statement restarts at bank 0 for every C tile)
+#     v60..v63 = read addresses A k-step 0 / 1, B k-step 0 / 1 of tile t + 1, set behind the barrier of tile t
+#   Reads of tile t + 1 (32 ds_read_b128) sit between the barrier of tile t, which publishes it, and the barrier of tile t + 1, behind
+#   which its A slot is overwritten (its B slot one tile later), in order of first use:
+#     second half of tile t:      A row 0 and the 16 B fragments (into the other bank), one per ~3 MFMAs; retired by the loop-top wait
+#     first half of tile t + 1:   A rows 1..7, one per 4 MFMAs, each into the registers of the same row of tile t (whose readers all
+#                                 issued a tile ago); LDS reads return in order, so s_waitcnt lgkmcnt(N) in front of rows 1, 2, 3
+#                                 and the barrier's lgkmcnt(0) in front of row 4 retire exactly the rows that are due.
+#   DMA pieces: where gen_body(2) puts them (spread evenly: B pieces one per 8 MFMAs through the first half, A pieces one per 7 behind
+#   the barrier).  The vmcnt(8) wait | MFMA | barrier, stagger and ring rotation are those of gen_body(1).
+#   gen_body(2) / hgemm_w4y_loop2.inc — the same DMA placement with the k-step-outer MFMA order — stays generated as this loop's A/B
+#   twin (the only difference is the MFMA order and the fragment plan it forces); LC_DIAG builds instantiate it as SCHED 6.
+PAIR_V0 = 60
+VCLOB_PAIR = list(range(PAIR_V0, 256))
+PVA = [f"v{PAIR_V0}", f"v{PAIR_V0 + 1}"]       # A read address, k-step 0 / 1
+PVB = [f"v{PAIR_V0 + 2}", f"v{PAIR_V0 + 3}"]   # B read address, k-step 0 / 1
+
+
+def pa(ks, i):
+    b = 64 + 32 * ks + 4 * i
+    return f"v[{b}:{b + 3}]"
+
+
+def pb(bank, ks, j):
+    b = 128 + 64 * bank + 32 * ks + 4 * j
+    return f"v[{b}:{b + 3}]"
+
+
+def pair_rd_a(ks, i):
+    return f"ds_read_b128 {pa(ks, i)}, {PVA[ks]} offset:{i * 2048}"
+
+
+def pair_rd_b(bank, ks, j):
+    return f"ds_read_b128 {pb(bank, ks, j)}, {PVB[ks]} offset:{j * 2048}"
+
+
+def pair_reads_ahead(bank):
+    """A row 0 and the B fragments of a tile, in order of first use."""
+    return [pair_rd_a(0, 0), pair_rd_a(1, 0)] + [pair_rd_b(bank, ks, j) for j in range(8) for ks in range(2)]
+
+
+def gen_init_pair():
+    L = []
+    e = L.append
+    e("s_mov_b32 %[t], 0")
+    e("s_mov_b32 %[acur], %[a0]")
+    e("s_add_u32 %[anxt], %[a0], 0x8000")
+    e("s_add_u32 %[b0], %[a0], 0x10000")
+    e("s_add_u32 %[b1], %[a0], 0x18000")
+    e("s_add_u32 %[b2], %[a0], 0x20000")
+    for ks in range(2):
+        e(f"v_add_u32_e32 {PVA[ks]}, %[acur], %[ar{ks}]")
+        e(f"v_add_u32_e32 {PVB[ks]}, %[b0], %[br{ks}]")
+    L += pair_reads_ahead(0)   # tile 0: A row 0 and B into bank 0; its A rows 1..7 are read by the first half of the body
+    e("s_sub_u32 %[swp], %[kt], 1")
+    e("s_min_u32 %[swp], %[swp], 2")
+    for ins in STAGGER:
+        e(ins)
+    e("s_lshl_b32 %[t2off], %[swp], 7")
+    return L
+
+
+def gen_half(h):
+    """One K tile of the pair loop: the tile's B fragments are in bank h, the next tile's go into bank 1 - h.  From the
+    loop-top wait to the MFMA behind the loop counter's compare (the caller adds the branch)."""
+    L = []
+    e = L.append
+    e("s_waitcnt lgkmcnt(0)")
+    fill = {}
+
+    def after(m, *ins):
+        fill.setdefault(m, []).extend(ins)
+
+    # first half: A rows 1..7 of THIS tile (the addresses are those set behind the previous barrier / by gen_init_pair), B pieces of t + 2
+    rd_a = [(4 * r + 1, pair_rd_a(r & 1, 1 + (r >> 1))) for r in range(14)]
+    for m, ins in rd_a:
+        after(m, ins)
+    d0, dstep = 3, 8
+    after(d0 - 1, "s_add_u32 %[tmp], %[b2], %[wv]")
+    for p in range(8):
+        after(d0 + dstep * p, f"s_add_u32 m0, %[tmp], {p * PIECE_STEP}",
+              "s_mov_b32 %[soff], %[t2off]" if p == 0 else "s_add_u32 %[soff], %[soff], %[blk]")
+        after(d0 + 1 + dstep * p, f"buffer_load_dwordx4 %[ao{p & 1}], %[rb], %[soff] offen lds")
+    assert all(len(v) == 1 or not any(x.startswith("ds_read") for x in v) for v in fill.values())
+    waits = {}
+    for i in (1, 2, 3):   # rows 1..3 start before the barrier's lgkmcnt(0): all but the reads issued behind row i's two may be outstanding
+        issued = sum(m < 16 * i for m, _ in rd_a)
+        assert issued >= 2 * i and issued - 2 * i < 16
+        waits[16 * i] = f"s_waitcnt lgkmcnt({issued - 2 * i})"
+    bar = 64
+    assert max(m for m, _ in rd_a) < bar - 2
+    waits[bar] = "s_waitcnt vmcnt(8) lgkmcnt(0)"
+    # second half: addresses and the 18 first-use reads of tile t + 1, A pieces of tile t + 2, ring rotation, loop counter
+    after(bar, "s_barrier", f"v_add_u32_e32 {PVA[0]}, %[anxt], %[ar0]", "s_add_u32 %[tmp], %[acur], %[wv]")
+    after(bar + 1, f"v_add_u32_e32 {PVA[1]}, %[anxt], %[ar1]", f"v_add_u32_e32 {PVB[0]}, %[b1], %[br0]",
+          f"v_add_u32_e32 {PVB[1]}, %[b1], %[br1]")
+    dma = [bar + 2 + 7 * g for g in range(8)]
+    for g, m in enumerate(dma):
+        after(m, f"s_add_u32 m0, %[tmp], {g * PIECE_STEP}",
+              "s_mov_b32 %[soff], %[t2off]" if g == 0 else "s_add_u32 %[soff], %[soff], %[blk]")
+        after(m + 1, f"buffer_load_dwordx4 %[ao{g & 1}], %[ra], %[soff] offen lds")
+    free = [m for m in range(dma[0] + 2, 126) if m not in fill]
+    ahead = pair_reads_ahead(1 - h)
+    for r, ins in enumerate(ahead):
+        after(free[3 * r // 2], ins)   # two reads per three free gaps
+    # ring rotation and the next tile's t2off = 128 min(t + 3, KT - 1): acur, anxt, b*, t2off are dead behind the first A piece and
+    # the address adds (the read addresses live in their own registers)
+    rot = [["s_mov_b32 %[swp], %[b0]"], ["s_mov_b32 %[b0], %[b1]"], ["s_mov_b32 %[b1], %[b2]"], ["s_mov_b32 %[b2], %[swp]"],
+           ["s_mov_b32 %[swp], %[acur]"], ["s_mov_b32 %[acur], %[anxt]"], ["s_mov_b32 %[anxt], %[swp]"],
+           ["s_add_u32 %[swp], %[t], 3"], ["s_sub_u32 %[t2off], %[kt], 1"], ["s_min_u32 %[swp], %[swp], %[t2off]"],
+           [STAGGER[0]], STAGGER[1:3], [STAGGER[3]], ["s_lshl_b32 %[t2off], %[swp], 7"]]
+    slots = [m for m in free if m not in fill]
+    place(rot, slots, after, "pair")
+    after(126, "s_add_u32 %[t], %[t], 1", "s_cmp_lt_u32 %[t], %[kt]")
+    for m in range(128):
+        i, j, ks = m >> 4, (m >> 1) & 7, m & 1
+        if m in waits:
+            e(waits[m])
+        e(f"v_mfma_f32_16x16x32_f16 {acc(i, j)}, {pb(h, ks, j)}, {pa(ks, i)}, {acc(i, j)}")
+        for ins in fill.get(m, []):
+            e(ins)
+    return L
+
+
+def gen_body_pair():
+    """The pair loop: two K tiles per trip, leaving behind either."""
+    lab, out = ".Lw4y_loop_%=", ".Lw4y_exit_%="
+    return [lab + ":"] + gen_half(0) + [f"s_cbranch_scc0 {out}"] + gen_half(1) + [f"s_cbranch_scc1 {lab}", out + ":"]
+
+
+def gen_pair():
+    return gen_init_pair() + gen_body_pair() + ["s_waitcnt vmcnt(0) lgkmcnt(0)"]
+
+
 def gen(sched):
     ablate = sched - NSCHED + 1 if sched >= NSCHED else 0   # 1 no DMA, 2 no vmcnt wait, 3 no reads
     base = 1 if ablate else sched
@@ -332,13 +478,16 @@ def render_nn():
             f"    : \"memory\", \"scc\", {vclob}, LC_AGPR_ALL);\n")
 
 
-def render(sched):
-    lines = gen(sched)
-    check_literal_vgprs(lines, VCLOB, f"hgemm_w4y TN loop, schedule {sched}")
+def render(sched, pair=False):
+    """sched 0..2 (+ the LC_DIAG ablations): hgemm_w4y_loop<sched>.inc; pair=True: hgemm_w4y_loop_pair.inc (same operands, wider clobber list)."""
+    lines = gen_pair() if pair else gen(sched)
+    VCLOB = VCLOB_PAIR if pair else globals()["VCLOB"]
+    check_literal_vgprs(lines, VCLOB, "hgemm_w4y TN pair loop" if pair else f"hgemm_w4y TN loop, schedule {sched}")
     body = "\n".join(f'    "{ln}\\n\\t"' for ln in lines)
     vclob = ", ".join(f'"v{r}"' for r in VCLOB)
-    n_mfma = sum(ln.startswith("v_mfma") for ln in lines)
-    head = (f"// GENERATED by tools/gen_hgemm_w4y.py (schedule {sched}) — do not edit ({len(lines)} instructions, {n_mfma} MFMAs per K tile).\n"
+    n_mfma = sum(ln.startswith("v_mfma") for ln in lines) // (2 if pair else 1)   # the pair loop is unrolled over two K tiles
+    what = "pair loop" if pair else f"schedule {sched}"
+    head = (f"// GENERATED by tools/gen_hgemm_w4y.py ({what}) — do not edit ({len(lines)} instructions, {n_mfma} MFMAs per K tile).\n"
             "// Operands (hgemm_w4y.hip): kt, stg (K-loop stagger in tiles, < kt), a0 (LDS address of A ring slot 0), wv (wave * 1024), blk (bytes between 32-row\n"
             "// blocks), ra / rb (buffer descriptors, u32x4 SGPR tuples), ao0 / ao1 (DMA lane offsets), ar0 / ar1 / br0 / br1\n"
             "// (fragment read lane offsets of k-step 0 / 1).\n")
@@ -362,6 +511,7 @@ def main():
         return 0
     todo = [(render(sched), out_path(sched)) for sched in range(NSCHED)]
     todo.append((render_nn(), ROOT / "leetcuda_amd" / "csrc" / "hgemm_w4y_loop_nn.inc"))
+    todo.append((render(2, pair=True), ROOT / "leetcuda_amd" / "csrc" / "hgemm_w4y_loop_pair.inc"))
     for text, out in todo:
         if "--check" in sys.argv:
             if not out.exists() or out.read_text() != text:
