@@ -32,28 +32,44 @@ int hgemm_f16(const Knobs& k, const void* A, const void* B, void* C, int M, int 
                       swizzle_stride, static_cast<hipStream_t>(stream));
 }
 
-// The argument checks of the attention entry points; their order decides which status a doubly-bad call gets.  grid_factor: what the
-// 1-D grid bound multiplies the 64-row query blocks by (lc_attn_fwd_bf16: 4).
-int check_attn_args(const void* Q, const void* K, const void* V, const void* O, int B, int H, int N, int D, int grid_factor) {
+constexpr int kAttnFlags = LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED;   // the flags of the _ex / _gqa calls
+
+// The argument checks of the attention entry points; their order decides which status a doubly-bad call gets.  Hkv: the K / V heads (H: not a
+// grouped-query call); grid_factor: what the 1-D grid bound multiplies the 64-row query blocks by (lc_attn_fwd_bf16: 4).
+int check_attn_args(const void* Q, const void* K, const void* V, const void* O, int B, int H, int Hkv, int N, int D, int grid_factor) {
   if (!Q || !K || !V || !O) return LC_ERR_ARG;
-  if (B <= 0 || H <= 0 || N <= 0 || D <= 0) return LC_ERR_SHAPE;
+  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
+  if (B <= 0 || N <= 0 || D <= 0) return LC_ERR_SHAPE;
   if (N % KVB != 0) return LC_ERR_SHAPE;
   if ((size_t)B * H * (size_t)(N / 64) * grid_factor > 0x7fffffffull) return LC_ERR_SHAPE;  // 1-D grid of workgroups
-  if ((size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;   // one head's K / V must fit the 32-bit buffer offsets of the LDS-DMA kernels
+  if (!attn_span_fits(N, D)) return LC_ERR_SHAPE;
   if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return LC_ERR_SHAPE;
+  if (Hkv != H && !is_small_headdim(D)) return LC_ERR_HEADDIM;   // (D >= 256: no grouped-query kernels yet)
   return LC_OK;
 }
 
-// one attention call on checked arguments (lc_attn_fwd_f16 / _f16_ex / _bf16; bf16: raw 16-bit lanes, the kernel flavour decodes them)
-// gqa > 1 (lc_attn_fwd_f16_gqa): K / V hold H / gqa heads; the plan is the one of the MHA call, its kernels' `_gqa` twins run
-int attn_fwd(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, bool vt, bool bf16, bool causal, void* stream,
-             int gqa = 1) {
+// one attention call on checked arguments (bf16: raw 16-bit lanes, the kernel flavour decodes them; c.gqa > 1: K / V hold H / c.gqa heads)
+int attn_fwd(const void* Q, const void* K, const void* V, void* O, const AttnCall& c, void* stream) {
   if (int rc = launch_guard()) return rc;
   AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), (long)B * H, N, D, vt, bf16, causal, &p)) return rc;
-  p.gqa = gqa;
-  return launch_attn_plan(p, static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V), static_cast<half_t*>(O), B, H, N,
-                          D, vt, bf16, static_cast<hipStream_t>(stream));
+  if (int rc = plan_attn(read_knobs(), c, &p)) return rc;
+  return launch_attn_plan(p, AttnPtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V), static_cast<half_t*>(O),
+                                      static_cast<hipStream_t>(stream)});
+}
+
+// The name calls: the buffer, group (G = H / Hkv, 1: not a grouped-query call), N, span and head-dim checks in the order of the forward call they
+// mirror; bad_n: the status of a bad N — LC_ERR_ARG for lc_attn_kernel_name[_bh], LC_ERR_SHAPE (what the forward call returns) for the newer calls.
+int attn_name(int BH, int G, int N, int D, int flags, bool bf16, int bad_n, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  if (G < 1 || (BH > 0 && BH % G != 0)) return LC_ERR_SHAPE;
+  if (N <= 0 || N % KVB != 0) return bad_n;
+  if (!attn_span_fits(N, D)) return LC_ERR_SHAPE;
+  if (G != 1 && !is_small_headdim(D)) return LC_ERR_HEADDIM;
+  AttnPlan p;
+  if (int rc = plan_attn(read_knobs(), AttnCall{BH > 0 ? (long)BH : -1, G, N, D, (flags & LC_ATTN_V_TRANSPOSED) != 0, bf16, (flags & LC_ATTN_CAUSAL) != 0}, &p))
+    return rc;
+  format_attn(p, buf, buflen);
+  return LC_OK;
 }
 
 // warmup + iters calls of `launch` (returns a status) between two events (lc_hgemm_time, lc_attn_time): ms per timed call
@@ -120,41 +136,17 @@ int lc_attn_kernel_name(int N, int D, int v_transposed, int bf16, char* buf, int
 }
 
 int lc_attn_kernel_name_bh(int BH, int N, int D, int v_transposed, int bf16, char* buf, int buflen) {
-  if (!buf || buflen < 8 || N <= 0 || N % KVB != 0) return LC_ERR_ARG;
-  if (D > 0 && (size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;   // (mirrors lc_attn_fwd_f16)
-  AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, v_transposed != 0, bf16 != 0, false, &p)) return rc;
-  format_attn(p, D, v_transposed != 0, bf16 != 0, buf, buflen);
-  return LC_OK;
+  return attn_name(BH, 1, N, D, v_transposed ? LC_ATTN_V_TRANSPOSED : 0, bf16 != 0, LC_ERR_ARG, buf, buflen);
 }
 
 int lc_attn_kernel_name_ex(int BH, int N, int D, int flags, char* buf, int buflen) {
-  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
-  const int vt = (flags & LC_ATTN_V_TRANSPOSED) != 0;
-  if (!(flags & LC_ATTN_CAUSAL)) return lc_attn_kernel_name_bh(BH, N, D, vt, 0, buf, buflen);
-  if (!buf || buflen < 8) return LC_ERR_ARG;
-  if (N <= 0 || N % KVB != 0) return LC_ERR_SHAPE;   // (the codes lc_attn_fwd_f16_ex returns)
-  if (D > 0 && (size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;
-  AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, vt != 0, false, true, &p)) return rc;
-  format_attn(p, D, vt != 0, false, buf, buflen);
-  return LC_OK;
+  return lc_attn_kernel_name_gqa(BH, 1, N, D, flags, buf, buflen);
 }
 
 int lc_attn_kernel_name_gqa(int BH, int G, int N, int D, int flags, char* buf, int buflen) {
-  if (G == 1) return lc_attn_kernel_name_ex(BH, N, D, flags, buf, buflen);
-  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
-  if (!buf || buflen < 8) return LC_ERR_ARG;
-  if (G < 1 || (BH > 0 && BH % G != 0)) return LC_ERR_SHAPE;
-  if (N <= 0 || N % KVB != 0) return LC_ERR_SHAPE;   // (the codes lc_attn_fwd_f16_gqa returns)
-  if (D > 0 && (size_t)N * (size_t)D * 2 >= 0x80000000ull) return LC_ERR_SHAPE;
-  if (D != 32 && D != 64 && D != 96 && D != 128) return LC_ERR_HEADDIM;
-  const bool vt = (flags & LC_ATTN_V_TRANSPOSED) != 0;
-  AttnPlan p;
-  if (int rc = plan_attn(read_knobs(), BH > 0 ? (long)BH : -1, N, D, vt, false, (flags & LC_ATTN_CAUSAL) != 0, &p)) return rc;
-  p.gqa = G;
-  format_attn(p, D, vt, false, buf, buflen);
-  return LC_OK;
+  if (flags & ~kAttnFlags) return LC_ERR_ARG;
+  // (G = 1 without the causal flag IS lc_attn_kernel_name_bh, its status for a bad N included)
+  return attn_name(BH, G, N, D, flags, false, G == 1 && !(flags & LC_ATTN_CAUSAL) ? LC_ERR_ARG : LC_ERR_SHAPE, buf, buflen);
 }
 
 int lc_tune_set(const char* key, int value) {
@@ -287,34 +279,27 @@ int lc_attn_fwd_f16(const void* Q, const void* K, const void* V, void* O, int B,
   (void)acc_f32;
   (void)stages;
   // (the family range check sits between the null check and the shape checks: both of its neighbours' LC_ERR_ARG outrank LC_ERR_SHAPE)
-  const int rc = check_attn_args(Q, K, V, O, B, H, N, D, 1);
+  const int rc = check_attn_args(Q, K, V, O, B, H, H, N, D, 1);
   if (rc == LC_ERR_ARG || family < LC_ATTN_SPLIT_Q || family > LC_ATTN_SPLIT_KV) return LC_ERR_ARG;
   if (rc) return rc;
-  return attn_fwd(Q, K, V, O, B, H, N, D, v_transposed != 0, false, false, stream);
+  return attn_fwd(Q, K, V, O, AttnCall{(long)B * H, 1, N, D, v_transposed != 0, false, false}, stream);
 }
 
 int lc_attn_fwd_f16_ex(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D, int flags, void* stream) {
-  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
-  const int vt = (flags & LC_ATTN_V_TRANSPOSED) != 0;
-  if (!(flags & LC_ATTN_CAUSAL)) return lc_attn_fwd_f16(Q, K, V, O, B, H, N, D, vt, LC_ATTN_SPLIT_Q, 0, 2, stream);
-  if (int rc = check_attn_args(Q, K, V, O, B, H, N, D, 1)) return rc;
-  return attn_fwd(Q, K, V, O, B, H, N, D, vt != 0, false, true, stream);
+  return lc_attn_fwd_f16_gqa(Q, K, V, O, B, H, H, N, D, flags, stream);
 }
 
+// Hkv = H IS the MHA call: same checks, plan, kernel and bits
 int lc_attn_fwd_f16_gqa(const void* Q, const void* K, const void* V, void* O, int B, int H, int Hkv, int N, int D, int flags, void* stream) {
-  if (flags & ~(LC_ATTN_CAUSAL | LC_ATTN_V_TRANSPOSED)) return LC_ERR_ARG;
-  if (Hkv == H) return lc_attn_fwd_f16_ex(Q, K, V, O, B, H, N, D, flags, stream);   // G = 1 IS that call: same plan, kernel and bits
-  if (!Q || !K || !V || !O) return LC_ERR_ARG;
-  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
-  if (int rc = check_attn_args(Q, K, V, O, B, H, N, D, 1)) return rc;
-  if (D != 32 && D != 64 && D != 96 && D != 128) return LC_ERR_HEADDIM;   // (D >= 256: no grouped-query kernels yet)
-  return attn_fwd(Q, K, V, O, B, H, N, D, (flags & LC_ATTN_V_TRANSPOSED) != 0, false, (flags & LC_ATTN_CAUSAL) != 0, stream, H / Hkv);
+  if (flags & ~kAttnFlags) return LC_ERR_ARG;
+  if (int rc = check_attn_args(Q, K, V, O, B, H, Hkv, N, D, 1)) return rc;
+  return attn_fwd(Q, K, V, O, AttnCall{(long)B * H, H / Hkv, N, D, (flags & LC_ATTN_V_TRANSPOSED) != 0, false, (flags & LC_ATTN_CAUSAL) != 0}, stream);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,
                      void* stream) {
-  if (int rc = check_attn_args(Q, K, V, O, B, H, N, D, 4)) return rc;
-  return attn_fwd(Q, K, V, O, B, H, N, D, false, true, false, stream);
+  if (int rc = check_attn_args(Q, K, V, O, B, H, H, N, D, 4)) return rc;
+  return attn_fwd(Q, K, V, O, AttnCall{(long)B * H, 1, N, D, false, true, false}, stream);
 }
 
 int lc_attn_entry_count(void) { return kNumAttnEntries; }
@@ -424,10 +409,10 @@ int lc_tune_calibrate(void* stream, float* out4) {
   int rc = LC_OK;
   if (hipMemsetAsync(buf, 0, 4 * elems * sizeof(half_t), st) != hipSuccess) rc = LC_ERR_LAUNCH;
   half_t *q = buf, *k = buf + elems, *v = buf + 2 * elems, *o = buf + 3 * elems;
+  const AttnPtrs ptrs{q, k, v, o, st};
   auto time_us = [&](int D, int bh, int N, int walk, int ns, double* us) -> int {
-    auto once = [&]() -> int {
-      return D == 128 ? launch_attn_w4u_d128(q, k, v, o, 1, bh, N, walk, ns, st) : launch_attn_w4u_d64(q, k, v, o, 1, bh, N, walk, ns, st);
-    };
+    const AttnW4uUnit* unit = find_attn_w4u(D, false, false);   // (D = 128 / 64)
+    auto once = [&]() -> int { return unit->launch(ptrs, bh, N, walk, ns, 1); };
     for (int i = 0; i < 3; ++i)
       if (int r = once()) return r;
     double best = 1e30;
@@ -498,16 +483,13 @@ int lc_clock_probe(void* out_u64x2, void* stream) {
 
 }  // extern "C"
 
+// every unit with slow-path counters: the MHA units, then the grouped-query ones (the last unit with an offender sets out4[3])
 extern "C" int lc_attn_slowpath_stats(unsigned* out4, int reset) {
-  if (int rc = lc::diag_attn_slowpath_g(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_u_d128(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_u_d128t(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_u_d64(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_u_d64t(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_g_gqa(out4, reset)) return rc;   // ... and of the grouped-query units
-  if (int rc = lc::diag_attn_slowpath_u_gqa_d128(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_u_gqa_d128t(out4, reset)) return rc;
-  if (int rc = lc::diag_attn_slowpath_u_gqa_d64(out4, reset)) return rc;
-  return lc::diag_attn_slowpath_u_gqa_d64t(out4, reset);
+  for (int gqa = 0; gqa < 2; ++gqa) {
+    if (int rc = kAttnW4iUnits[gqa]->slowpath(out4, reset)) return rc;
+    for (const AttnW4uUnit* u : kAttnW4uUnits)
+      if (u->gqa == (gqa != 0))
+        if (int rc = u->slowpath(out4, reset)) return rc;
+  }
+  return LC_OK;
 }
-

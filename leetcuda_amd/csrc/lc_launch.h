@@ -2,6 +2,7 @@
 // hold the kernels and the launch planning, built in parallel by leetcuda_amd/build.py).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 
 #include <atomic>
 #include <mutex>
@@ -211,12 +212,10 @@ inline int stagger_arg(int kt) {
 // tu_core.hip: what a plan (lc_plan.h) launches — the builtin-MFMA kernels of this unit or the launchers below
 struct HgemmPlan;
 struct AttnPlan;
+struct AttnPtrs;
 int launch_hgemm(const HgemmPlan& p, const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int swizzle_stride, hipStream_t st);
-int launch_attn_plan(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt, bool bf16,
-                     hipStream_t st);
-// tu_attn_gqa.hip: a plan with AttnPlan::gqa > 1 (lc_attn_fwd_f16_gqa; K / V hold H / gqa heads): the `_gqa` twin of the plan's kernel
-int launch_attn_plan_gqa(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt,
-                         hipStream_t st);
+// the plan's kernel on the plan's own problem (AttnPlan::call; gqa > 1: K / V hold H / gqa heads, the `_gqa` twin runs)
+int launch_attn_plan(const AttnPlan& p, const AttnPtrs& a);
 int launch_clock_probe(unsigned long long* out_u64x2, hipStream_t st);   // lc_clock_probe_kernel: shader cycles, the constant 100 MHz clock
 // the mid-size kernel (hgemm_mid.hip, tu_mid.hip): (64 tmw) x (64 tnw) tiles, ns ring slots
 int launch_hgemm_mid(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, bool b_kn, int tmw, int tnw, int ns, int pw,
@@ -237,56 +236,92 @@ int launch_w4_family(const half_t* A, const half_t* B, half_t* C, int M, int N, 
 int launch_valu_rung(const half_t* A, const half_t* B, half_t* C, int M, int N, int K, int rung, hipStream_t st);
 void valu_rung_tile(int rung, int* tm, int* tn, int* tk);
 const char* valu_rung_kernel_name(int rung);
-// tu_attn_w4u_{d128,d128t,d64,d64t}.hip: THE merged-phase attention kernel (attn_w4u.hip), one unit per (head dim, V layout): N % 256 == 0;
-// walk 0 = one 256-row query block per workgroup, 1 = persistent workgroup per CU with a static walk, 2 = persistent with a dynamic
-// per-XCD block queue (falls back to 0 when there are no more blocks than CUs), 3 = split-KV: nsplit workgroups per query block +
-// a combine kernel, partials in the stream's cached workspace (falls back to 0 while the stream is being captured)
-int launch_attn_w4u_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);
-int launch_attn_w4u_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);   // V as [B,H,D,N]
-int launch_attn_w4u_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);
-int launch_attn_w4u_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, hipStream_t st);    // V as [B,H,D,N]
-// causal (N % 256 == 0; attn_fwd_w4u_causal_kernel): order 0 = grid longest block first, 1 = head-major (tu_plan.hip choose_attn_causal)
-int launch_attn_w4u_causal_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
-int launch_attn_w4u_causal_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
-int launch_attn_w4u_causal_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
-int launch_attn_w4u_causal_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, hipStream_t st);
-int diag_attn_slowpath_u_d128(unsigned* out4, int reset);   // slow-path counters of each unit's kernels (host copy; resets when asked)
-int diag_attn_slowpath_u_d128t(unsigned* out4, int reset);
-int diag_attn_slowpath_u_d64(unsigned* out4, int reset);
-int diag_attn_slowpath_u_d64t(unsigned* out4, int reset);
-// tu_attn_w4u_gqa_{d128,d128t,d64,d64t}.hip: the grouped-query forms (attn_w4u_gqa.hip; K / V hold H / kvg heads, query head h reads K / V head
-// h / kvg): the launchers above with the group size as one more argument; every walk, fallback and the split-KV workspace as above
-int launch_attn_w4u_gqa_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
-int launch_attn_w4u_gqa_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
-int launch_attn_w4u_gqa_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
-int launch_attn_w4u_gqa_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int walk, int nsplit, int kvg, hipStream_t st);
-int launch_attn_w4u_causal_gqa_d128(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
-int launch_attn_w4u_causal_gqa_d128t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
-int launch_attn_w4u_causal_gqa_d64(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
-int launch_attn_w4u_causal_gqa_d64t(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int order, int kvg, hipStream_t st);
-int diag_attn_slowpath_u_gqa_d128(unsigned* out4, int reset);
-int diag_attn_slowpath_u_gqa_d128t(unsigned* out4, int reset);
-int diag_attn_slowpath_u_gqa_d64(unsigned* out4, int reset);
-int diag_attn_slowpath_u_gqa_d64t(unsigned* out4, int reset);
+// What every attention launcher is handed besides its shape: Q, O [B,H,N,D]; K, V [B,H / kvg,N,D] (V transposed: [B,H / kvg,D,N]); the stream.
+// The launchers take BH = B x H: no kernel tells a batch from a head (a grouped-query kernel reads K / V head bh / kvg, H % kvg == 0).
+struct AttnPtrs {
+  const half_t *Q, *K, *V;
+  half_t* O;
+  hipStream_t st;
+};
+// softmax scale 1 / sqrt(D) in the exp2 domain: the `sl2` argument of every attention kernel
+inline float attn_scale_log2e(int D) { return (1.0f / sqrtf((float)D)) * 1.4426950408889634f; }
+// the tail of every attention launcher: the dynamic-LDS attribute (a kernel that uses dynamic LDS), the launch, its status
+template <typename KernelT, typename... Args>
+int launch_attn_kernel(KernelT kern, dim3 grid, dim3 block, int lds, hipStream_t st, Args... args) {
+  if (lds > 0)
+    if (int rc = set_dyn_lds(kern, lds)) return rc;
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  return check_launch();
+}
+// ... for a kernel and its `_gqa` twin, which differ in one trailing argument: WITH_KVG: the twin, which takes the group size kvg = H / Hkv
+template <bool WITH_KVG, typename KernelT, typename... Args>
+int launch_attn_kernel_kvg(KernelT kern, dim3 grid, dim3 block, int lds, hipStream_t st, int kvg, Args... args) {
+  if constexpr (WITH_KVG) return launch_attn_kernel(kern, grid, block, lds, st, args..., kvg);
+  else return launch_attn_kernel(kern, grid, block, lds, st, args...);
+}
+// slow-path counters of ONE unit's kernels (its __device__ symbol; attn_mp.h LC_AN_SLOWPATH_SYM), added onto out4[0..2] (out4[3]: last
+// offender, taken when this unit has one); resets them when asked
+template <typename SymT>
+int attn_slowpath_read(const SymT& sym, unsigned* out4, int reset) {
+  unsigned mine[4] = {0, 0, 0, 0};
+  if (hipMemcpyFromSymbol(mine, HIP_SYMBOL(sym), 16) != hipSuccess) return LC_ERR_LAUNCH;
+  if (out4) {
+    for (int i = 0; i < 3; ++i) out4[i] += mine[i];
+    if (mine[0]) out4[3] = mine[3];
+  }
+  if (reset) {
+    const unsigned z[4] = {0, 0, 0, 0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(sym), z, 16) != hipSuccess) return LC_ERR_LAUNCH;
+  }
+  return LC_OK;
+}
+// tu_attn_w4u_{d128,d128t,d64,d64t}.hip: THE merged-phase attention kernel (attn_w4u.hip), one unit per (head dim, V layout), and
+// tu_attn_w4u_gqa_{d128,d128t,d64,d64t}.hip: its grouped-query forms (attn_w4u_gqa.hip; K / V hold H / kvg heads, query head h reads K / V head
+// h / kvg).  Each unit exports ONE record (tu_attn_w4u_impl.h); every unit has the same signatures, the MHA units are only ever handed kvg = 1.
+//   launch: N % 256 == 0; walk 0 = one 256-row query block per workgroup, 1 = persistent workgroup per CU with a static walk, 2 = persistent
+//     with a dynamic per-XCD block queue (falls back to 0 when there are no more blocks than CUs), 3 = split-KV: nsplit workgroups per query
+//     block + a combine kernel, partials in the stream's cached workspace (falls back to 0 while the stream is being captured)
+//   launch_causal: N % 256 == 0 (attn_fwd_w4u_causal_kernel); order 0 = grid longest block first, 1 = head-major (tu_plan.hip choose_attn_causal)
+//   slowpath: the slow-path counters of the unit's kernels (attn_slowpath_read)
+struct AttnW4uUnit {
+  int D;
+  bool vt, gqa;   // V as [B,H,D,N]; the `_gqa` kernels
+  int (*launch)(const AttnPtrs& a, int BH, int N, int walk, int nsplit, int kvg);
+  int (*launch_causal)(const AttnPtrs& a, int BH, int N, int order, int kvg);
+  int (*slowpath)(unsigned* out4, int reset);
+};
+extern const AttnW4uUnit g_attn_w4u_d128, g_attn_w4u_d128t, g_attn_w4u_d64, g_attn_w4u_d64t;
+extern const AttnW4uUnit g_attn_w4u_gqa_d128, g_attn_w4u_gqa_d128t, g_attn_w4u_gqa_d64, g_attn_w4u_gqa_d64t;
+// THE list of those units: what find_attn_w4u serves and lc_attn_slowpath_stats sums — a unit missing here cannot be launched either
+inline constexpr const AttnW4uUnit* kAttnW4uUnits[] = {&g_attn_w4u_d128,     &g_attn_w4u_d128t,     &g_attn_w4u_d64,     &g_attn_w4u_d64t,
+                                                       &g_attn_w4u_gqa_d128, &g_attn_w4u_gqa_d128t, &g_attn_w4u_gqa_d64, &g_attn_w4u_gqa_d64t};
+inline const AttnW4uUnit* find_attn_w4u(int D, bool vt, bool gqa) {   // nullptr: no such unit
+  for (const AttnW4uUnit* u : kAttnW4uUnits)
+    if (u->D == D && u->vt == vt && u->gqa == gqa) return u;
+  return nullptr;
+}
 // tu_attn_w4i.hip: the generated merged-phase kernel (attn_w4i.hip: a phase = one generated asm statement): D in {32, 64, 96, 128},
-// N % 256 == 0, V as [B,H,N,D]; the only merged-phase kernel for D = 96 / 32
-int launch_attn_w4i(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, int sched, hipStream_t st);
-int diag_attn_slowpath_g(unsigned* out4, int reset);   // + the slow-path counters of the w4i kernels
-// tu_attn_w4i_gqa.hip: its grouped-query form attn_fwd_w4i_gqa_kernel<D, SCHED> (K / V hold H / kvg heads)
-int launch_attn_w4i_gqa(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, int sched, int kvg, hipStream_t st);
-int diag_attn_slowpath_g_gqa(unsigned* out4, int reset);
+// N % 256 == 0, V as [B,H,N,D]; the only merged-phase kernel for D = 96 / 32; tu_attn_w4i_gqa.hip: its grouped-query form
+// attn_fwd_w4i_gqa_kernel<D, SCHED> (K / V hold H / kvg heads).  One record each (tu_attn_w4i_impl.h), indexed by "grouped-query".
+struct AttnW4iUnit {
+  int (*launch)(const AttnPtrs& a, int BH, int N, int D, int sched, int kvg);
+  int (*slowpath)(unsigned* out4, int reset);
+};
+extern const AttnW4iUnit g_attn_w4i, g_attn_w4i_gqa;
+inline constexpr const AttnW4iUnit* kAttnW4iUnits[2] = {&g_attn_w4i, &g_attn_w4i_gqa};
+// tu_attn_gqa.hip: the grouped-query lock-step kernels (attn_fwd_gqa.hip; the MHA ones live in tu_core.hip), nw = 8 / 4 / 2 waves
+int launch_attn_lockstep_gqa(const AttnPtrs& a, int BH, int N, int D, bool vt, bool causal, int nw, int kvg);
 // tu_attn_big.hip: full-width large-head-dim kernel, D in {256, 512}, N % 128 == 0, V as [B,H,N,D]; fp16 or bf16
-int launch_attn_bigd2(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool bf16, bool bigd3,
-                      hipStream_t st);   // bigd3: attn_bigd3 instead (lc_tune_set "attn_d512" = 2)
+int launch_attn_bigd2(const AttnPtrs& a, int BH, int N, int D, bool bf16, bool bigd3);   // bigd3: attn_bigd3 instead (lc_tune_set "attn_d512" = 2)
 // tu_attn_big4.hip: D = 1024 (attn_bigd4.hip: two waves share 32 query rows, each owns 512 columns; N % 64 == 0, V as [B,H,N,D], fp16) and
 // attn_bigd2's V-transposed instantiation (D = 256, N % 128 == 0, V as [B,H,D,N], fp16)
-int launch_attn_bigd4(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int span8, hipStream_t st);   // span8: DMA spread (eighths of a phase; 0 = default)
-int launch_attn_bigd2_vt(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, hipStream_t st);
+int launch_attn_bigd4(const AttnPtrs& a, int BH, int N, int span8);   // span8: DMA spread (eighths of a phase; 0 = default)
+int launch_attn_bigd2_vt(const AttnPtrs& a, int BH, int N, int D);
 // tu_attn_big6.hip: D = 512 on v_mfma_f32_16x16x32 (attn_bigd6.hip), N % 128 == 0, V as [B,H,N,D]; fp16 or bf16
-int launch_attn_bigd6(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, bool bf16, hipStream_t st);
+int launch_attn_bigd6(const AttnPtrs& a, int BH, int N, bool bf16);
 // tu_attn_big7.hip: D = 256, 64 query rows per wave on v_mfma_f32_16x16x32 (attn_bigd7.hip), N % 256 == 0, V as [B,H,N,D]; fp16 or bf16
-int launch_attn_bigd7(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, bool bf16, hipStream_t st);
-int launch_attn_bigd7_vt(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st);   // V as [B,H,D,N], fp16
+int launch_attn_bigd7(const AttnPtrs& a, int BH, int N, bool bf16);
+int launch_attn_bigd7_vt(const AttnPtrs& a, int BH, int N);   // V as [B,H,D,N], fp16
 // tu_fp8.hip: fp8 e4m3 GEMM, mx = 1 (MX, 4 waves) / 2 (MX, 8 waves) / 0 (plain K = 16)
 int launch_gemm_fp8(const uint8_t* A, const uint8_t* B, half_t* C, int M, int N, int K, float alpha, int tiles_m,
                     int tiles_n, int panel_w, int mx, hipStream_t st);

@@ -106,12 +106,22 @@ void format_hgemm(const HgemmPlan& p, int M, int N, bool b_kn, char* buf, int bu
 // Causal calls (lc_attn_fwd_f16_ex, choose_attn_causal): W4U_CAUSAL  attn_fwd_w4u_causal_kernel<D, VT> (D = 64 / 128, N % 256 == 0; one block
 // per workgroup, order = "attn_causal_order");  LOCKSTEP_CAUSAL  attn_fwd_causal_kernel<D, nw, VT> (everything else with D <= 128).
 enum class AKern { W4U, W4I, LOCKSTEP, BIGD4, BIGD6, BIGD7, BIGD2, BIGD3, COLSPLIT, W4U_CAUSAL, LOCKSTEP_CAUSAL };
+// The problem of one attention call; plan_attn keeps it in the plan, so that the name (format_attn) and the launch (launch_attn_plan) need no second copy.
+struct AttnCall {
+  long bh;     // B x H query heads; -1: unknown (lc_attn_kernel_name: "a grid that fills the GPU")
+  int gqa;     // group size H / Hkv of a grouped-query call, 1 = MHA.  The planner decides NOTHING by it: > 1 runs and names the `_gqa` twin of the
+  int N, D;    // kernel the MHA call of the same (B H, N, D, V layout, causal, knobs) gets (the merged-phase `_gqa` units, tu_attn_gqa.hip)
+  bool vt, bf16, causal;   // V as [B,H,D,N]; bf16 inputs and output; causal mask (fp16, D <= 128)
+};
+inline bool is_small_headdim(int D) { return D == 32 || D == 64 || D == 96 || D == 128; }   // the head dims of the D <= 128 kernels (choose_attn_nw)
+// one head's K / V must fit the 32-bit buffer offsets of the LDS-DMA kernels (a bound on positive sizes: the callers rank N, D <= 0 themselves)
+inline bool attn_span_fits(int N, int D) { return N <= 0 || D <= 0 || (size_t)N * (size_t)D * 2 < 0x80000000ull; }
 struct AttnPlan {   // walk / nsplit: W4U; sched: W4I ("attn_w4i_sched"); nw: LOCKSTEP / COLSPLIT waves; span8: BIGD4's DMA spread in eighths
   AKern kern;         // of a phase ("attn_d1024"; 0 = the default, 8); abl: LOCKSTEP's LC_DIAG ablation ("attn_ablate"; D = 128, V as [B,H,N,D])
   int walk, nsplit, sched, nw, span8, abl, order;   // order: W4U_CAUSAL's grid order
-  int gqa;            // group size H / Hkv of a grouped-query call (lc_attn_fwd_f16_gqa sets it AFTER plan_attn: the planner never sees Hkv);
-};                    // > 1: the `_gqa` twin of the plan's kernel runs (tu_attn_gqa.hip) and format_attn names it; 0 / 1: the kernels above
-int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, bool causal, AttnPlan* p);
-void format_attn(const AttnPlan& p, int D, bool vt, bool bf16, char* buf, int buflen);
+  AttnCall call;      // what was planned
+};
+int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p);
+void format_attn(const AttnPlan& p, char* buf, int buflen);
 
 }  // namespace lc

@@ -4,7 +4,7 @@
 #include <math.h>
 
 #include "lc_plan.h"
-#include "attn_fwd.hip"
+#include "tu_attn_lockstep_impl.h"
 #include "hgemm_generic.hip"
 #include "hgemm_edge.hip"
 #include "hgemm_mfma128.hip"
@@ -210,121 +210,75 @@ int launch_hgemm(const HgemmPlan& p, const half_t* A, const half_t* B, half_t* C
 // ------------------------------------------------------------------------------------------------
 // attention launchers
 namespace {
-template <int D, int NW, bool VT, int ABL = 0>
-int launch_attn(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N,
-                hipStream_t st) {
-  auto kern = attn_fwd_kernel<D, NW, VT, ABL>;
-  constexpr int lds = attn_lds_bytes<D, VT>();
-  if (int rc = set_dyn_lds(kern, lds)) return rc;
-  const int nqb = N / (NW * 32);
-  const dim3 grid((unsigned)((size_t)nqb * B * H)), block(NW * 64);
-  const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, grid, block, lds, st, Q, K, V, O, N, nqb, sl2);
-  return check_launch();
-}
-template <int D, bool VT>
-int launch_lockstep(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st) {
-#ifdef LC_DIAG
-  if constexpr (D == 128 && !VT) {   // perf-diagnosis instantiations (lc_tune_set "attn_ablate")
-    switch (p.abl) {
-      case 1: return launch_attn<D, 8, VT, 1>(Q, K, V, O, B, H, N, st);
-      case 2: return launch_attn<D, 8, VT, 2>(Q, K, V, O, B, H, N, st);
-      case 3: return launch_attn<D, 8, VT, 3>(Q, K, V, O, B, H, N, st);
-      case 4: return launch_attn<D, 8, VT, 4>(Q, K, V, O, B, H, N, st);
-      case 6: return launch_attn<D, 8, VT, 6>(Q, K, V, O, B, H, N, st);
-      case 7: return launch_attn<D, 8, VT, 7>(Q, K, V, O, B, H, N, st);
-      case 8: return launch_attn<D, 8, VT, 8>(Q, K, V, O, B, H, N, st);
-      case 16: return launch_attn<D, 8, VT, 16>(Q, K, V, O, B, H, N, st);
-      case 24: return launch_attn<D, 8, VT, 24>(Q, K, V, O, B, H, N, st);
-      case 30: return launch_attn<D, 8, VT, 30>(Q, K, V, O, B, H, N, st);
-      case 31: return launch_attn<D, 8, VT, 31>(Q, K, V, O, B, H, N, st);
-      case 32: return launch_attn<D, 8, VT, 32>(Q, K, V, O, B, H, N, st);
-      default: break;
-    }
-  }
-#endif
-  if (p.nw == 8) return launch_attn<D, 8, VT>(Q, K, V, O, B, H, N, st);
-  if (p.nw == 4) return launch_attn<D, 4, VT>(Q, K, V, O, B, H, N, st);
-  return launch_attn<D, 2, VT>(Q, K, V, O, B, H, N, st);
-}
-template <int D, int NW, bool VT>
-int launch_attn_causal(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st) {
-  auto kern = attn_fwd_causal_kernel<D, NW, VT>;
-  constexpr int lds = attn_lds_bytes<D, VT>();
-  if (int rc = set_dyn_lds(kern, lds)) return rc;
-  const int nqb = N / (NW * 32);
-  const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)nqb * B * H)), dim3(NW * 64), lds, st, Q, K, V, O, N, nqb, sl2);
-  return check_launch();
-}
-template <int D, bool VT>
-int launch_lockstep_causal(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st) {
-  if (p.nw == 8) return launch_attn_causal<D, 8, VT>(Q, K, V, O, B, H, N, st);
-  if (p.nw == 4) return launch_attn_causal<D, 4, VT>(Q, K, V, O, B, H, N, st);
-  return launch_attn_causal<D, 2, VT>(Q, K, V, O, B, H, N, st);
-}
-
 template <int D, int NW, bool VT, bool BF16 = false>
-int launch_attn_bigd(const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N,
-                     hipStream_t st) {
+int launch_attn_bigd(const AttnPtrs& a, int BH, int N) {
   constexpr int DO = D > 256 ? 256 : D;   // output columns per workgroup (D = 512: two column halves)
-  auto kern = attn_fwd_bigd_kernel<D, DO, NW, VT, BF16>;
-  constexpr int lds = attn_bigd_lds_bytes<NW>();
-  if (int rc = set_dyn_lds(kern, lds)) return rc;
   const int nqb = N / (NW * 32);
-  const dim3 grid((unsigned)((size_t)nqb * B * H * (D / DO))), block(NW * 64);
-  const float sl2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  hipLaunchKernelGGL(kern, grid, block, lds, st, Q, K, V, O, N, nqb, sl2);
-  return check_launch();
+  return launch_attn_kernel(attn_fwd_bigd_kernel<D, DO, NW, VT, BF16>, dim3((unsigned)((size_t)nqb * BH * (D / DO))), dim3(NW * 64), attn_bigd_lds_bytes<NW>(),
+                            a.st, a.Q, a.K, a.V, a.O, N, nqb, attn_scale_log2e(D));
 }
 template <int D, bool VT>   // the column-split kernel (bf16: D = 256 / 512, V as [B,H,N,D])
-int launch_colsplit(const AttnPlan& p, bool bf16, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, hipStream_t st) {
+int launch_colsplit(int nw, bool bf16, const AttnPtrs& a, int BH, int N) {
   if constexpr (!VT && D != 1024) {
-    if (bf16) return p.nw == 4 ? launch_attn_bigd<D, 4, false, true>(Q, K, V, O, B, H, N, st) : launch_attn_bigd<D, 2, false, true>(Q, K, V, O, B, H, N, st);
+    if (bf16) return nw == 4 ? launch_attn_bigd<D, 4, false, true>(a, BH, N) : launch_attn_bigd<D, 2, false, true>(a, BH, N);
   }
-  return p.nw == 4 ? launch_attn_bigd<D, 4, VT>(Q, K, V, O, B, H, N, st) : launch_attn_bigd<D, 2, VT>(Q, K, V, O, B, H, N, st);
+  return nw == 4 ? launch_attn_bigd<D, 4, VT>(a, BH, N) : launch_attn_bigd<D, 2, VT>(a, BH, N);
 }
-
 template <bool VT>
-int launch_attn_plan_vt(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool bf16,
-                        hipStream_t st) {
-  switch (p.kern) {
-    case AKern::W4U:
-      if (D == 128) return VT ? launch_attn_w4u_d128t(Q, K, V, O, B, H, N, p.walk, p.nsplit, st) : launch_attn_w4u_d128(Q, K, V, O, B, H, N, p.walk, p.nsplit, st);
-      return VT ? launch_attn_w4u_d64t(Q, K, V, O, B, H, N, p.walk, p.nsplit, st) : launch_attn_w4u_d64(Q, K, V, O, B, H, N, p.walk, p.nsplit, st);
-    case AKern::W4I: return launch_attn_w4i(Q, K, V, O, B, H, N, D, p.sched, st);
-    case AKern::LOCKSTEP:
-      return D == 32   ? launch_lockstep<32, VT>(p, Q, K, V, O, B, H, N, st)
-             : D == 64 ? launch_lockstep<64, VT>(p, Q, K, V, O, B, H, N, st)
-             : D == 96 ? launch_lockstep<96, VT>(p, Q, K, V, O, B, H, N, st)
-                       : launch_lockstep<128, VT>(p, Q, K, V, O, B, H, N, st);
-    case AKern::BIGD4: return launch_attn_bigd4(Q, K, V, O, B, H, N, p.span8, st);
-    case AKern::BIGD6: return launch_attn_bigd6(Q, K, V, O, B, H, N, bf16, st);
-    case AKern::BIGD7: return VT ? launch_attn_bigd7_vt(Q, K, V, O, B, H, N, st) : launch_attn_bigd7(Q, K, V, O, B, H, N, bf16, st);
-    case AKern::BIGD2:
-    case AKern::BIGD3:
-      return VT ? launch_attn_bigd2_vt(Q, K, V, O, B, H, N, D, st) : launch_attn_bigd2(Q, K, V, O, B, H, N, D, bf16, p.kern == AKern::BIGD3, st);
-    case AKern::COLSPLIT:
-      return D == 256   ? launch_colsplit<256, VT>(p, bf16, Q, K, V, O, B, H, N, st)
-             : D == 512 ? launch_colsplit<512, VT>(p, bf16, Q, K, V, O, B, H, N, st)
-                        : launch_colsplit<1024, VT>(p, bf16, Q, K, V, O, B, H, N, st);
-    case AKern::W4U_CAUSAL:
-      if (D == 128) return VT ? launch_attn_w4u_causal_d128t(Q, K, V, O, B, H, N, p.order, st) : launch_attn_w4u_causal_d128(Q, K, V, O, B, H, N, p.order, st);
-      return VT ? launch_attn_w4u_causal_d64t(Q, K, V, O, B, H, N, p.order, st) : launch_attn_w4u_causal_d64(Q, K, V, O, B, H, N, p.order, st);
-    case AKern::LOCKSTEP_CAUSAL:
-      return D == 32   ? launch_lockstep_causal<32, VT>(p, Q, K, V, O, B, H, N, st)
-             : D == 64 ? launch_lockstep_causal<64, VT>(p, Q, K, V, O, B, H, N, st)
-             : D == 96 ? launch_lockstep_causal<96, VT>(p, Q, K, V, O, B, H, N, st)
-                       : launch_lockstep_causal<128, VT>(p, Q, K, V, O, B, H, N, st);
-  }
-  return LC_ERR_HEADDIM;
+int launch_colsplit_d(int D, int nw, bool bf16, const AttnPtrs& a, int BH, int N) {
+  return D == 256   ? launch_colsplit<256, VT>(nw, bf16, a, BH, N)
+         : D == 512 ? launch_colsplit<512, VT>(nw, bf16, a, BH, N)
+                    : launch_colsplit<1024, VT>(nw, bf16, a, BH, N);
 }
 }  // namespace
 
-int launch_attn_plan(const AttnPlan& p, const half_t* Q, const half_t* K, const half_t* V, half_t* O, int B, int H, int N, int D, bool vt, bool bf16,
-                     hipStream_t st) {
-  if (p.gqa > 1) return bf16 ? LC_ERR_HEADDIM : launch_attn_plan_gqa(p, Q, K, V, O, B, H, N, D, vt, st);   // (K / V hold H / p.gqa heads)
-  return vt ? launch_attn_plan_vt<true>(p, Q, K, V, O, B, H, N, D, bf16, st) : launch_attn_plan_vt<false>(p, Q, K, V, O, B, H, N, D, bf16, st);
+// ONE dispatch for every attention plan.  c.gqa > 1 (K / V hold H / c.gqa heads): the `_gqa` twin of the plan's kernel — fp16 and D <= 128 only;
+// the merged-phase units by lookup (lc_launch.h), the lock-step twins in tu_attn_gqa.hip.  A plan without a kernel is LC_ERR_HEADDIM, never another kernel.
+int launch_attn_plan(const AttnPlan& p, const AttnPtrs& a) {
+  const AttnCall& c = p.call;
+  const int BH = (int)c.bh, N = c.N, D = c.D;   // (B H < 2^31: the entry points bound the grid)
+  const bool vt = c.vt, bf16 = c.bf16, g = c.gqa > 1;
+  if (g && (bf16 || !is_small_headdim(D))) return LC_ERR_HEADDIM;
+  switch (p.kern) {
+    case AKern::W4U:
+    case AKern::W4U_CAUSAL:
+      if (const AttnW4uUnit* u = find_attn_w4u(D, vt, g))
+        return p.kern == AKern::W4U ? u->launch(a, BH, N, p.walk, p.nsplit, c.gqa) : u->launch_causal(a, BH, N, p.order, c.gqa);
+      break;
+    case AKern::W4I:
+      if (!vt) return kAttnW4iUnits[g]->launch(a, BH, N, D, p.sched, c.gqa);
+      break;
+    case AKern::LOCKSTEP:
+    case AKern::LOCKSTEP_CAUSAL:
+      if (g) return launch_attn_lockstep_gqa(a, BH, N, D, vt, p.kern == AKern::LOCKSTEP_CAUSAL, p.nw, c.gqa);
+#ifdef LC_DIAG
+      if (p.kern == AKern::LOCKSTEP && D == 128 && !vt) {   // perf-diagnosis instantiations (lc_tune_set "attn_ablate")
+        switch (p.abl) {
+          case 1: return launch_lockstep_t<128, 8, false, false, 1>(a, BH, N, 1);
+          case 2: return launch_lockstep_t<128, 8, false, false, 2>(a, BH, N, 1);
+          case 3: return launch_lockstep_t<128, 8, false, false, 3>(a, BH, N, 1);
+          case 4: return launch_lockstep_t<128, 8, false, false, 4>(a, BH, N, 1);
+          case 6: return launch_lockstep_t<128, 8, false, false, 6>(a, BH, N, 1);
+          case 7: return launch_lockstep_t<128, 8, false, false, 7>(a, BH, N, 1);
+          case 8: return launch_lockstep_t<128, 8, false, false, 8>(a, BH, N, 1);
+          case 16: return launch_lockstep_t<128, 8, false, false, 16>(a, BH, N, 1);
+          case 24: return launch_lockstep_t<128, 8, false, false, 24>(a, BH, N, 1);
+          case 30: return launch_lockstep_t<128, 8, false, false, 30>(a, BH, N, 1);
+          case 31: return launch_lockstep_t<128, 8, false, false, 31>(a, BH, N, 1);
+          case 32: return launch_lockstep_t<128, 8, false, false, 32>(a, BH, N, 1);
+          default: break;
+        }
+      }
+#endif
+      return launch_lockstep(a, BH, N, D, vt, p.kern == AKern::LOCKSTEP_CAUSAL, p.nw, 1);
+    case AKern::BIGD4: return launch_attn_bigd4(a, BH, N, p.span8);
+    case AKern::BIGD6: return launch_attn_bigd6(a, BH, N, bf16);
+    case AKern::BIGD7: return vt ? launch_attn_bigd7_vt(a, BH, N) : launch_attn_bigd7(a, BH, N, bf16);
+    case AKern::BIGD2:
+    case AKern::BIGD3: return vt ? launch_attn_bigd2_vt(a, BH, N, D) : launch_attn_bigd2(a, BH, N, D, bf16, p.kern == AKern::BIGD3);
+    case AKern::COLSPLIT: return vt ? launch_colsplit_d<true>(D, p.nw, bf16, a, BH, N) : launch_colsplit_d<false>(D, p.nw, bf16, a, BH, N);
+  }
+  return LC_ERR_HEADDIM;
 }
 
 int launch_clock_probe(unsigned long long* out, hipStream_t st) {

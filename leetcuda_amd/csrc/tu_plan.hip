@@ -655,16 +655,22 @@ bool use_bigd7(const Knobs& kn, int D, bool vt, int N, long bh) {
 
 }  // namespace
 
-// ONE decision per attention call (lc_attn_fwd_f16 / _bf16 / _f16_ex launch it, lc_attn_kernel_name_bh / _ex report it; bf16 launches have
-// V as [B,H,N,D]; causal: fp16, D <= 128).  Returns LC_OK or LC_ERR_HEADDIM.
-int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, bool causal, AttnPlan* p) {
-  if (D == 32 || D == 64 || D == 96 || D == 128) {
+// ONE decision per attention call (lc_attn_fwd_f16 / _bf16 / _f16_ex / _f16_gqa launch it, lc_attn_kernel_name_bh / _ex / _gqa report it; bf16
+// launches have V as [B,H,N,D]; causal: fp16, D <= 128), kept in the plan with the call it was made for (c.gqa decides nothing here).  Returns
+// LC_OK or LC_ERR_HEADDIM.
+int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p) {
+  const long bh = c.bh;
+  const int N = c.N, D = c.D;
+  const bool vt = c.vt, bf16 = c.bf16;
+  if (is_small_headdim(D)) {
     if (bf16) return LC_ERR_HEADDIM;
-    *p = causal ? choose_attn_causal(k, D, N, bh) : choose_attn_nw(k, D, vt, N, bh);
+    *p = c.causal ? choose_attn_causal(k, D, N, bh) : choose_attn_nw(k, D, vt, N, bh);
+    p->call = c;
     return LC_OK;
   }
-  if (causal) return LC_ERR_HEADDIM;
+  if (c.causal) return LC_ERR_HEADDIM;
   *p = AttnPlan{};
+  p->call = c;
   p->span8 = k.attn_d1024;
   p->nw = N % 128 == 0 ? 4 : 2;
   if (use_bigd4(k, D, vt, N) && !bf16) p->kern = AKern::BIGD4;
@@ -677,9 +683,11 @@ int plan_attn(const Knobs& k, long bh, int N, int D, bool vt, bool bf16, bool ca
 }
 
 // The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).
-void format_attn(const AttnPlan& p, int D, bool v_transposed, bool bf16, char* buf, int buflen) {
+void format_attn(const AttnPlan& p, char* buf, int buflen) {
+  const int D = p.call.D;
+  const bool v_transposed = p.call.vt;
   const char* vt = v_transposed ? "true" : "false";
-  const char* bf = bf16 ? "true" : "false";
+  const char* bf = p.call.bf16 ? "true" : "false";
   switch (p.kern) {
     // (a persistent walk with no more blocks than CUs launches WALK 0; the name reports the walk asked for at this N; 3 = split-KV, whose
     // launch also runs attn_split_combine_kernel<D>)
@@ -695,7 +703,7 @@ void format_attn(const AttnPlan& p, int D, bool v_transposed, bool bf16, char* b
     case AKern::W4U_CAUSAL: snprintf(buf, buflen, "attn_fwd_w4u_causal_kernel<%d,%s>", D, vt); break;
     case AKern::LOCKSTEP_CAUSAL: snprintf(buf, buflen, "attn_fwd_causal_kernel<%d,%d,%s>", D, p.nw, vt); break;
   }
-  if (p.gqa > 1) {   // the grouped-query twin: "_kernel<" -> "_gqa_kernel<", same template arguments
+  if (p.call.gqa > 1) {   // the grouped-query twin: "_kernel<" -> "_gqa_kernel<", same template arguments
     char* at = strstr(buf, "_kernel<");
     const size_t len = strlen(buf);
     if (at && len + 4 < (size_t)buflen) {

@@ -318,3 +318,31 @@ def test_model_sized(oracle, shape, causal):
     c = ((torch.arange(B * Hkv, device="cuda") % 7 - 3).float() / 4).half().view(B, Hkv, 1, 1)      # -0.75 .. 0.75, neighbours differ
     oc = _gqa(capi, q, k, c.expand(B, Hkv, N, D).contiguous(), causal=causal)
     assert (oc.float() - expand_kv(c, G).float()).abs().max().item() < 1e-3
+
+
+@pytest.mark.parametrize("D,causal", [(128, True), (64, True), (128, False), (64, False), (96, False)])
+def test_slow_path_counters_of_the_gqa_units_are_summed_and_reset(D, causal):
+    """lc_attn_slowpath_stats covers the grouped-query units: on the inputs of tests/test_gpu_causal.py
+    test_overflow_slow_path_under_the_mask (scores that grow along the key index) the `_gqa` twin counts what the MHA kernel counts on
+    expanded K / V — the same body on the same values —, and a read with reset leaves nothing behind.  D = 64 / 128: the merged-phase
+    units (tu_attn_w4u_gqa_*.hip); D = 96: the generated kernel's (tu_attn_w4i_gqa.hip)."""
+    capi = _capi()
+    B, H, Hkv, N = 1, 4, 2, 1024
+    torch.manual_seed(1234 + D)
+    q = torch.full((B, H, N, D), 4.0 / D ** 0.5, dtype=torch.half, device="cuda")
+    ramp = (4.0 * torch.arange(N, device="cuda", dtype=torch.float32) / N).half()
+    k = ramp.view(1, 1, N, 1).expand(B, Hkv, N, D).contiguous()
+    v = torch.randn(B, Hkv, N, D, dtype=torch.half, device="cuda")
+    with _knobs(capi, rule_cus=256, attn_calib=1):      # (the split rule as on a 256-CU device with the built-in constants: no lock-step kernel here)
+        gqa, _ = _names(capi, q, k, False, causal)
+        assert "_gqa_kernel<" in gqa and gqa.startswith("attn_fwd_w4i_gqa" if D == 96 else "attn_fwd_w4u_"), gqa
+        capi.attn_slowpath_stats(reset=True)
+        _mha(capi, q, k, v, causal=causal)
+        m = capi.attn_slowpath_stats(reset=True)
+        _gqa(capi, q, k, v, causal=causal)
+        g = capi.attn_slowpath_stats(reset=True)
+        z = capi.attn_slowpath_stats(reset=False)
+    assert g[:3] == m[:3], (g, m)
+    if causal:
+        assert g[0] > 0, g
+    assert z[:3] == [0, 0, 0], z
