@@ -248,6 +248,62 @@ def test_status_strings_and_argument_errors(built):
     assert lib.lc_clock_probe(None, None) == capi.LC_ERR_ARG
 
 
+def test_fp8_entry_points_refuse_bad_arguments(built):
+    """lc_gemm_fp8_e4m3, lc_gemm_mxfp8 and lc_mxfp8_pack_scales: every refusal the header states, one violation per call on never-dereferenced
+    dummy pointers.  All of them return before the launch guard, so no device is needed — and no call here is legal (that one would launch)."""
+    from leetcuda_amd import capi
+    lib = capi.load()
+    ARG, SHAPE = capi.LC_ERR_ARG, capi.LC_ERR_SHAPE
+    p = C.c_void_p(4096)                                   # 16-byte aligned, never dereferenced
+    M, N, K = 512, 768, 384
+
+    def fp8(a=p, b=p, c=p, m=M, n=N, k=K):
+        return lib.lc_gemm_fp8_e4m3(a, b, c, m, n, k, 1.0, 1, None)
+
+    def mxf(a=p, pa=p, b=p, pb=p, c=p, m=M, n=N, k=K):
+        return lib.lc_gemm_mxfp8(a, pa, b, pb, c, m, n, k, 1.0, 1, None)
+
+    def pack(s=p, out=p, rows=M, k=K):
+        return lib.lc_mxfp8_pack_scales(s, out, rows, k, None)
+
+    # each null pointer (before any shape check: the dims below are bad too in the second pass)
+    for bad in ({}, {"m": 0}):
+        for name in "abc":
+            assert fp8(**{name: None}, **bad) == ARG, (name, bad)
+        for name in ("a", "pa", "b", "pb", "c"):
+            assert mxf(**{name: None}, **bad) == ARG, (name, bad)
+    assert pack(s=None) == ARG and pack(out=None) == ARG and pack(s=None, rows=0) == ARG
+    # non-positive dims; M, N not multiples of the 256 x 256 tile; K not a multiple of the 128-deep K tile
+    for fn in (fp8, mxf):
+        for name in "mnk":
+            for v in (0, -256, -1):
+                assert fn(**{name: v}) == SHAPE, (fn.__name__, name, v)
+        for name in "mn":
+            for v in (128, 255, 257, 384, 256 * 3 + 16):
+                assert fn(**{name: v}) == SHAPE, (fn.__name__, name, v)
+        for v in (32, 64, 96, 127, 129, 192, 128 * 5 + 64):
+            assert fn(k=v) == SHAPE, (fn.__name__, v)
+    for v in (0, -256, -1):
+        assert pack(rows=v) == SHAPE and pack(k=v) == SHAPE, v
+    for v in (128, 255, 257, 384):
+        assert pack(rows=v) == SHAPE, v
+    for v in (32, 64, 127, 129, 192):
+        assert pack(k=v) == SHAPE, v
+    # A / B / C off 16-byte alignment (8 is not enough), PA / PB / P off 8-byte alignment (4 is not enough)
+    for off in (1, 2, 4, 8, 12):
+        q = C.c_void_p(4096 + off)
+        for name in "abc":
+            assert fp8(**{name: q}) == SHAPE and mxf(**{name: q}) == SHAPE, (name, off)
+    for off in (1, 2, 4, 6):
+        q = C.c_void_p(4096 + off)
+        assert mxf(pa=q) == SHAPE and mxf(pb=q) == SHAPE and pack(out=q) == SHAPE, off
+    # MX only: K * 260 >= 2^31 is beyond the 32-bit DMA offsets of the one kernel that serves it (the first such K, and 2^23)
+    kbig = (((1 << 31) + 259) // 260 + 127) // 128 * 128
+    assert kbig % 128 == 0 and kbig * 260 >= 1 << 31 and (kbig - 128) * 260 < 1 << 31
+    for v in (kbig, 1 << 23, (1 << 31) - 128):
+        assert mxf(k=v) == SHAPE, v
+
+
 def test_hgemm_dispatch_covers_the_reference_legal_shapes(built):
     """Kernel selection needs no GPU (lc_hgemm_kernel_name reports the plan lc_hgemm_f16 launches: plan_hgemm).  The reference's kernels
     are legal on M, N multiples of 128 and K multiples of 32 (hgemm_mma_stage.cu:650,675-676): with a large 256-tileable interior those

@@ -173,7 +173,9 @@ def test_generated_fp8_k128_loop_is_current_and_consumes_the_right_tiles():
     """gemm_fp8_w4k's K loop (tools/gen_gemm_fp8_w4k.py): committed .inc == generator output, and a replay of the generated stream as a
     dataflow machine — LDS ring slots hold tile numbers, ds_reads copy (tile, operand, fragment, half) tags into registers, DMA pieces
     overwrite slots, the barrier publishes — must show every MFMA of K tile t consuming exactly A fragment i / B fragment j of tile t,
-    with every register half written by a read that an s_waitcnt lgkmcnt has retired (LDS reads return in order)."""
+    with every register half written by a read that an s_waitcnt lgkmcnt has retired (LDS reads return in order).  Under the K-loop
+    stagger (every start tile stg of every KT) "tile t" is MEMORY tile (min(t, KT - 1) + stg) mod KT — the tags are memory tiles, read
+    from the DMA / scale source offsets — and the walk consumes every memory tile in exactly one logical tile."""
     import importlib.util
     import re
     root = Path(__file__).resolve().parent.parent
@@ -184,10 +186,11 @@ def test_generated_fp8_k128_loop_is_current_and_consumes_the_right_tiles():
         assert out.read_text() == text, out
     for mx in (False, True):
         L = gen.gen(mx)
-        for KT in (1, 2, 3, 4, 7):
+        for KT, stg in ((kt, g) for kt in (1, 2, 3, 4, 5, 7) for g in range(kt)):
             # SGPR / VGPR state.  LDS slot addresses: A ring 0x0 / 0x8000, B ring 0x10000 / 0x18000 / 0x20000 relative to a0 = 0.
-            sg = {"kt": KT, "stg": 0, "a0": 0, "wv": 0, "blk": 0}
-            slot_tile = {0x0: 0, 0x8000: 1, 0x10000: 0, 0x18000: 1, 0x20000: None}   # what the prologue staged
+            sg = {"kt": KT, "stg": stg, "a0": 0, "wv": 0, "blk": 0}
+            mem = lambda t: (min(t, KT - 1) + stg) % KT      # memory tile of logical tile t (gemm_fp8_w4k.hip issue_prologue: clamp, then wrap)
+            slot_tile = {0x0: mem(0), 0x8000: mem(1), 0x10000: mem(0), 0x18000: mem(1), 0x20000: None}   # what the prologue staged
             pending_dma = []          # (slot address, tile) issued, not yet published by a vmcnt wait
             vaddr = {}                # address VGPR -> (slot address, register half)
             reg = {}                  # fragment register base -> {half: (tile, op, frag) or None}
@@ -195,6 +198,7 @@ def test_generated_fp8_k128_loop_is_current_and_consumes_the_right_tiles():
             scale_reg, scale_q, m0 = {}, [], None
             dirty = set()             # ring slots read since the last barrier (another wave may still be reading them)
             mf_seen, pc, scc, steps = [], 0, 0, 0
+            walked = {}               # logical tile -> the memory tiles its MFMAs consumed
             labels = {l[:-1]: i for i, l in enumerate(L) if l.endswith(":")}
             sval = lambda tok: sg[tok.strip("%[]")] if tok.startswith("%[") else int(tok, 0)
             while pc < len(L):
@@ -272,12 +276,14 @@ def test_generated_fp8_k128_loop_is_current_and_consumes_the_right_tiles():
                     i, j = blk >> 3, blk & 7
                     fb_, fa_ = int(re.match(r"v\[(\d+):", args[1]).group(1)), int(re.match(r"v\[(\d+):", args[2]).group(1))
                     t = len(mf_seen) // 64
-                    want_t = min(t, KT - 1)
-                    assert reg[fa_] == {0: (want_t, "a", i), 1: (want_t, "a", i)}, (KT, t, i, j, reg[fa_])
-                    assert reg[fb_] == {0: (want_t, "b", j), 1: (want_t, "b", j)}, (KT, t, i, j, reg[fb_])
+                    want_t = mem(t)
+                    assert reg[fa_] == {0: (want_t, "a", i), 1: (want_t, "a", i)}, (KT, stg, t, i, j, reg[fa_])
+                    assert reg[fb_] == {0: (want_t, "b", j), 1: (want_t, "b", j)}, (KT, stg, t, i, j, reg[fb_])
+                    walked.setdefault(t, set()).update(v[0] for r in (fa_, fb_) for v in reg[r].values())
                     if mx:
                         sb_, sa_ = int(args[4][1:]), int(args[5].split()[0][1:])
-                        assert scale_reg[sa_ & ~1] == want_t and scale_reg[sb_ & ~1] == want_t
+                        assert scale_reg[sa_ & ~1] == want_t and scale_reg[sb_ & ~1] == want_t, (KT, stg, t, i, j)
+                        walked[t].update((scale_reg[sa_ & ~1], scale_reg[sb_ & ~1]))
                         assert (sa_ & 1) == (i >> 2) and (sb_ & 3) == 2 + (j >> 2)
                         sel = re.search(r"op_sel:\[(\d),(\d),0\] op_sel_hi:\[(\d),(\d),0\]", ins)
                         assert int(sel.group(1)) + 2 * int(sel.group(3)) == (j & 3) and int(sel.group(2)) + 2 * int(sel.group(4)) == (i & 3)
@@ -294,6 +300,9 @@ def test_generated_fp8_k128_loop_is_current_and_consumes_the_right_tiles():
             for t in range(KT):
                 assert sorted(mf_seen[64 * t:64 * t + 64]) == [(i, j) for i in range(8) for j in range(8)]
             assert not pending_dma and not lds_q
+            # one memory tile per logical tile, and over the walk every memory tile exactly once
+            assert all(len(v) == 1 for v in walked.values()), (KT, stg, walked)
+            assert sorted(next(iter(walked[t])) for t in range(KT)) == list(range(KT)), (KT, stg, walked)
         # stream hygiene, as for the fp16 loops
         for a, b in zip(L, L[1:]):
             assert not (a.startswith("s_add_u32 m0") and b.startswith("buffer_load"))
