@@ -152,6 +152,9 @@ const char* lc_build_info(int* is_diag);
  *                  cached per-stream workspace (a few MiB, never freed); while a stream is being captured the unsplit kernel runs
  *                  Small grids the rule leaves unsplit (<= half a GPU of 256-row blocks, N <= 2048) run the 4-wave lock-step kernel, whose
  *                  128-row workgroups fill twice the CUs (+ 9 ... 12 %)
+ *   "attn_decode_split" KV ranges per (batch, K / V head) of lc_attn_decode_f16: 0 = auto (the smallest S that gives every CU a workgroup, at least 4
+ *                  tiles of 64 cache positions of Ncap per range, at most 64), 1 .. 64 = exactly that many (ranges may be empty: the small test
+ *                  shapes reach the split path that way); the name call reports it as " xS"
  *   "attn_bigd_map" block -> query block map of the D = 1024 / D = 512 kernels: 1 = every XCD owns consecutive query blocks of a head (its 32
  *                  CUs share one pass over the head's K / V: the fewest fabric bytes), 2 = round-robin over the XCDs (every XCD streams every
  *                  head: ~2 x the fabric bytes, but the 8 XCDs walk the same heads out of the Infinity Cache); 0 = auto: 2 for D = 1024
@@ -315,6 +318,36 @@ int lc_attn_fwd_f16_ex(const void* Q, const void* K, const void* V, void* O, int
 int lc_attn_fwd_f16_gqa(const void* Q, const void* K, const void* V, void* O, int B, int H, int Hkv, int N, int D,
                         int flags, void* stream);
 int lc_attn_kernel_name_gqa(int BH, int G, int N, int D, int flags, char* buf, int buflen);
+
+/* EXTENSION: attention of Nq new query tokens per sequence over a KV cache (decode; attn_decode.hip).
+ * Q, O: [B,H,Nq,D] fp16.  K, V: [B,Hkv,Ncap,D] fp16 — the cache, Ncap = its capacity in tokens (any value >= 1).
+ * kv_len: DEVICE int32[B], number of valid cache positions of each batch entry (the Nq new tokens already appended), or NULL = Ncap for all.
+ * Read by the kernel, never by the host: a captured graph may be replayed after the array was changed in place.  Values are clamped to
+ * [0, Ncap] in the kernel.
+ * G = H / Hkv; query head h reads K / V head h / G (the convention of lc_attn_fwd_f16_gqa).
+ * Without LC_ATTN_CAUSAL every query sees keys 0 .. L_b - 1.  With it, query i sees keys j <= L_b - Nq + i (bottom-right aligned: the last
+ * query sees the whole cache; the flash-attn kv-cache convention).  A row with no visible key (L_b == 0, or causal with L_b - Nq + i < 0)
+ * gets O = 0.  The result never depends on what the cache holds at positions >= L_b (NaN and Inf included).
+ * workspace: NULL, or a caller-owned device buffer of at least lc_attn_decode_workspace_bytes(...) bytes, 16-byte aligned, that makes the
+ * split-KV form legal while `stream` is being captured.  Without it the split-KV form keeps its partials in the stream's cached workspace
+ * (lc_workspace_bytes); a stream that is being captured then runs the one-launch form (S = 1).
+ * Restrictions: D in {64, 128} (else LC_ERR_HEADDIM); R = G x Nq query rows per K / V head, 1 <= R <= 64 (else LC_ERR_SHAPE: chunked
+ * prefill against a cache is out of scope); LC_ATTN_V_TRANSPOSED and unknown flag bits: LC_ERR_ARG; Hkv < 1, Hkv > H, H % Hkv != 0,
+ * non-positive dims, one head's Ncap x D x 2 >= 2 GiB, pointers not 16-byte aligned: LC_ERR_SHAPE.  Checks in lc_attn_fwd_f16_gqa's order
+ * (flags / null pointer, then shape, then head dim; then a non-NULL workspace that is too small or not 16-byte aligned: LC_ERR_ARG), all
+ * before any device work.
+ * Kernel: attn_decode_kernel<D, RT> (RT = 1 / 2 / 4 row tiles of 16 hold the R rows), one workgroup per (batch, K / V head, KV range s of S);
+ * S > 1: + attn_decode_combine_kernel<D> over fp32 partials.  S is chosen on the host from (B x Hkv, ceil(Ncap / 64), the CU count,
+ * "attn_decode_split"), never from kv_len; each batch entry's ranges are cut in the kernel from its own L_b.
+ * Reproducibility: the bits of one (batch, K / V head) depend on its Q, K, V, L_b, Nq, flags and S only — not on B, on the other batch
+ * entries' lengths or on the grid position (compare the batch-variance note of lc_attn_fwd_f16: here only S depends on B, through the rule).
+ * lc_attn_decode_workspace_bytes: what the current plan of that shape needs (0 for S = 1, and for a shape the call refuses).
+ * lc_attn_decode_kernel_name never launches: the kernel's demangled name, with S > 1 followed by " xS" (the split-K HGEMM convention). */
+int lc_attn_decode_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len,
+                       int B, int H, int Hkv, int Nq, int Ncap, int D, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_decode_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D);
+int lc_attn_decode_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, char* buf, int buflen);
 
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */

@@ -52,6 +52,9 @@ SYMBOLS = {
     "lc_attn_fwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "lc_attn_fwd_f16_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_fwd_f16_gqa": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "lc_attn_decode_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_decode_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "lc_attn_decode_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -389,6 +392,53 @@ def attn_fwd_gqa(q, k, v, o, v_transposed=False, causal=False):
     flags = (ATTN_CAUSAL if causal else 0) | (ATTN_V_TRANSPOSED if v_transposed else 0)
     check(load().lc_attn_fwd_f16_gqa(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, Hkv, N, D, flags, _stream()), "lc_attn_fwd_f16_gqa")
     return o
+
+
+def _attn_dims_decode(q, k, v, o, kv_len=None):
+    """q, o [B,H,Nq,D]; k, v [B,Hkv,Ncap,D] (the cache); kv_len None or int32 [B]; H % Hkv == 0.  Returns B, H, Hkv, Nq, Ncap, D."""
+    if q.dim() != 4 or k.dim() != 4:
+        _shape_err("4-D [B,H,Nq,D] / [B,Hkv,Ncap,D] tensors expected")
+    B, H, Nq, D = q.shape
+    Hkv, Ncap = k.shape[1], k.shape[2]
+    if tuple(k.shape) != (B, Hkv, Ncap, D) or tuple(v.shape) != (B, Hkv, Ncap, D) or tuple(o.shape) != (B, H, Nq, D):
+        _shape_err(f"q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} o {tuple(o.shape)}")
+    if Hkv < 1 or Hkv > H or H % Hkv != 0:
+        _shape_err(f"{H} query heads on {Hkv} K/V heads")
+    if kv_len is not None and tuple(kv_len.shape) != (B,):
+        _shape_err(f"kv_len {tuple(kv_len.shape)} for batch {B}")
+    return B, H, Hkv, Nq, Ncap, D
+
+
+def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None):
+    """Decode attention over a KV cache (lc_attn_decode_f16): q, o [B,H,Nq,D] fp16; k, v [B,Hkv,Ncap,D] fp16; kv_len None (= Ncap) or a
+    DEVICE int32 [B] tensor of valid cache lengths, read by the kernel; causal: query i sees keys j <= kv_len[b] - Nq + i.  workspace: None or
+    a device tensor of at least attn_decode_workspace_bytes(...) bytes (makes the split-KV form legal under graph capture)."""
+    import torch
+    _need_gpu(q, k, v, o)
+    assert q.dtype == k.dtype == v.dtype == o.dtype == torch.half
+    B, H, Hkv, Nq, Ncap, D = _attn_dims_decode(q, k, v, o, kv_len)
+    if kv_len is not None:
+        _need_gpu(kv_len)
+        assert kv_len.dtype == torch.int32
+    ws, ws_bytes = 0, 0
+    if workspace is not None:
+        _need_gpu(workspace)
+        ws, ws_bytes = _ptr(workspace), workspace.numel() * workspace.element_size()
+    check(load().lc_attn_decode_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, B, H, Hkv, Nq, Ncap, D,
+                                    ATTN_CAUSAL if causal else 0, ws or None, ws_bytes, _stream()), "lc_attn_decode_f16")
+    return o
+
+
+def attn_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, D) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs (0: one launch, no workspace)."""
+    return int(load().lc_attn_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, D))
+
+
+def attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False) -> str:
+    """The kernel attn_decode runs for this shape under the current knobs: "attn_decode_kernel<D,RT>", + " xS" with S > 1 KV ranges."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, ATTN_CAUSAL if causal else 0, buf, 128), "lc_attn_decode_kernel_name")
+    return buf.value.decode()
 
 
 def attn_fwd_bf16(q, k, v, o):

@@ -72,6 +72,21 @@ int attn_name(int BH, int G, int N, int D, int flags, bool bf16, int bad_n, char
   return LC_OK;
 }
 
+// The checks shared by lc_attn_decode_f16 (ptrs: its Q, K, V, O) and its two query calls (ptrs = nullptr): shape, then head dim, in the order of
+// check_attn_args; then the plan.  (Flags and null pointers are the callers' business: they come first.)
+int decode_plan(const void* const* ptrs, int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, DecodePlan* p) {
+  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
+  if (B <= 0 || Nq <= 0 || Ncap <= 0 || D <= 0) return LC_ERR_SHAPE;
+  if ((long)(H / Hkv) * Nq > 64) return LC_ERR_SHAPE;   // R = G x Nq query rows per K / V head: four row tiles of 16 (no chunked prefill against a cache)
+  if (!attn_span_fits(Ncap, D)) return LC_ERR_SHAPE;
+  if ((size_t)B * Hkv * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x Hkv x S workgroups, S <= 64
+  if (ptrs)
+    for (int i = 0; i < 4; ++i)
+      if (!aligned16(ptrs[i])) return LC_ERR_SHAPE;
+  if (D != 64 && D != 128) return LC_ERR_HEADDIM;
+  return plan_attn_decode(read_knobs(), B, H, Hkv, Nq, Ncap, D, (flags & LC_ATTN_CAUSAL) != 0, p);
+}
+
 // warmup + iters calls of `launch` (returns a status) between two events (lc_hgemm_time, lc_attn_time): ms per timed call
 template <typename Launch>
 int time_launches(int warmup, int iters, void* stream, float* ms_per_launch, Launch launch) {
@@ -294,6 +309,33 @@ int lc_attn_fwd_f16_gqa(const void* Q, const void* K, const void* V, void* O, in
   if (flags & ~kAttnFlags) return LC_ERR_ARG;
   if (int rc = check_attn_args(Q, K, V, O, B, H, Hkv, N, D, 1)) return rc;
   return attn_fwd(Q, K, V, O, AttnCall{(long)B * H, H / Hkv, N, D, (flags & LC_ATTN_V_TRANSPOSED) != 0, false, (flags & LC_ATTN_CAUSAL) != 0}, stream);
+}
+
+int lc_attn_decode_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len, int B, int H, int Hkv, int Nq, int Ncap, int D,
+                       int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
+  if (!Q || !K || !V || !O) return LC_ERR_ARG;
+  const void* ptrs[4] = {Q, K, V, O};
+  DecodePlan p;
+  if (int rc = decode_plan(ptrs, B, H, Hkv, Nq, Ncap, D, flags, &p)) return rc;
+  if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_decode(p, DecodePtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V),
+                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream)}, workspace);
+}
+
+size_t lc_attn_decode_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D) {
+  DecodePlan p;
+  return decode_plan(nullptr, B, H, Hkv, Nq, Ncap, D, 0, &p) == LC_OK ? decode_workspace_bytes(p) : 0;
+}
+
+int lc_attn_decode_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, char* buf, int buflen) {
+  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  DecodePlan p;
+  if (int rc = decode_plan(nullptr, B, H, Hkv, Nq, Ncap, D, flags, &p)) return rc;
+  format_attn_decode(p, buf, buflen);
+  return LC_OK;
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -11,6 +11,7 @@
 LC_KNOB_SNAP(attn_nw, 0, ok_attn_nw, false)               // attention kernel for D <= 128: 0 = auto, 513 / 515 / 517 / 514 / 8 / 4 / 2 (choose_attn_nw, lc_abi.h)
 LC_KNOB_SNAP(attn_walk, 0, ok_03, false)                  // block walk of the merged-phase kernel under attn_nw = 0: 0 = auto by N, 1 / 2 / 3 = WALK 0 / 1 / 2
 LC_KNOB_SNAP(attn_split, 0, ok_split, false)              // split-KV of the merged-phase kernel on grids that do not fill the GPU: 0 = auto (attn_split_auto), 1 = off, 2 / 4 / 8 / 16 = that many KV ranges per query block
+LC_KNOB_SNAP(attn_decode_split, 0, ok_064, false)          // KV ranges per (batch, K / V head) of the decode kernel (attn_decode.hip): 0 = auto (plan_attn_decode), 1 .. 64 = exactly that many (empty ranges are legal)
 LC_KNOB_SNAP(attn_causal_order, 0, ok_02, false)          // grid order of the causal merged-phase kernel: 0 = auto (choose_attn_causal), 1 = longest query block first, 2 = head-major (xcd_remap; same bits)
 LC_KNOB(attn_bigd_map, 0, ok_02, false)                   // block -> query block map of attn_bigd4 / attn_bigd6: 0 = auto (D = 1024: round-robin over the XCDs, D = 512: XCD-contiguous), 1 = XCD-contiguous, 2 = round-robin (same bits; profiles/r5f_bigd_map.log)
 LC_KNOB(attn_bigd_stagger, 0, ok_02, false)               // attn_bigd4 (D = 1024): the KV walk of the workgroups on XCD x starts x eighths of the sequence in: 0 = auto (with the round-robin block map), 1 = off, 2 = on (results agree to rounding)

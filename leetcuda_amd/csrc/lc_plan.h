@@ -76,7 +76,8 @@ struct TailSplit { int nblk, R, tmw, ns; };   // nblk = -1: one launch of all T 
 //   - the workspace lease fails (the same fallbacks; LC_HGEMM_KPAD's padded problem holds the lease, so its plan runs workspace-free, unforked)
 //   - the fork's side stream cannot be made: both launches on the caller's stream
 //   (attention: the same for split-KV; and a persistent w4u walk with no more blocks than CUs runs walk 0, the dynamic queue on a CU count
-//   that is not a multiple of 8 or under capture the static walk — tu_attn_w4u_impl.h)
+//   that is not a multiple of 8 or under capture the static walk — tu_attn_w4u_impl.h;
+//   decode attention, DecodePlan with S > 1 and no caller workspace: the stream is being captured, or the workspace lease fails: S = 1, one launch)
 enum class HFam { VALU, TILE256, MFMA128, MID, RAGGED, KPAD, EDGE, GENERIC };
 struct HgemmPlan {
   Knobs k;                  // the snapshot (launch: panel_tiles, LC_HGEMM_KPAD's plan of the padded problem)
@@ -123,5 +124,28 @@ struct AttnPlan {   // walk / nsplit: W4U; sched: W4I ("attn_w4i_sched"); nw: LO
 };
 int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p);
 void format_attn(const AttnPlan& p, char* buf, int buflen);
+
+// ONE decision per decode-attention call (lc_attn_decode_f16; attn_decode.hip): attn_decode_kernel<D, RT> on B x Hkv x S workgroups, S > 1 followed by
+// attn_decode_combine_kernel<D>.  RT = row tiles of 16 that hold the R = (H / Hkv) x Nq query rows of a K / V head.  S, the KV ranges per (batch, K / V
+// head), is decided from (B x Hkv, ceil(Ncap / 64), rule_cus, "attn_decode_split") and NEVER from kv_len, which only the kernel reads: the smallest S
+// that gives every CU a workgroup, with at least 4 tiles of Ncap per range, at most 64; the knob forces 1 .. 64 (ranges may then be empty).
+struct DecodePlan {
+  int B, H, Hkv, Nq, Ncap, D;
+  bool causal;
+  int RT, S;
+};
+int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p);   // checked arguments
+void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel)
+// bytes of fp32 partials a plan with S > 1 needs: S x B H Nq rows x (D + 1) floats; 0 for S = 1
+inline size_t decode_workspace_bytes(const DecodePlan& p) {
+  return p.S > 1 ? (size_t)p.S * ((size_t)p.B * p.H * p.Nq) * (size_t)(p.D + 1) * sizeof(float) : 0;
+}
+struct DecodePtrs {
+  const half_t *Q, *K, *V;
+  half_t* O;
+  const int* kv_len;   // device int32[B] or nullptr
+  hipStream_t st;
+};
+int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace);   // tu_attn_decode.hip
 
 }  // namespace lc

@@ -30,6 +30,7 @@ bool ok_02(int v) { return v >= 0 && v <= 2; }
 bool ok_03(int v) { return v >= 0 && v <= 3; }
 bool ok_04(int v) { return v >= 0 && v <= 4; }
 bool ok_08(int v) { return v >= 0 && v <= 8; }
+bool ok_064(int v) { return v >= 0 && v <= 64; }
 bool ok_rule_cus(int v) { return v == 0 || (v >= 64 && v <= 1024); }
 bool ok_mid_ns(int v) { return v == 0 || v == 2 || v == 3; }
 bool ok_ragged_tile(int v) { return v == 0 || v == 12 || v == 22 || v == 23 || v == 32 || v == 33; }
@@ -683,6 +684,27 @@ int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p) {
 }
 
 // The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).
+// Decode attention (attn_decode.hip).  The auto rule: a workgroup streams its range at a rate that does not depend on the grid, so the call is as
+// fast as its longest range once every CU has a workgroup — the smallest S with B Hkv S >= CUs — and a range shorter than 4 tiles (one per wave) leaves
+// waves without work while the combine still reads S partials.
+int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p) {
+  const int R = (H / Hkv) * Nq;
+  *p = DecodePlan{B, H, Hkv, Nq, Ncap, D, causal, R <= 16 ? 1 : R <= 32 ? 2 : 4, 1};
+  if (k.attn_decode_split > 0) {
+    p->S = k.attn_decode_split;
+    return LC_OK;
+  }
+  const long groups = (long)B * Hkv, tiles = ((long)Ncap + 63) / 64;
+  long S = (rule_cus(k) + groups - 1) / groups;
+  S = std::min(S, tiles / 4);
+  p->S = (int)std::max(1L, std::min(S, 64L));
+  return LC_OK;
+}
+void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
+  if (p.S > 1) snprintf(buf, buflen, "attn_decode_kernel<%d,%d> x%d", p.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)
+  else snprintf(buf, buflen, "attn_decode_kernel<%d,%d>", p.D, p.RT);
+}
+
 void format_attn(const AttnPlan& p, char* buf, int buflen) {
   const int D = p.call.D;
   const bool v_transposed = p.call.vt;

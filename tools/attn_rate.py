@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
           causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
           instead of this library (context only); kvh = K: grouped-query attention, K / V tensors with K heads through lc_attn_fwd_f16_gqa
           (FLOPs counted as for the H query heads); kvh = K with expand: what a caller without that entry does — repeat_interleave K and V
           to H heads in every step, then the MHA call; kvh = K with expanded: the MHA call on K / V expanded once, outside the timing
           (the same values through the MHA kernel: the reference for the GQA kernel's time); knobs = lc_tune_set keys attn_nw / attn_walk / attn_split / attn_d512 /
           attn_w4i_sched / attn_causal_order)
+   q = Nq: DECODE attention through lc_attn_decode_f16 — Nq query tokens per sequence against a KV cache of capacity N with kvh = K heads
+          (default K = H); len = L: every batch entry's kv_len (default N); dsplit = S: "attn_decode_split"; causal: the bottom-right aligned
+          mask; with sdpa: scaled_dot_product_attention on k[:, :, :L] / v[:, :, :L] (enable_gqa where this torch has it, else on K / V
+          expanded once outside the timing; non-causal only: torch's is_causal is top-left aligned).  Decode rows report microseconds per
+          call (median, best, worst over the rounds) and K / V GB/s = 2 B K L D 2 bytes / median time
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
 cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
 causal: half of that, the flash-attn convention) and the median time per call."""
@@ -34,7 +39,7 @@ if os.environ.get("LC_AB_LIB"):    # A/B of two builds on one box: point the cty
     capi.LIB_PATH = Path(os.environ["LC_AB_LIB"]).resolve()
 capi.load()
 KNOBS = {"bigd_stagger": "attn_bigd_stagger", "bigd_map": "attn_bigd_map", "nw": "attn_nw", "walk": "attn_walk", "d512": "attn_d512", "d1024": "attn_d1024", "sched": "attn_w4i_sched", "split": "attn_split",
-         "order": "attn_causal_order"}
+         "order": "attn_causal_order", "dsplit": "attn_decode_split"}
 cache = {}
 
 
@@ -53,9 +58,71 @@ def tensors(B, H, N, D, bf16, zero, kvh=0):
     return cache[key]
 
 
+def timed(step):
+    """ms per call of `step` over >= secs seconds of back-to-back calls"""
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    n = max(5, int(secs / (e0.elapsed_time(e1) / 5 * 1e-3)))
+    e0.record()
+    for _ in range(n):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def opt_int(opts, key, default):
+    return next((int(o.split("=")[1]) for o in opts if o.startswith(key + "=")), default)
+
+
+def run_decode(spec, shape, opts):
+    """(name, K / V GB/s, ms per call) of one decode call"""
+    B, H, N, D = shape
+    nq, kvh, L, causal = opt_int(opts, "q", 1), opt_int(opts, "kvh", H), opt_int(opts, "len", N), "causal" in opts
+    key = ("decode", B, H, N, D, kvh, nq)
+    if key not in cache:
+        cache.clear()
+        torch.manual_seed(0)
+        mk = lambda *s: torch.randn(*s, device="cuda").half()  # noqa: E731
+        cache[key] = (mk(B, H, nq, D), mk(B, kvh, N, D), mk(B, kvh, N, D), torch.zeros(B, H, nq, D, device="cuda", dtype=torch.half))
+    q, k, v, o = cache[key]
+    lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
+    split = opt_int(opts, "dsplit", 0)
+    capi.tune("attn_decode_split", split)
+    try:
+        if "sdpa" in opts:
+            if causal:
+                raise SystemExit(f"{spec}: the sdpa arm of a decode spec is non-causal")
+            ks, vs = k[:, :, :L], v[:, :, :L]
+            try:
+                torch.nn.functional.scaled_dot_product_attention(q, ks, vs, enable_gqa=True)
+                name = "torch sdpa enable_gqa"
+                step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ks, vs, enable_gqa=True)  # noqa: E731
+            except TypeError:
+                ke, ve = ks.repeat_interleave(H // kvh, dim=1), vs.repeat_interleave(H // kvh, dim=1)
+                name = "torch sdpa (K / V expanded)"
+                step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ke, ve)  # noqa: E731
+        else:
+            name = capi.attn_decode_kernel_name(B, H, kvh, nq, N, D, causal=causal)
+            step = lambda: capi.attn_decode(q, k, v, o, lens, causal=causal)  # noqa: E731
+        ms = timed(step)
+    finally:
+        capi.tune("attn_decode_split", 0)
+    return name, 2.0 * B * kvh * L * D * 2 / ms * 1e-6, ms
+
+
 def run(spec):
     shape, *opts = spec.split(":")
     B, H, N, D = (int(x) for x in shape.split(","))
+    if any(o.startswith("q=") for o in opts):
+        return run_decode(spec, (B, H, N, D), opts)
     bf16, zero, vt, causal, sdpa = "bf16" in opts, "zero" in opts, "vt" in opts, "causal" in opts, "sdpa" in opts
     kvh = next((int(o.split("=")[1]) for o in opts if o.startswith("kvh=")), 0)
     expand = "expand" in opts
@@ -86,22 +153,7 @@ def run(spec):
         else:
             name = capi.attn_kernel_name(N, D, vt, bf16, bh=B * H, causal=causal)
             step = (lambda: capi.attn_fwd_bf16(q, k, v, o)) if bf16 else (lambda: capi.attn_fwd(q, k, v, o, v_transposed=vt, causal=causal))
-        for _ in range(3):
-            step()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        n = max(5, int(secs / (e0.elapsed_time(e1) / 5 * 1e-3)))
-        e0.record()
-        for _ in range(n):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / n
+        ms = timed(step)
     finally:
         for kk in knobs:
             capi.tune(kk, capi.tune_items()[kk][1])      # back to the library default
@@ -120,4 +172,8 @@ if any("causal" in s.split(":") for s in args):
     print("(causal TFLOP/s count half of 4 B H N^2 D: the flash-attn convention)", flush=True)
 for s in args:
     v, t = sorted(res[s]), sorted(times[s])
+    if any(o.startswith("q=") for o in s.split(":")):     # decode: res holds K / V GB/s
+        print(f"RATE {s:40s} {names[s]:32s} median {t[len(t) // 2] * 1e3:8.1f} us  best {t[0] * 1e3:8.1f}  worst {t[-1] * 1e3:8.1f}  "
+              f"K/V {v[len(v) // 2]:7.0f} GB/s", flush=True)
+        continue
     print(f"RATE {s:34s} {names[s]:44s} median {v[len(v) // 2]:7.1f}  best {v[-1]:7.1f}  worst {v[0]:7.1f} TFLOP/s  {t[len(t) // 2] * 1e3:9.1f} us", flush=True)
