@@ -349,6 +349,42 @@ int lc_attn_decode_f16(const void* Q, const void* K, const void* V, void* O, con
 size_t lc_attn_decode_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D);
 int lc_attn_decode_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, char* buf, int buflen);
 
+/* EXTENSION: lc_attn_decode_f16 over a PAGED KV cache addressed through a block table (attn_decode_paged.hip) — what a
+ * serving loop that keeps its cache in fixed-size pages calls, with no gather in front.
+ * Q, O: [B,H,Nq,D] fp16, as in lc_attn_decode_f16.
+ * Kpool, Vpool: [num_pages,Hkv,page_size,D] fp16, dense: one (page, K / V head) is one contiguous run of page_size x D halves.  (A contiguous
+ * [B,Hkv,Ncap,D] cache with Ncap a power of two IS a pool with num_pages = B, page_size = Ncap and the table [[0],[1],...]: no copy.)
+ * block_table: DEVICE int32[B,max_pages], dense; entry [b][p] is the pool page that holds logical keys p page_size .. (p + 1) page_size - 1 of
+ * batch entry b.  One table serves K and V and every K / V head.
+ * kv_len: DEVICE int32[B], required.  The logical capacity is Ncap = max_pages x page_size; kv_len is clamped to [0, Ncap] in the kernel.
+ * Only the kernel reads block_table and kv_len, never the host: a captured graph may be replayed after either was rewritten in place.
+ * Flags, the bottom-right causal convention, "a row without a visible key gets O = 0", R = (H / Hkv) x Nq <= 64 and D in {64, 128} are those of
+ * lc_attn_decode_f16.
+ * Never read: table entries at positions >= ceil(L_b / page_size), and pool rows that hold logical positions >= L_b; the result depends on
+ * neither (NaN and Inf included).
+ * MEMORY SAFETY: the host cannot check the table.  The kernel clamps every page id it reads to [0, num_pages - 1] before use — a garbage entry
+ * reads a wrong page, never an address outside the pool — and that clamp is the whole of the memory-safety story: num_pages must be the true
+ * page count of BOTH pools.
+ * page_size: a power of two >= 16 (else LC_ERR_SHAPE); one (page, head) run below 2 GiB.  The pool as a whole may exceed 4 GiB (64-bit page
+ * base, 32-bit offset inside a run).
+ * Checks, in lc_attn_decode_f16's order and all before any device work: unknown flags or a NULL Q / Kpool / Vpool / O / block_table / kv_len:
+ * LC_ERR_ARG; then LC_ERR_SHAPE for H % Hkv, non-positive B / Nq / num_pages / max_pages / D, a bad page_size, R > 64, max_pages x page_size x
+ * D x 2 >= 2 GiB, the grid bound, Q / O / pools not 16-byte aligned; then D not in {64, 128}: LC_ERR_HEADDIM; then a non-NULL workspace that is
+ * too small or not 16-byte aligned: LC_ERR_ARG.
+ * Kernel: attn_decode_paged_kernel<D, RT>, S > 1: + attn_decode_combine_kernel<D>; S, the workspace bytes and the capture / failed-lease
+ * fallback to S = 1 are those of lc_attn_decode_f16 at Ncap = max_pages x page_size (same rule, same "attn_decode_split", same CU count).
+ * For the same Q, logical cache contents, kv_len, flags and S the output is BIT-IDENTICAL to lc_attn_decode_f16 on the gathered contiguous
+ * cache of that Ncap: paging changes where a row comes from and nothing about the arithmetic.
+ * The name call never launches: "attn_decode_paged_kernel<D,RT>", with S > 1 followed by " xS". */
+int lc_attn_decode_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                             const int* block_table, const int* kv_len,
+                             int B, int H, int Hkv, int Nq,
+                             int num_pages, int page_size, int max_pages, int D, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_decode_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D);
+int lc_attn_decode_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                     int flags, char* buf, int buflen);
+
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

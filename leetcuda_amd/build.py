@@ -26,6 +26,12 @@ LIB_NAME = "libleetcuda_amd.so"
 ORACLE_NAME = "liblc_oracle.so"
 
 
+# Translation units whose audit report is a file of its own next to isa_audit.json (same rules, same refusal to link on a violation).
+# isa_audit.json is read by name patterns and entry counts: "attn_decode" is counted as the eight kernels of tu_attn_decode.hip, and the
+# paged kernels' names (attn_decode_paged_kernel<D, RT>) contain that string.
+AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json"}
+
+
 def _newer(target: Path, sources) -> bool:
     """True when `target` exists and is newer than every source."""
     if not target.exists():
@@ -194,14 +200,19 @@ def build_abi(force: bool = False, audit: bool = True) -> Path:
                 _mark("unit:" + obj.stem, _unit_digest(objdir / (obj.stem + ".d"), flags))
     if audit:
         from leetcuda_amd import isa_audit
-        reps, bad = isa_audit.audit_files([objdir / (u.stem + ".s") for u in units])
+        reps, bad = [], []
+        for report, stems in [("isa_audit.json", [u.stem for u in units if u.stem not in AUDIT_OWN_REPORT]),
+                              *((name, [stem]) for stem, name in AUDIT_OWN_REPORT.items())]:
+            part, part_bad = isa_audit.audit_files([objdir / (stem + ".s") for stem in stems])
+            reps += part
+            bad += part_bad
+            (objdir / report).write_text(json.dumps(
+                [{"kernel": r.name, "vgpr": r.vgpr_count, "agpr": r.agpr_count, "scratch": r.scratch,
+                  "asm_loads": r.asm_loads, "compiler_accvgpr": r.compiler_accvgpr, "violations": r.violations}
+                 for r in part], indent=1))
         for r in reps:
             print(f"[audit] {r.name}: vgpr {r.vgpr_count} agpr {r.agpr_count} scratch {r.scratch} "
                   f"asm loads {r.asm_loads} compiler v_accvgpr {r.compiler_accvgpr}", flush=True)
-        (objdir / "isa_audit.json").write_text(json.dumps(
-            [{"kernel": r.name, "vgpr": r.vgpr_count, "agpr": r.agpr_count, "scratch": r.scratch,
-              "asm_loads": r.asm_loads, "compiler_accvgpr": r.compiler_accvgpr, "violations": r.violations}
-             for r in reps], indent=1))
         if bad:
             if out.exists():
                 out.unlink()     # never leave a library around whose hidden-state invariants do not hold

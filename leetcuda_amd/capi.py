@@ -55,6 +55,9 @@ SYMBOLS = {
     "lc_attn_decode_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_decode_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "lc_attn_decode_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_decode_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_decode_paged_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "lc_attn_decode_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -438,6 +441,56 @@ def attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False) -> str:
     """The kernel attn_decode runs for this shape under the current knobs: "attn_decode_kernel<D,RT>", + " xS" with S > 1 KV ranges."""
     buf = C.create_string_buffer(128)
     check(load().lc_attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, ATTN_CAUSAL if causal else 0, buf, 128), "lc_attn_decode_kernel_name")
+    return buf.value.decode()
+
+
+def _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len):
+    """q, o [B,H,Nq,D]; k_pool, v_pool [num_pages,Hkv,page_size,D]; block_table int32 [B,max_pages]; kv_len int32 [B]; H % Hkv == 0.
+    Returns B, H, Hkv, Nq, num_pages, page_size, max_pages, D."""
+    if q.dim() != 4 or k_pool.dim() != 4:
+        _shape_err("4-D [B,H,Nq,D] / [num_pages,Hkv,page_size,D] tensors expected")
+    B, H, Nq, D = q.shape
+    P, Hkv, ps = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
+    if tuple(k_pool.shape) != (P, Hkv, ps, D) or tuple(v_pool.shape) != (P, Hkv, ps, D) or tuple(o.shape) != (B, H, Nq, D):
+        _shape_err(f"q {tuple(q.shape)} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)} o {tuple(o.shape)}")
+    if Hkv < 1 or Hkv > H or H % Hkv != 0:
+        _shape_err(f"{H} query heads on {Hkv} K/V heads")
+    if block_table is None or block_table.dim() != 2 or block_table.shape[0] != B:
+        _shape_err(f"block_table {None if block_table is None else tuple(block_table.shape)} for batch {B}")
+    if kv_len is None or tuple(kv_len.shape) != (B,):
+        _shape_err(f"kv_len {None if kv_len is None else tuple(kv_len.shape)} for batch {B}")
+    return B, H, Hkv, Nq, P, ps, block_table.shape[1], D
+
+
+def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None):
+    """Decode attention over a paged KV cache (lc_attn_decode_paged_f16): q, o [B,H,Nq,D] fp16; k_pool, v_pool [num_pages,Hkv,page_size,D]
+    fp16, page_size a power of two >= 16; block_table a DEVICE int32 [B,max_pages] tensor of pool page ids; kv_len a DEVICE int32 [B] tensor;
+    both are read by the kernel only (page ids are clamped to the pool there).  causal, workspace: as attn_decode."""
+    import torch
+    _need_gpu(q, k_pool, v_pool, o)
+    assert q.dtype == k_pool.dtype == v_pool.dtype == o.dtype == torch.half
+    B, H, Hkv, Nq, P, ps, mp, D = _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len)
+    _need_gpu(block_table, kv_len)
+    assert block_table.dtype == torch.int32 and kv_len.dtype == torch.int32
+    ws, ws_bytes = 0, 0
+    if workspace is not None:
+        _need_gpu(workspace)
+        ws, ws_bytes = _ptr(workspace), workspace.numel() * workspace.element_size()
+    check(load().lc_attn_decode_paged_f16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), B, H, Hkv, Nq, P, ps, mp,
+                                          D, ATTN_CAUSAL if causal else 0, ws or None, ws_bytes, _stream()), "lc_attn_decode_paged_f16")
+    return o
+
+
+def attn_decode_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs: those of attn_decode at Ncap = max_pages x page_size."""
+    return int(load().lc_attn_decode_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D))
+
+
+def attn_decode_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
+    """The kernel attn_decode_paged runs for this shape under the current knobs: "attn_decode_paged_kernel<D,RT>", + " xS" with S > 1."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_decode_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, ATTN_CAUSAL if causal else 0, buf, 128),
+          "lc_attn_decode_paged_kernel_name")
     return buf.value.decode()
 
 

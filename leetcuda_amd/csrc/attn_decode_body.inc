@@ -1,0 +1,300 @@
+// attn_decode_body.inc — the body of attn_decode_kernel<D, RT> (attn_decode.hip) and of attn_decode_paged_kernel<D, RT> (attn_decode_paged.hip),
+// included textually by both: the two kernels differ in how a key row becomes an address and in nothing else.  The including kernel has the
+// template parameters D, RT, the parameters Q, K, V, O, kv_len, part_o, part_lse, H, Hkv, Nq, Ncap, causal, S, sl2, total_rows, a
+// `constexpr bool PAGED` and a `const DecodePaging pg` (PAGED = false: unused) in scope.  See attn_decode.hip for the design.
+  using L = DecodeLds<D, RT>;
+  constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
+  constexpr int DB = D / 16;    // 16-wide blocks of d
+  constexpr int CH = D / 8;     // 16-byte chunks per row
+  // keys per pipeline step: a wave walks its 64-key tiles in steps of 64 keys — of 32 where the accumulators of four row tiles at D = 128 leave
+  // no room for a whole tile's K and V in flight (hipcc spilled; the audit's rule R2)
+  constexpr int STEP = (D == 128 && RT == 4) ? 32 : 64;
+  constexpr int SPT = DEC_KVB / STEP;     // steps per tile
+  constexpr int NKB = STEP / 16;          // 16-key blocks of Sᵀ per step
+  constexpr int NPS = STEP / 32;          // 32-key k-steps of Oᵀ += Vᵀ Pᵀ per step
+  constexpr int VL = STEP * CH / 64;      // V chunks per lane and step
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+
+  const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
+  const int i16 = lane & 15, h = lane >> 4;
+  // (integer division runs on the vector ALU: readfirstlane tells hipcc that the quotients are wave-uniform — scalar addressing, a scalar tile loop)
+  const int bk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)S)), s_idx = (int)blockIdx.x - bk * S;
+  const int b = __builtin_amdgcn_readfirstlane(bk / Hkv), kvh = bk - b * Hkv;
+  const int G = __builtin_amdgcn_readfirstlane(H / Hkv), R = G * Nq;
+  int Lb = kv_len ? kv_len[b] : Ncap;
+  Lb = __builtin_amdgcn_readfirstlane(Lb);   // (a vector load of a uniform address: tell hipcc that the tile loop is wave-uniform)
+  Lb = Lb < 0 ? 0 : (Lb > Ncap ? Ncap : Lb);
+  const int T = (Lb + DEC_KVB - 1) / DEC_KVB;
+  // (T < 2^24 tiles — one head's cache is below 2 GiB — and S <= 64: the products fit 32 bits)
+  const int t0 = __builtin_amdgcn_readfirstlane((int)((unsigned)(s_idx * T) / (unsigned)S));
+  const int t1 = __builtin_amdgcn_readfirstlane((int)((unsigned)((s_idx + 1) * T) / (unsigned)S));
+
+  const long row0 = ((long)b * H + (long)kvh * G) * Nq;   // the R rows of this (batch, K / V head): one contiguous [R, D] matrix
+  const half_t* Qg = Q + row0 * D;
+  // (PAGED: K / V are the pools; the base of a load group is that of its page, below)
+  const half_t* Kg = PAGED ? K : K + ((long)b * Hkv + kvh) * (long)Ncap * D;
+  const half_t* Vg = PAGED ? V : V + ((long)b * Hkv + kvh) * (long)Ncap * D;
+
+  // ---- Q -> LDS (rows >= R: row R - 1)
+  for (int c = tid; c < 16 * RT * CH; c += 256) {
+    const int r = c / CH, ch = c % CH;
+    const int rs = r < R ? r : R - 1;
+    *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Qg + (long)rs * D + ch * 8);
+  }
+  __syncthreads();
+
+  // visible keys of this lane's query row in each row tile: keys j < lim
+  int lim[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    int r = 16 * rt + i16;
+    r = r < R ? r : R - 1;
+    int v = causal ? Lb - Nq + (r % Nq) + 1 : Lb;
+    lim[rt] = v < 0 ? 0 : v;
+  }
+
+  float m[RT], l[RT];
+  f32x4_t o[RT][DB];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    m[rt] = DEC_NEG_INF;
+    l[rt] = 0.f;
+#pragma unroll
+    for (int db = 0; db < DB; ++db) o[rt][db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+
+  char* vimg = lds + L::kVOff + w * L::kVBytes;
+  // transposed-read address of this lane inside a 32-key k-step: row 4 h + q (+ 16 for the second half), d = 16 db + 4 p
+  const int q4 = i16 >> 2, p4 = i16 & 3;
+  int tr_off[DB];
+#pragma unroll
+  for (int db = 0; db < DB; ++db) tr_off[db] = dec_v_off<D>(4 * h + q4, 2 * db + (p4 >> 1)) + 8 * (p4 & 1);
+
+  u32x4_t kf[NKB][KS], vf[VL];
+  const int last = Lb - 1;   // (>= 0 whenever a tile exists)
+  // step u of this wave: keys key0(u) ... key0(u) + STEP - 1 of tile t0 + w + 4 (u / SPT)
+  auto key0 = [&](int u) { return (t0 + w + DEC_WAVES * (u / SPT)) * DEC_KVB + (u % SPT) * STEP; };
+  // PAGED: the pool page of each 16-key block of a step.  A block's keys share a page (page_size % 16 == 0), and so do the 4 or 8 key rows of a
+  // V chunk group with their block; the clamp to `last` keeps that true (keys past it collapse onto one row, inside last's own block), and it
+  // keeps the table index below ceil(L_b / page_size).  Ids are clamped to the pool: a garbage entry reads a wrong page, never outside the pool.
+  // readfirstlane: table reads are scalar loads, page bases live in SGPRs (per-lane 64-bit addresses would not fit <128,4>'s register file)
+  int pid[PAGED ? NKB : 1];
+  auto page_ids = [&](int u) {
+    const int k0 = key0(u);
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+      int first = k0 + 16 * kb;
+      first = first < last ? first : last;
+      int id = __builtin_amdgcn_readfirstlane(pg.table[(long)b * pg.max_pages + (first >> pg.lps)]);
+      id = id < 0 ? 0 : id;
+      pid[kb] = id < pg.num_pages ? id : pg.num_pages - 1;
+    }
+  };
+  // byte base of (page id, this K / V head): 64-bit, scalar; the offset inside the run is 32-bit (one run is below 2 GiB: checked by the host)
+  auto page_base = [&](const half_t* pool, int id) {
+    return reinterpret_cast<const char*>(pool) + ((((long)id * Hkv + kvh) << pg.lps) * (D * 2));
+  };
+  const int pmask = PAGED ? (1 << pg.lps) - 1 : -1;
+  auto load_k = [&](int u) {
+    const int k0 = key0(u);
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+      int key = k0 + 16 * kb + i16;
+      key = key < last ? key : last;
+      if constexpr (PAGED) {
+        const char* base = page_base(Kg, pid[kb]);
+        const unsigned off = (unsigned)(key & pmask) * (D * 2) + h * (D / 2);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const u32x4_t*>(base + (off + 16 * s));
+      } else {
+        const unsigned off = (unsigned)key * (D * 2) + h * (D / 2);   // bytes inside the head: < 2 GiB (checked by the host), base in SGPRs
+#pragma unroll
+        for (int s = 0; s < KS; ++s) kf[kb][s] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(Kg) + (off + 16 * s));
+      }
+    }
+  };
+  auto load_v = [&](int u) {
+    const int k0 = key0(u);
+#pragma unroll
+    for (int n = 0; n < VL; ++n) {
+      const int c = n * 64 + lane;
+      int key = k0 + c / CH;
+      key = key < last ? key : last;
+      if constexpr (PAGED)   // (chunk group n: the 64 / CH key rows from k0 + n 64 / CH on, inside 16-key block n 4 / CH)
+        vf[n] = *reinterpret_cast<const u32x4_t*>(page_base(Vg, pid[n * 4 / CH]) + ((unsigned)(key & pmask) * (D * 2) + (c % CH) * 16));
+      else
+        vf[n] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(Vg) + ((unsigned)key * (D * 2) + (c % CH) * 16));
+    }
+  };
+  auto store_v = [&]() {
+#pragma unroll
+    for (int n = 0; n < VL; ++n) {
+      const int c = n * 64 + lane;
+      *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CH, c % CH)) = vf[n];
+    }
+  };
+
+  const int my_tiles = t1 - t0 - w > 0 ? (t1 - t0 - w + DEC_WAVES - 1) / DEC_WAVES : 0;
+  const int steps = my_tiles * SPT;
+  if (steps > 0) {
+    if constexpr (PAGED) page_ids(0);
+    load_k(0);
+    load_v(0);
+    if constexpr (PAGED) page_ids(1);   // (a step past the last one names the page of key L_b - 1: always a valid table position)
+    store_v();
+  }
+  for (int u = 0; u < steps; ++u) {
+    // ---- Sᵀ = K Qᵀ for this tile (the K registers are free behind it)
+    // and the online softmax (log2 domain) of each row tile right behind its scores: Sᵀ -> P in fp16, register for register the B operand of
+    // Oᵀ += Vᵀ Pᵀ (16 score registers per lane alive at a time, not 16 RT)
+    const int k0 = key0(u) + 4 * h;
+    half8_t pf[RT][NPS];
+    float alpha[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      half8_t qf[KS];
+#pragma unroll
+      for (int s = 0; s < KS; ++s)
+        qf[s] = *reinterpret_cast<const half8_t*>(lds + (16 * rt + i16) * L::kQStride + (h * (D / 4) + 8 * s) * 2);
+      f32x4_t st[NKB];
+#pragma unroll
+      for (int kb = 0; kb < NKB; ++kb) {
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) acc = mfma16(__builtin_bit_cast(half8_t, kf[kb][s]), qf[s], acc);
+        st[kb] = acc;
+      }
+      float mx = DEC_NEG_INF;
+#pragma unroll
+      for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float x = (k0 + 16 * kb + r < lim[rt]) ? st[kb][r] * sl2 : DEC_NEG_INF;   // select on the INDEX: the score may be anything
+          st[kb][r] = x;
+          mx = fmaxf(mx, x);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float mn = fmaxf(m[rt], mx);
+      const float mu = (mn == DEC_NEG_INF) ? 0.f : mn;   // no visible key yet: every exponent below is exp2(-inf) = 0
+      alpha[rt] = __builtin_amdgcn_exp2f(m[rt] - mu);
+      m[rt] = mn;
+      float ps = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(st[kb][r] - mu);
+          ps += p;
+          pf[rt][kb >> 1][4 * (kb & 1) + r] = (half_t)p;
+        }
+      l[rt] = l[rt] * alpha[rt] + ps;   // (this lane's keys of the step: the four lane groups of a row are summed once, behind the loop)
+    }
+    // ---- the next tile's K and V loads into the registers that are free now: a whole tile in flight under the rest of the arithmetic (the
+    // scheduling barrier keeps hipcc from hoisting them over the scores: that is what keeps the four-row-tile kernel inside the register file)
+    __builtin_amdgcn_sched_barrier(0);
+    const bool more = u + 1 < steps;
+    if (more) load_k(u + 1);
+    if (more) load_v(u + 1);
+    // PAGED: the table entries of step u + 2, read one iteration before the loads that need them: no K / V load waits for a table load
+    if constexpr (PAGED) page_ids(u + 2);
+    // ---- rescale O only when some row's maximum moved (a multiplication by exactly 1 otherwise: same bits).  A block of its own, so that the
+    // accumulators stay where the MFMAs below want them instead of travelling through the vector ALU on every tile
+    bool moved = false;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) moved |= alpha[rt] != 1.f;
+    if (__builtin_amdgcn_ballot_w64(moved) != 0) {
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int db = 0; db < DB; ++db) o[rt][db] *= alpha[rt];
+    }
+    // ---- Oᵀ += Vᵀ Pᵀ: the Vᵀ fragments of a 16-wide block of d out of the image serve every row tile
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+      half8_t va[NPS];
+#pragma unroll
+      for (int s = 0; s < NPS; ++s) va[s] = cat4(lds_tr16(vimg + (D * 2) * (32 * s) + tr_off[db]), lds_tr16(vimg + (D * 2) * (32 * s + 16) + tr_off[db]));
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int s = 0; s < NPS; ++s) o[rt][db] = mfma16(va[s], pf[rt][s], o[rt][db]);
+    }
+    if (more) store_v();   // (LDS operations of one wave execute in order: the transposed reads above are behind us)
+  }
+
+  // ---- merge the four waves' (m, l, O)
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    l[rt] += __shfl_xor(l[rt], 16);
+    l[rt] += __shfl_xor(l[rt], 32);
+  }
+  float* ml = reinterpret_cast<float*>(lds + L::kMlOff);
+  if (h == 0) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      ml[w * 16 * RT + 16 * rt + i16] = m[rt];
+      ml[(DEC_WAVES + w) * 16 * RT + 16 * rt + i16] = l[rt];
+    }
+  }
+  __syncthreads();   // every wave is out of its key loop: the V images are free
+  float lt[RT], mt[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    float mm = DEC_NEG_INF;
+#pragma unroll
+    for (int x = 0; x < DEC_WAVES; ++x) mm = fmaxf(mm, ml[x * 16 * RT + 16 * rt + i16]);
+    const float mu = (mm == DEC_NEG_INF) ? 0.f : mm;
+    float ls = 0.f;
+#pragma unroll
+    for (int x = 0; x < DEC_WAVES; ++x) ls += ml[(DEC_WAVES + x) * 16 * RT + 16 * rt + i16] * __builtin_amdgcn_exp2f(ml[x * 16 * RT + 16 * rt + i16] - mu);
+    const float mine = __builtin_amdgcn_exp2f(m[rt] - mu);
+#pragma unroll
+    for (int db = 0; db < DB; ++db) o[rt][db] *= mine;
+    lt[rt] = ls;
+    mt[rt] = mm;
+  }
+  f32x4_t* slot = reinterpret_cast<f32x4_t*>(lds + L::kVOff);
+  constexpr int SLOT = L::kOBytes / 16;   // f32x4 per slot
+  auto put = [&](int sl) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int db = 0; db < DB; ++db) slot[sl * SLOT + (rt * DB + db) * 64 + lane] = o[rt][db];
+  };
+  auto add = [&](int sl) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+      for (int db = 0; db < DB; ++db) o[rt][db] += slot[sl * SLOT + (rt * DB + db) * 64 + lane];
+  };
+  if (w >= 2) put(w - 2);
+  __syncthreads();
+  if (w < 2) add(w);
+  __syncthreads();
+  if (w == 1) put(0);
+  __syncthreads();
+  if (w != 0) return;
+  add(0);
+
+  // ---- wave 0 writes: fp16 O (S == 1) or the normalised fp32 partial + the row's log2-domain log-sum-exp
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    const int r = 16 * rt + i16;
+    if (r >= R) continue;   // padding rows store nothing
+    const float inv = lt[rt] > 0.f ? 1.f / lt[rt] : 0.f;
+    const long row = row0 + r;
+    if (S == 1) {
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        const f32x4_t x = o[rt][db] * inv;
+        half4_t y = {(half_t)x[0], (half_t)x[1], (half_t)x[2], (half_t)x[3]};
+        *reinterpret_cast<half4_t*>(O + row * D + 16 * db + 4 * h) = y;
+      }
+    } else {
+      float* po = part_o + ((long)s_idx * total_rows + row) * D;
+#pragma unroll
+      for (int db = 0; db < DB; ++db) *reinterpret_cast<f32x4_t*>(po + 16 * db + 4 * h) = o[rt][db] * inv;
+      if (h == 0) part_lse[(long)s_idx * total_rows + row] = lt[rt] > 0.f ? mt[rt] + log2f(lt[rt]) : DEC_NEG_INF;
+    }
+  }

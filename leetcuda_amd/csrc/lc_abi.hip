@@ -87,6 +87,22 @@ int decode_plan(const void* const* ptrs, int B, int H, int Hkv, int Nq, int Ncap
   return plan_attn_decode(read_knobs(), B, H, Hkv, Nq, Ncap, D, (flags & LC_ATTN_CAUSAL) != 0, p);
 }
 
+// lc_attn_decode_paged_f16 and its two query calls: decode_plan's checks on Ncap = max_pages x page_size, with the page checks where Ncap's sit; the
+// plan is that of the contiguous call of that Ncap (same S, same workspace bytes) with the paging recorded.  ptrs: Q, Kpool, Vpool, O.
+int decode_paged_plan(const void* const* ptrs, int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags,
+                      DecodePlan* p) {
+  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
+  if (B <= 0 || Nq <= 0 || num_pages <= 0 || max_pages <= 0 || D <= 0) return LC_ERR_SHAPE;
+  if (page_size < 16 || (page_size & (page_size - 1)) != 0) return LC_ERR_SHAPE;   // a power of two >= 16: a 16-key load group never straddles a page
+  const long ncap = (long)max_pages * page_size;
+  if (ncap > 0x7fffffffL) return LC_ERR_SHAPE;
+  if (int rc = decode_plan(ptrs, B, H, Hkv, Nq, (int)ncap, D, flags, p)) return rc;
+  p->page_size = page_size;
+  p->num_pages = num_pages;
+  p->max_pages = max_pages;
+  return LC_OK;
+}
+
 // warmup + iters calls of `launch` (returns a status) between two events (lc_hgemm_time, lc_attn_time): ms per timed call
 template <typename Launch>
 int time_launches(int warmup, int iters, void* stream, float* ms_per_launch, Launch launch) {
@@ -321,7 +337,7 @@ int lc_attn_decode_f16(const void* Q, const void* K, const void* V, void* O, con
   if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
   if (int rc = launch_guard()) return rc;
   return launch_attn_decode(p, DecodePtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V),
-                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream)}, workspace);
+                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), nullptr}, workspace);
 }
 
 size_t lc_attn_decode_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D) {
@@ -334,6 +350,34 @@ int lc_attn_decode_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, i
   if (!buf || buflen < 8) return LC_ERR_ARG;
   DecodePlan p;
   if (int rc = decode_plan(nullptr, B, H, Hkv, Nq, Ncap, D, flags, &p)) return rc;
+  format_attn_decode(p, buf, buflen);
+  return LC_OK;
+}
+
+int lc_attn_decode_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* block_table, const int* kv_len, int B, int H,
+                             int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (!Q || !Kpool || !Vpool || !O || !block_table || !kv_len) return LC_ERR_ARG;
+  const void* ptrs[4] = {Q, Kpool, Vpool, O};
+  DecodePlan p;
+  if (int rc = decode_paged_plan(ptrs, B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, &p)) return rc;
+  if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_decode(p, DecodePtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(Kpool), static_cast<const half_t*>(Vpool),
+                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table}, workspace);
+}
+
+size_t lc_attn_decode_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D) {
+  DecodePlan p;   // (num_pages decides nothing)
+  return decode_paged_plan(nullptr, B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, &p) == LC_OK ? decode_workspace_bytes(p) : 0;
+}
+
+int lc_attn_decode_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
+  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  DecodePlan p;
+  if (int rc = decode_paged_plan(nullptr, B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, &p)) return rc;
   format_attn_decode(p, buf, buflen);
   return LC_OK;
 }

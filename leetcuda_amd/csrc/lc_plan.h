@@ -129,10 +129,13 @@ void format_attn(const AttnPlan& p, char* buf, int buflen);
 // attn_decode_combine_kernel<D>.  RT = row tiles of 16 that hold the R = (H / Hkv) x Nq query rows of a K / V head.  S, the KV ranges per (batch, K / V
 // head), is decided from (B x Hkv, ceil(Ncap / 64), rule_cus, "attn_decode_split") and NEVER from kv_len, which only the kernel reads: the smallest S
 // that gives every CU a workgroup, with at least 4 tiles of Ncap per range, at most 64; the knob forces 1 .. 64 (ranges may then be empty).
+// A paged call (lc_attn_decode_paged_f16; attn_decode_paged.hip) is the same decision with Ncap = max_pages x page_size: page_size > 0 names and
+// launches attn_decode_paged_kernel<D, RT>; RT, S and the workspace bytes are those of the contiguous call of that Ncap.
 struct DecodePlan {
   int B, H, Hkv, Nq, Ncap, D;
   bool causal;
   int RT, S;
+  int page_size, num_pages, max_pages;   // 0: a contiguous [B,Hkv,Ncap,D] cache
 };
 int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p);   // checked arguments
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel)
@@ -145,7 +148,10 @@ struct DecodePtrs {
   half_t* O;
   const int* kv_len;   // device int32[B] or nullptr
   hipStream_t st;
+  const int* block_table;   // paged: device int32[B, max_pages] (K, V: the pools); else nullptr
 };
 int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace);   // tu_attn_decode.hip
+// the S range workgroups of a paged plan (tu_attn_decode_paged.hip; launch_attn_decode calls it and owns S, the partials and the combine)
+int launch_attn_decode_paged_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 }  // namespace lc

@@ -1,5 +1,6 @@
 // tu_attn_decode.hip — translation unit of the decode attention kernels (attn_decode.hip: attn_decode_kernel<D, RT>, attn_decode_combine_kernel<D>)
-// and the launcher of a DecodePlan (lc_plan.h).  lc_attn_decode_f16 (lc_abi.hip) checks and plans; this unit launches — see lc_launch.h
+// and the launcher of a DecodePlan (lc_plan.h).  lc_attn_decode_f16 / lc_attn_decode_paged_f16 (lc_abi.hip) check and plan; this unit launches — see
+// lc_launch.h.  A plan with page_size > 0 runs attn_decode_paged_kernel<D, RT> (tu_attn_decode_paged.hip) in place of attn_decode_kernel<D, RT>
 #include "attn_decode.hip"
 #include "lc_plan.h"
 
@@ -17,12 +18,14 @@ int launch_decode_rt(const DecodePlan& p, int S, const DecodePtrs& a, float* par
 template <int D>
 int launch_decode_d(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
   int rc;
-  switch (p.RT) {
-    case 1: rc = launch_decode_rt<D, 1>(p, S, a, part_o, part_lse); break;
-    case 2: rc = launch_decode_rt<D, 2>(p, S, a, part_o, part_lse); break;
-    case 4: rc = launch_decode_rt<D, 4>(p, S, a, part_o, part_lse); break;
-    default: return LC_ERR_SHAPE;
-  }
+  if (p.page_size > 0) rc = launch_attn_decode_paged_ranges(p, S, a, part_o, part_lse);   // (tu_attn_decode_paged.hip; the combine below is shared)
+  else
+    switch (p.RT) {
+      case 1: rc = launch_decode_rt<D, 1>(p, S, a, part_o, part_lse); break;
+      case 2: rc = launch_decode_rt<D, 2>(p, S, a, part_o, part_lse); break;
+      case 4: rc = launch_decode_rt<D, 4>(p, S, a, part_o, part_lse); break;
+      default: return LC_ERR_SHAPE;
+    }
   if (rc != LC_OK || S == 1) return rc;
   const long rows = (long)p.B * p.H * p.Nq;
   constexpr int rows_per_block = 256 / (D / 4);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
           causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
           instead of this library (context only); kvh = K: grouped-query attention, K / V tensors with K heads through lc_attn_fwd_f16_gqa
           (FLOPs counted as for the H query heads); kvh = K with expand: what a caller without that entry does — repeat_interleave K and V
@@ -13,6 +13,8 @@ usage: attn_rate.py [--seconds S] [--rounds R] spec...
           mask; with sdpa: scaled_dot_product_attention on k[:, :, :L] / v[:, :, :L] (enable_gqa where this torch has it, else on K / V
           expanded once outside the timing; non-causal only: torch's is_causal is top-left aligned).  Decode rows report microseconds per
           call (median, best, worst over the rounds) and K / V GB/s = 2 B K L D 2 bytes / median time
+          page = P (with q): the same logical cache scattered over a randomly permuted pool of N / P pages of P keys per sequence, through
+          lc_attn_decode_paged_f16 and a block table (combinable with q, len, dsplit, causal; N % P == 0)
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
 cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
 causal: half of that, the flash-attn convention) and the median time per call."""
@@ -95,6 +97,23 @@ def run_decode(spec, shape, opts):
     q, k, v, o = cache[key]
     lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
     split = opt_int(opts, "dsplit", 0)
+    page = opt_int(opts, "page", 0)
+    if page:
+        if N % page or "sdpa" in opts:
+            raise SystemExit(f"{spec}: page needs N % page == 0 and this library")
+        pkey = ("pool", page) + key
+        if pkey not in cache:                           # (the contiguous cache stays resident: both arms of an A/B read the same values)
+            for old_key in [x for x in cache if x[0] == "pool"]:
+                del cache[old_key]
+            mp = N // page
+            perm = torch.randperm(B * mp, device="cuda", generator=torch.Generator(device="cuda").manual_seed(page))
+            pools = []
+            for x in (k, v):
+                pool = torch.empty(B * mp, kvh, page, D, device="cuda", dtype=torch.half)
+                pool[perm] = x.view(B, kvh, mp, page, D).permute(0, 2, 1, 3, 4).reshape(B * mp, kvh, page, D)
+                pools.append(pool)
+            cache[pkey] = (pools[0], pools[1], perm.view(B, mp).to(torch.int32).contiguous())
+        k_pool, v_pool, table = cache[pkey]
     capi.tune("attn_decode_split", split)
     try:
         if "sdpa" in opts:
@@ -109,6 +128,9 @@ def run_decode(spec, shape, opts):
                 ke, ve = ks.repeat_interleave(H // kvh, dim=1), vs.repeat_interleave(H // kvh, dim=1)
                 name = "torch sdpa (K / V expanded)"
                 step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ke, ve)  # noqa: E731
+        elif page:
+            name = capi.attn_decode_paged_kernel_name(B, H, kvh, nq, page, N // page, D, causal=causal)
+            step = lambda: capi.attn_decode_paged(q, k_pool, v_pool, o, table, lens, causal=causal)  # noqa: E731
         else:
             name = capi.attn_decode_kernel_name(B, H, kvh, nq, N, D, causal=causal)
             step = lambda: capi.attn_decode(q, k, v, o, lens, causal=causal)  # noqa: E731
@@ -173,7 +195,7 @@ if any("causal" in s.split(":") for s in args):
 for s in args:
     v, t = sorted(res[s]), sorted(times[s])
     if any(o.startswith("q=") for o in s.split(":")):     # decode: res holds K / V GB/s
-        print(f"RATE {s:40s} {names[s]:32s} median {t[len(t) // 2] * 1e3:8.1f} us  best {t[0] * 1e3:8.1f}  worst {t[-1] * 1e3:8.1f}  "
+        print(f"RATE {s:40s} {names[s]:38s} median {t[len(t) // 2] * 1e3:8.1f} us  best {t[0] * 1e3:8.1f}  worst {t[-1] * 1e3:8.1f}  "
               f"K/V {v[len(v) // 2]:7.0f} GB/s", flush=True)
         continue
     print(f"RATE {s:34s} {names[s]:44s} median {v[len(v) // 2]:7.1f}  best {v[-1]:7.1f}  worst {v[0]:7.1f} TFLOP/s  {t[len(t) // 2] * 1e3:9.1f} us", flush=True)
