@@ -385,6 +385,35 @@ size_t lc_attn_decode_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int p
 int lc_attn_decode_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
                                      int flags, char* buf, int buflen);
 
+/* EXTENSION: lc_attn_decode_paged_f16 over a paged KV cache kept in fp8 (attn_decode_paged_kv8.hip): the call is bound
+ * by reading K and V once, and this halves what is read.
+ *   O = softmax(Q (k_scale[g] K8)^T / sqrt(D)) (v_scale[g] V8),   g = the K / V head of the query head
+ * Q, O, block_table, kv_len, flags, workspace and stream are exactly those of lc_attn_decode_paged_f16.
+ * Kpool8, Vpool8: [num_pages,Hkv,page_size,D] bytes, each an OCP e4m3fn value (the format of lc_gemm_fp8_e4m3 and of torch.float8_e4m3fn: bias
+ * 7, no infinity, 0x7f / 0xff = NaN), dense and 16-byte aligned.
+ * k_scale, v_scale: DEVICE float[Hkv], one scale per K / V head, or NULL = 1.0.  Like block_table and kv_len they are read by the kernel only: a
+ * captured graph may be replayed after they were rewritten in place.  They are applied in fp32 (k_scale inside the score scale, v_scale inside
+ * the normalisation of O), never to an fp16 value.
+ * The mask, the clamps of kv_len and of page ids, "a row without a visible key gets O = 0" and what is never read (table entries at positions >=
+ * ceil(L_b / page_size), pool bytes of positions >= L_b — NaN codes included) are those of lc_attn_decode_paged_f16; so is the memory-safety note.
+ * Checks: lc_attn_decode_paged_f16's, in its order, with the two fp8 pools in the pointer and alignment checks; k_scale / v_scale may be NULL and
+ * are not checked.  The span bound is that of one-byte elements: max_pages x page_size x D >= 2 GiB is LC_ERR_SHAPE.
+ * Kernel: attn_decode_paged_kv8_kernel<D, RT>, S > 1: + attn_decode_combine_kernel<D>.  RT, S, the workspace bytes and the capture / failed-lease
+ * fallback to S = 1 are those of lc_attn_decode_paged_f16 for the same shape (same rule, same "attn_decode_split", same CU count).
+ * Every e4m3 value is an fp16 value and the kernel converts exactly, so with power-of-two scales that keep the dequantised values normal fp16
+ * numbers the output is BIT-IDENTICAL to lc_attn_decode_paged_f16 on the dequantised fp16 pool (same Q, table, kv_len, flags and S).
+ * Not here: a contiguous fp8 entry (a contiguous cache with Ncap a power of two is a pool with num_pages = B), per-token or per-page scales,
+ * a quantise-and-append kernel, e5m2, fp8 Q.
+ * The name call never launches: "attn_decode_paged_kv8_kernel<D,RT>", with S > 1 followed by " xS". */
+int lc_attn_decode_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O,
+                             const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                             int B, int H, int Hkv, int Nq,
+                             int num_pages, int page_size, int max_pages, int D, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_decode_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D);
+int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                         int flags, char* buf, int buflen);
+
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

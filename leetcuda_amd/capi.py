@@ -58,6 +58,9 @@ SYMBOLS = {
     "lc_attn_decode_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_decode_paged_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "lc_attn_decode_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_decode_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_decode_paged_kv8_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "lc_attn_decode_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -491,6 +494,58 @@ def attn_decode_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal
     buf = C.create_string_buffer(128)
     check(load().lc_attn_decode_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, ATTN_CAUSAL if causal else 0, buf, 128),
           "lc_attn_decode_paged_kernel_name")
+    return buf.value.decode()
+
+
+def _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale):
+    """The dtype and shape checks of attn_decode_paged_kv8 (no GPU needed): fp16 q / o, fp8 e4m3fn or uint8 pools, float32 [Hkv] scales or None.
+    Returns _attn_dims_decode_paged's tuple."""
+    import torch
+    fp8 = (torch.float8_e4m3fn, torch.uint8)
+    if q.dtype != torch.half or o.dtype != torch.half:
+        raise TypeError(f"q / o must be float16, got {q.dtype} / {o.dtype}")
+    if k_pool8.dtype not in fp8 or v_pool8.dtype not in fp8:
+        raise TypeError(f"k_pool8 / v_pool8 must be float8_e4m3fn or uint8, got {k_pool8.dtype} / {v_pool8.dtype}")
+    dims = _attn_dims_decode_paged(q, k_pool8, v_pool8, o, block_table, kv_len)
+    if block_table.dtype != torch.int32 or kv_len.dtype != torch.int32:
+        raise TypeError(f"block_table / kv_len must be int32, got {block_table.dtype} / {kv_len.dtype}")
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            continue
+        if s.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {s.dtype}")
+        if tuple(s.shape) != (dims[2],):
+            _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
+    return dims
+
+
+def attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=None, v_scale=None, causal=False, workspace=None):
+    """Decode attention over a paged KV cache kept in fp8 (lc_attn_decode_paged_kv8): attn_decode_paged with k_pool8, v_pool8
+    [num_pages,Hkv,page_size,D] of torch.float8_e4m3fn (or its bytes as uint8) and k_scale, v_scale DEVICE float32 [Hkv] tensors (None = 1.0):
+    K = k_scale[g] K8, V = v_scale[g] V8.  The scales are read by the kernel only, like block_table and kv_len."""
+    B, H, Hkv, Nq, P, ps, mp, D = _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale)
+    _need_gpu(q, k_pool8, v_pool8, o, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    ws, ws_bytes = 0, 0
+    if workspace is not None:
+        _need_gpu(workspace)
+        ws, ws_bytes = _ptr(workspace), workspace.numel() * workspace.element_size()
+    check(load().lc_attn_decode_paged_kv8(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(block_table), _ptr(kv_len),
+                                          _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
+                                          B, H, Hkv, Nq, P, ps, mp, D, ATTN_CAUSAL if causal else 0, ws or None, ws_bytes, _stream()),
+          "lc_attn_decode_paged_kv8")
+    return o
+
+
+def attn_decode_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs: those of attn_decode_paged for the same shape."""
+    return int(load().lc_attn_decode_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D))
+
+
+def attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
+    """The kernel attn_decode_paged_kv8 runs for this shape under the current knobs: "attn_decode_paged_kv8_kernel<D,RT>", + " xS" with S > 1."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, ATTN_CAUSAL if causal else 0, buf, 128),
+          "lc_attn_decode_paged_kv8_kernel_name")
     return buf.value.decode()
 
 

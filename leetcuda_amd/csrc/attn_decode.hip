@@ -20,7 +20,8 @@
 //     log2 domain (-inf: the range held no visible key) to the workspace; attn_decode_combine_kernel<D> merges the S partials (weight 0 for
 //     an empty range, O = 0 when every range is empty)
 // Reproducibility: the bits of one (batch, K / V head) depend on its Q, K, V, L_b, Nq, the causal flag and S only.
-// The body is shared with the paged-cache kernel (attn_decode_paged.hip), which replaces the address of a key row and nothing else.
+// The body is shared with the paged-cache kernel (attn_decode_paged.hip), which replaces the address of a key row and nothing else,
+// and with the fp8-cache kernel (attn_decode_paged_kv8.hip, §4.3g), which loads bytes and converts them in registers.
 #pragma once
 #include "lc_common.h"
 
@@ -58,6 +59,21 @@ struct DecodePaging {
   int num_pages, lps, max_pages;   // lps = log2(page_size), page_size >= 16
 };
 
+// An fp8 cache (attn_decode_paged_kv8.hip): K / V pool elements are OCP e4m3fn bytes, the value of element x of K / V head g is
+// k_scale[g] x (v_scale[g] x).  The fp16 kernels leave every field unused.
+struct DecodeKv8 {
+  const float *k_scale, *v_scale;   // device float[Hkv] or nullptr (= 1.0)
+};
+
+// eight e4m3 bytes (a: bytes 0 .. 3, b: bytes 4 .. 7, memory order) as eight fp16 values, element i = byte i: one v_cvt_scalef32_pk_f16_fp8 per two
+// elements, scale 1.0 — every e4m3 value is an fp16 value (the smallest, 2^-9, a normal one), so the conversion is exact; 0x7f / 0xff give NaN
+LC_DEVINL u32x4_t kv8_half8(uint32_t a, uint32_t b) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(a, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(a, 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, 1.0f, true))};
+}
+
 template <int D, int RT>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restrict__ Q, const half_t* __restrict__ K, const half_t* __restrict__ V,
                                                           half_t* __restrict__ O, const int* __restrict__ kv_len, float* __restrict__ part_o,
@@ -65,6 +81,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
                                                           float sl2, long total_rows) {
   constexpr bool PAGED = false;
   const DecodePaging pg{};
+  constexpr bool KV8 = false;
+  const DecodeKv8 kv8{};
 #include "attn_decode_body.inc"
 }
 

@@ -1,7 +1,9 @@
-// attn_decode_body.inc — the body of attn_decode_kernel<D, RT> (attn_decode.hip) and of attn_decode_paged_kernel<D, RT> (attn_decode_paged.hip),
-// included textually by both: the two kernels differ in how a key row becomes an address and in nothing else.  The including kernel has the
-// template parameters D, RT, the parameters Q, K, V, O, kv_len, part_o, part_lse, H, Hkv, Nq, Ncap, causal, S, sl2, total_rows, a
-// `constexpr bool PAGED` and a `const DecodePaging pg` (PAGED = false: unused) in scope.  See attn_decode.hip for the design.
+// attn_decode_body.inc — the body of attn_decode_kernel<D, RT> (attn_decode.hip), of attn_decode_paged_kernel<D, RT> (attn_decode_paged.hip) and of
+// attn_decode_paged_kv8_kernel<D, RT> (attn_decode_paged_kv8.hip), included textually by all three: the first two differ in how a key row becomes
+// an address and in nothing else; the third (KV8, always PAGED) loads e4m3 bytes instead of halves, converts them to fp16 in registers in front of
+// the two consumers and applies the per-head scales in fp32.  The including kernel has the template parameters D, RT, the parameters Q, K, V, O,
+// kv_len, part_o, part_lse, H, Hkv, Nq, Ncap, causal, S, sl2, total_rows, a `constexpr bool PAGED` with a `const DecodePaging pg` (PAGED = false:
+// unused) and a `constexpr bool KV8` with a `const DecodeKv8 kv8` (KV8 = false: unused) in scope.  See attn_decode.hip for the design.
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -13,6 +15,12 @@
   constexpr int NKB = STEP / 16;          // 16-key blocks of Sᵀ per step
   constexpr int NPS = STEP / 32;          // 32-key k-steps of Oᵀ += Vᵀ Pᵀ per step
   constexpr int VL = STEP * CH / 64;      // V chunks per lane and step
+  // KV8: a cache element is one byte.  A lane's D / 4 contiguous elements of a key row are KR = D / 64 dwordx4, a 16-byte V chunk holds 16
+  // elements of one key row (CHV per row, VLR per lane and step): half the registers in flight
+  constexpr int ROWB = KV8 ? D : D * 2;   // bytes of a cache row
+  constexpr int KR = KV8 ? KS / 2 : KS;
+  constexpr int CHV = KV8 ? CH / 2 : CH;
+  constexpr int VLR = KV8 ? VL / 2 : VL;
   extern __shared__ __attribute__((aligned(16))) char lds[];
 
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
@@ -70,7 +78,7 @@
 #pragma unroll
   for (int db = 0; db < DB; ++db) tr_off[db] = dec_v_off<D>(4 * h + q4, 2 * db + (p4 >> 1)) + 8 * (p4 & 1);
 
-  u32x4_t kf[NKB][KS], vf[VL];
+  u32x4_t kf[NKB][KR], vf[VLR];
   const int last = Lb - 1;   // (>= 0 whenever a tile exists)
   // step u of this wave: keys key0(u) ... key0(u) + STEP - 1 of tile t0 + w + 4 (u / SPT)
   auto key0 = [&](int u) { return (t0 + w + DEC_WAVES * (u / SPT)) * DEC_KVB + (u % SPT) * STEP; };
@@ -92,7 +100,7 @@
   };
   // byte base of (page id, this K / V head): 64-bit, scalar; the offset inside the run is 32-bit (one run is below 2 GiB: checked by the host)
   auto page_base = [&](const half_t* pool, int id) {
-    return reinterpret_cast<const char*>(pool) + ((((long)id * Hkv + kvh) << pg.lps) * (D * 2));
+    return reinterpret_cast<const char*>(pool) + ((((long)id * Hkv + kvh) << pg.lps) * ROWB);
   };
   const int pmask = PAGED ? (1 << pg.lps) - 1 : -1;
   auto load_k = [&](int u) {
@@ -101,7 +109,12 @@
     for (int kb = 0; kb < NKB; ++kb) {
       int key = k0 + 16 * kb + i16;
       key = key < last ? key : last;
-      if constexpr (PAGED) {
+      if constexpr (KV8) {   // bytes h D / 4 ... of the row; k-step s is bytes 8 s ... 8 s + 7 of them (k_frag)
+        const char* base = page_base(Kg, pid[kb]);
+        const unsigned off = (unsigned)(key & pmask) * ROWB + h * (D / 4);
+#pragma unroll
+        for (int s = 0; s < KR; ++s) kf[kb][s] = *reinterpret_cast<const u32x4_t*>(base + (off + 16 * s));
+      } else if constexpr (PAGED) {
         const char* base = page_base(Kg, pid[kb]);
         const unsigned off = (unsigned)(key & pmask) * (D * 2) + h * (D / 2);
 #pragma unroll
@@ -116,11 +129,13 @@
   auto load_v = [&](int u) {
     const int k0 = key0(u);
 #pragma unroll
-    for (int n = 0; n < VL; ++n) {
+    for (int n = 0; n < VLR; ++n) {
       const int c = n * 64 + lane;
-      int key = k0 + c / CH;
+      int key = k0 + c / CHV;
       key = key < last ? key : last;
-      if constexpr (PAGED)   // (chunk group n: the 64 / CH key rows from k0 + n 64 / CH on, inside 16-key block n 4 / CH)
+      if constexpr (KV8)   // (chunk group n: the 64 / CHV = 8 or 16 key rows from k0 + n 64 / CHV on, inside 16-key block n 4 / CHV)
+        vf[n] = *reinterpret_cast<const u32x4_t*>(page_base(Vg, pid[n * 4 / CHV]) + ((unsigned)(key & pmask) * ROWB + (c % CHV) * 16));
+      else if constexpr (PAGED)   // (chunk group n: the 64 / CH key rows from k0 + n 64 / CH on, inside 16-key block n 4 / CH)
         vf[n] = *reinterpret_cast<const u32x4_t*>(page_base(Vg, pid[n * 4 / CH]) + ((unsigned)(key & pmask) * (D * 2) + (c % CH) * 16));
       else
         vf[n] = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(Vg) + ((unsigned)key * (D * 2) + (c % CH) * 16));
@@ -128,11 +143,27 @@
   };
   auto store_v = [&]() {
 #pragma unroll
-    for (int n = 0; n < VL; ++n) {
+    for (int n = 0; n < VLR; ++n) {
       const int c = n * 64 + lane;
-      *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CH, c % CH)) = vf[n];
+      if constexpr (KV8) {   // one e4m3 chunk is the two adjacent fp16 chunks 2 (c % CHV), + 1 of its row: the image is the fp16 kernels'
+        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CHV, 2 * (c % CHV))) = kv8_half8(vf[n][0], vf[n][1]);
+        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CHV, 2 * (c % CHV) + 1)) = kv8_half8(vf[n][2], vf[n][3]);
+      } else {
+        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CH, c % CH)) = vf[n];
+      }
     }
   };
+  // the A operand of k-step s of 16-key block kb
+  auto k_frag = [&](int kb, int s) {
+    if constexpr (KV8) return __builtin_bit_cast(half8_t, kv8_half8(kf[kb][s >> 1][2 * (s & 1)], kf[kb][s >> 1][2 * (s & 1) + 1]));
+    else return __builtin_bit_cast(half8_t, kf[kb][s]);
+  };
+  // KV8: the scales of this K / V head, fp32 only: k_scale goes once into the score scale, v_scale into the normalisation of O
+  float sc2 = sl2, vsc = 1.f;
+  if constexpr (KV8) {
+    if (kv8.k_scale) sc2 *= __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, kv8.k_scale[kvh])));
+    if (kv8.v_scale) vsc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, kv8.v_scale[kvh])));
+  }
 
   const int my_tiles = t1 - t0 - w > 0 ? (t1 - t0 - w + DEC_WAVES - 1) / DEC_WAVES : 0;
   const int steps = my_tiles * SPT;
@@ -161,7 +192,7 @@
       for (int kb = 0; kb < NKB; ++kb) {
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < KS; ++s) acc = mfma16(__builtin_bit_cast(half8_t, kf[kb][s]), qf[s], acc);
+        for (int s = 0; s < KS; ++s) acc = mfma16(k_frag(kb, s), qf[s], acc);
         st[kb] = acc;
       }
       float mx = DEC_NEG_INF;
@@ -169,7 +200,7 @@
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float x = (k0 + 16 * kb + r < lim[rt]) ? st[kb][r] * sl2 : DEC_NEG_INF;   // select on the INDEX: the score may be anything
+          const float x = (k0 + 16 * kb + r < lim[rt]) ? st[kb][r] * sc2 : DEC_NEG_INF;   // select on the INDEX: the score may be anything
           st[kb][r] = x;
           mx = fmaxf(mx, x);
         }
@@ -282,7 +313,8 @@
   for (int rt = 0; rt < RT; ++rt) {
     const int r = 16 * rt + i16;
     if (r >= R) continue;   // padding rows store nothing
-    const float inv = lt[rt] > 0.f ? 1.f / lt[rt] : 0.f;
+    float inv = lt[rt] > 0.f ? 1.f / lt[rt] : 0.f;
+    if constexpr (KV8) inv *= vsc;
     const long row = row0 + r;
     if (S == 1) {
 #pragma unroll

@@ -131,11 +131,14 @@ void format_attn(const AttnPlan& p, char* buf, int buflen);
 // that gives every CU a workgroup, with at least 4 tiles of Ncap per range, at most 64; the knob forces 1 .. 64 (ranges may then be empty).
 // A paged call (lc_attn_decode_paged_f16; attn_decode_paged.hip) is the same decision with Ncap = max_pages x page_size: page_size > 0 names and
 // launches attn_decode_paged_kernel<D, RT>; RT, S and the workspace bytes are those of the contiguous call of that Ncap.
+// An fp8-cache call (lc_attn_decode_paged_kv8; attn_decode_paged_kv8.hip) is the paged decision again: kv8 names and launches
+// attn_decode_paged_kv8_kernel<D, RT> on e4m3 pools and decides nothing else.
 struct DecodePlan {
   int B, H, Hkv, Nq, Ncap, D;
   bool causal;
   int RT, S;
   int page_size, num_pages, max_pages;   // 0: a contiguous [B,Hkv,Ncap,D] cache
+  bool kv8;                              // paged only: the pools hold e4m3 bytes
 };
 int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p);   // checked arguments
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel)
@@ -149,9 +152,12 @@ struct DecodePtrs {
   const int* kv_len;   // device int32[B] or nullptr
   hipStream_t st;
   const int* block_table;   // paged: device int32[B, max_pages] (K, V: the pools); else nullptr
+  const float *k_scale, *v_scale;   // kv8 (K, V: the e4m3 pools' bytes): device float[Hkv] or nullptr = 1.0; else nullptr
 };
 int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace);   // tu_attn_decode.hip
 // the S range workgroups of a paged plan (tu_attn_decode_paged.hip; launch_attn_decode calls it and owns S, the partials and the combine)
 int launch_attn_decode_paged_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+// the same of a kv8 plan (tu_attn_decode_paged_kv8.hip)
+int launch_attn_decode_paged_kv8_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 }  // namespace lc

@@ -1,6 +1,7 @@
 // tu_attn_decode.hip — translation unit of the decode attention kernels (attn_decode.hip: attn_decode_kernel<D, RT>, attn_decode_combine_kernel<D>)
 // and the launcher of a DecodePlan (lc_plan.h).  lc_attn_decode_f16 / lc_attn_decode_paged_f16 (lc_abi.hip) check and plan; this unit launches — see
-// lc_launch.h.  A plan with page_size > 0 runs attn_decode_paged_kernel<D, RT> (tu_attn_decode_paged.hip) in place of attn_decode_kernel<D, RT>
+// lc_launch.h.  A plan with page_size > 0 runs attn_decode_paged_kernel<D, RT> (tu_attn_decode_paged.hip) in place of attn_decode_kernel<D, RT>,
+// one with kv8 set attn_decode_paged_kv8_kernel<D, RT> (tu_attn_decode_paged_kv8.hip)
 #include "attn_decode.hip"
 #include "lc_plan.h"
 
@@ -18,7 +19,8 @@ int launch_decode_rt(const DecodePlan& p, int S, const DecodePtrs& a, float* par
 template <int D>
 int launch_decode_d(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
   int rc;
-  if (p.page_size > 0) rc = launch_attn_decode_paged_ranges(p, S, a, part_o, part_lse);   // (tu_attn_decode_paged.hip; the combine below is shared)
+  if (p.kv8) rc = launch_attn_decode_paged_kv8_ranges(p, S, a, part_o, part_lse);   // (tu_attn_decode_paged_kv8.hip)
+  else if (p.page_size > 0) rc = launch_attn_decode_paged_ranges(p, S, a, part_o, part_lse);   // (tu_attn_decode_paged.hip; the combine below is shared)
   else
     switch (p.RT) {
       case 1: rc = launch_decode_rt<D, 1>(p, S, a, part_o, part_lse); break;

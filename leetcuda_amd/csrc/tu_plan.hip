@@ -689,7 +689,7 @@ int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p) {
 // waves without work while the combine still reads S partials.
 int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p) {
   const int R = (H / Hkv) * Nq;
-  *p = DecodePlan{B, H, Hkv, Nq, Ncap, D, causal, R <= 16 ? 1 : R <= 32 ? 2 : 4, 1, 0, 0, 0};
+  *p = DecodePlan{B, H, Hkv, Nq, Ncap, D, causal, R <= 16 ? 1 : R <= 32 ? 2 : 4, 1, 0, 0, 0, false};
   if (k.attn_decode_split > 0) {
     p->S = k.attn_decode_split;
     return LC_OK;
@@ -701,7 +701,7 @@ int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, in
   return LC_OK;
 }
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
-  const char* kern = p.page_size > 0 ? "attn_decode_paged_kernel" : "attn_decode_kernel";
+  const char* kern = p.kv8 ? "attn_decode_paged_kv8_kernel" : p.page_size > 0 ? "attn_decode_paged_kernel" : "attn_decode_kernel";
   if (p.S > 1) snprintf(buf, buflen, "%s<%d,%d> x%d", kern, p.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)
   else snprintf(buf, buflen, "%s<%d,%d>", kern, p.D, p.RT);
 }

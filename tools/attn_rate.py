@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P[:kv8]] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
           causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
           instead of this library (context only); kvh = K: grouped-query attention, K / V tensors with K heads through lc_attn_fwd_f16_gqa
           (FLOPs counted as for the H query heads); kvh = K with expand: what a caller without that entry does — repeat_interleave K and V
@@ -15,6 +15,8 @@ usage: attn_rate.py [--seconds S] [--rounds R] spec...
           call (median, best, worst over the rounds) and K / V GB/s = 2 B K L D 2 bytes / median time
           page = P (with q): the same logical cache scattered over a randomly permuted pool of N / P pages of P keys per sequence, through
           lc_attn_decode_paged_f16 and a block table (combinable with q, len, dsplit, causal; N % P == 0)
+          kv8 (with page): that pool quantised to e4m3 with one scale per K / V head (amax / 448), through lc_attn_decode_paged_kv8; its
+          K / V GB/s count one byte per element
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
 cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
 causal: half of that, the flash-attn convention) and the median time per call."""
@@ -98,12 +100,15 @@ def run_decode(spec, shape, opts):
     lens = torch.full((B,), L, dtype=torch.int32, device="cuda")
     split = opt_int(opts, "dsplit", 0)
     page = opt_int(opts, "page", 0)
+    kv8 = "kv8" in opts
+    if kv8 and not page:
+        raise SystemExit(f"{spec}: kv8 needs page=P")
     if page:
         if N % page or "sdpa" in opts:
             raise SystemExit(f"{spec}: page needs N % page == 0 and this library")
-        pkey = ("pool", page) + key
-        if pkey not in cache:                           # (the contiguous cache stays resident: both arms of an A/B read the same values)
-            for old_key in [x for x in cache if x[0] == "pool"]:
+        pkey = ("pool", page, kv8) + key
+        if pkey not in cache:                           # (the contiguous cache stays resident: both arms of an A/B read the same values;
+            for old_key in [x for x in cache if x[0] == "pool" and x[1] != page]:      # so do the fp16 and the fp8 pool of one page size)
                 del cache[old_key]
             mp = N // page
             perm = torch.randperm(B * mp, device="cuda", generator=torch.Generator(device="cuda").manual_seed(page))
@@ -112,8 +117,12 @@ def run_decode(spec, shape, opts):
                 pool = torch.empty(B * mp, kvh, page, D, device="cuda", dtype=torch.half)
                 pool[perm] = x.view(B, kvh, mp, page, D).permute(0, 2, 1, 3, 4).reshape(B * mp, kvh, page, D)
                 pools.append(pool)
-            cache[pkey] = (pools[0], pools[1], perm.view(B, mp).to(torch.int32).contiguous())
-        k_pool, v_pool, table = cache[pkey]
+            sc = [None, None]
+            if kv8:                                     # per-head scales that map the head's largest magnitude onto e4m3's largest, 448
+                sc = [(x.float().abs().amax(dim=(0, 2, 3)) / 448.0).contiguous() for x in (k, v)]
+                pools = [(pool.float() / s.view(1, kvh, 1, 1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn) for pool, s in zip(pools, sc)]
+            cache[pkey] = (pools[0], pools[1], perm.view(B, mp).to(torch.int32).contiguous(), sc[0], sc[1])
+        k_pool, v_pool, table, k_scale, v_scale = cache[pkey]
     capi.tune("attn_decode_split", split)
     try:
         if "sdpa" in opts:
@@ -128,6 +137,9 @@ def run_decode(spec, shape, opts):
                 ke, ve = ks.repeat_interleave(H // kvh, dim=1), vs.repeat_interleave(H // kvh, dim=1)
                 name = "torch sdpa (K / V expanded)"
                 step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ke, ve)  # noqa: E731
+        elif kv8:
+            name = capi.attn_decode_paged_kv8_kernel_name(B, H, kvh, nq, page, N // page, D, causal=causal)
+            step = lambda: capi.attn_decode_paged_kv8(q, k_pool, v_pool, o, table, lens, k_scale, v_scale, causal=causal)  # noqa: E731
         elif page:
             name = capi.attn_decode_paged_kernel_name(B, H, kvh, nq, page, N // page, D, causal=causal)
             step = lambda: capi.attn_decode_paged(q, k_pool, v_pool, o, table, lens, causal=causal)  # noqa: E731
@@ -137,7 +149,7 @@ def run_decode(spec, shape, opts):
         ms = timed(step)
     finally:
         capi.tune("attn_decode_split", 0)
-    return name, 2.0 * B * kvh * L * D * 2 / ms * 1e-6, ms
+    return name, 2.0 * B * kvh * L * D * (1 if kv8 else 2) / ms * 1e-6, ms
 
 
 def run(spec):
