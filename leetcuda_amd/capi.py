@@ -400,19 +400,51 @@ def attn_fwd_gqa(q, k, v, o, v_transposed=False, causal=False):
     return o
 
 
-def _attn_dims_decode(q, k, v, o, kv_len=None):
-    """q, o [B,H,Nq,D]; k, v [B,Hkv,Ncap,D] (the cache); kv_len None or int32 [B]; H % Hkv == 0.  Returns B, H, Hkv, Nq, Ncap, D."""
+def _decode_dims(q, k, v, o, cache, kname, vname, batched):
+    """What _attn_dims_decode and _attn_dims_decode_paged share: q, o [B,H,Nq,D]; k, v of one 4-D shape with Hkv at 1 and D last (batched: B first);
+    H % Hkv == 0.  Returns B, H, Hkv, Nq, D."""
     if q.dim() != 4 or k.dim() != 4:
-        _shape_err("4-D [B,H,Nq,D] / [B,Hkv,Ncap,D] tensors expected")
+        _shape_err(f"4-D [B,H,Nq,D] / {cache} tensors expected")
     B, H, Nq, D = q.shape
-    Hkv, Ncap = k.shape[1], k.shape[2]
-    if tuple(k.shape) != (B, Hkv, Ncap, D) or tuple(v.shape) != (B, Hkv, Ncap, D) or tuple(o.shape) != (B, H, Nq, D):
-        _shape_err(f"q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} o {tuple(o.shape)}")
+    Hkv = k.shape[1]
+    if k.shape[3] != D or (batched and k.shape[0] != B) or tuple(v.shape) != tuple(k.shape) or tuple(o.shape) != (B, H, Nq, D):
+        _shape_err(f"q {tuple(q.shape)} {kname} {tuple(k.shape)} {vname} {tuple(v.shape)} o {tuple(o.shape)}")
     if Hkv < 1 or Hkv > H or H % Hkv != 0:
         _shape_err(f"{H} query heads on {Hkv} K/V heads")
+    return B, H, Hkv, Nq, D
+
+
+def _attn_dims_decode(q, k, v, o, kv_len=None):
+    """q, o [B,H,Nq,D]; k, v [B,Hkv,Ncap,D] (the cache); kv_len None or int32 [B]; H % Hkv == 0.  Returns B, H, Hkv, Nq, Ncap, D."""
+    B, H, Hkv, Nq, D = _decode_dims(q, k, v, o, "[B,Hkv,Ncap,D]", "k", "v", True)
     if kv_len is not None and tuple(kv_len.shape) != (B,):
         _shape_err(f"kv_len {tuple(kv_len.shape)} for batch {B}")
-    return B, H, Hkv, Nq, Ncap, D
+    return B, H, Hkv, Nq, k.shape[2], D
+
+
+def _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len):
+    """q, o [B,H,Nq,D]; k_pool, v_pool [num_pages,Hkv,page_size,D]; block_table int32 [B,max_pages]; kv_len int32 [B]; H % Hkv == 0.
+    Returns B, H, Hkv, Nq, num_pages, page_size, max_pages, D."""
+    B, H, Hkv, Nq, D = _decode_dims(q, k_pool, v_pool, o, "[num_pages,Hkv,page_size,D]", "k_pool", "v_pool", False)
+    if block_table is None or block_table.dim() != 2 or block_table.shape[0] != B:
+        _shape_err(f"block_table {None if block_table is None else tuple(block_table.shape)} for batch {B}")
+    if kv_len is None or tuple(kv_len.shape) != (B,):
+        _shape_err(f"kv_len {None if kv_len is None else tuple(kv_len.shape)} for batch {B}")
+    return B, H, Hkv, Nq, k_pool.shape[0], k_pool.shape[2], block_table.shape[1], D
+
+
+def _workspace_args(workspace):
+    """(pointer or None, bytes) of the optional caller workspace of a decode call"""
+    if workspace is None:
+        return None, 0
+    _need_gpu(workspace)
+    return _ptr(workspace) or None, workspace.numel() * workspace.element_size()
+
+
+def _decode_kernel_name(symbol, *shape, causal) -> str:
+    buf = C.create_string_buffer(128)
+    check(getattr(load(), symbol)(*shape, ATTN_CAUSAL if causal else 0, buf, 128), symbol)
+    return buf.value.decode()
 
 
 def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None):
@@ -422,16 +454,12 @@ def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None):
     import torch
     _need_gpu(q, k, v, o)
     assert q.dtype == k.dtype == v.dtype == o.dtype == torch.half
-    B, H, Hkv, Nq, Ncap, D = _attn_dims_decode(q, k, v, o, kv_len)
+    dims = _attn_dims_decode(q, k, v, o, kv_len)
     if kv_len is not None:
         _need_gpu(kv_len)
         assert kv_len.dtype == torch.int32
-    ws, ws_bytes = 0, 0
-    if workspace is not None:
-        _need_gpu(workspace)
-        ws, ws_bytes = _ptr(workspace), workspace.numel() * workspace.element_size()
-    check(load().lc_attn_decode_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, B, H, Hkv, Nq, Ncap, D,
-                                    ATTN_CAUSAL if causal else 0, ws or None, ws_bytes, _stream()), "lc_attn_decode_f16")
+    check(load().lc_attn_decode_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, *dims,
+                                    ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), "lc_attn_decode_f16")
     return o
 
 
@@ -442,27 +470,7 @@ def attn_decode_workspace_bytes(B, H, Hkv, Nq, Ncap, D) -> int:
 
 def attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False) -> str:
     """The kernel attn_decode runs for this shape under the current knobs: "attn_decode_kernel<D,RT>", + " xS" with S > 1 KV ranges."""
-    buf = C.create_string_buffer(128)
-    check(load().lc_attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, ATTN_CAUSAL if causal else 0, buf, 128), "lc_attn_decode_kernel_name")
-    return buf.value.decode()
-
-
-def _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len):
-    """q, o [B,H,Nq,D]; k_pool, v_pool [num_pages,Hkv,page_size,D]; block_table int32 [B,max_pages]; kv_len int32 [B]; H % Hkv == 0.
-    Returns B, H, Hkv, Nq, num_pages, page_size, max_pages, D."""
-    if q.dim() != 4 or k_pool.dim() != 4:
-        _shape_err("4-D [B,H,Nq,D] / [num_pages,Hkv,page_size,D] tensors expected")
-    B, H, Nq, D = q.shape
-    P, Hkv, ps = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
-    if tuple(k_pool.shape) != (P, Hkv, ps, D) or tuple(v_pool.shape) != (P, Hkv, ps, D) or tuple(o.shape) != (B, H, Nq, D):
-        _shape_err(f"q {tuple(q.shape)} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)} o {tuple(o.shape)}")
-    if Hkv < 1 or Hkv > H or H % Hkv != 0:
-        _shape_err(f"{H} query heads on {Hkv} K/V heads")
-    if block_table is None or block_table.dim() != 2 or block_table.shape[0] != B:
-        _shape_err(f"block_table {None if block_table is None else tuple(block_table.shape)} for batch {B}")
-    if kv_len is None or tuple(kv_len.shape) != (B,):
-        _shape_err(f"kv_len {None if kv_len is None else tuple(kv_len.shape)} for batch {B}")
-    return B, H, Hkv, Nq, P, ps, block_table.shape[1], D
+    return _decode_kernel_name("lc_attn_decode_kernel_name", B, H, Hkv, Nq, Ncap, D, causal=causal)
 
 
 def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None):
@@ -472,15 +480,11 @@ def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, w
     import torch
     _need_gpu(q, k_pool, v_pool, o)
     assert q.dtype == k_pool.dtype == v_pool.dtype == o.dtype == torch.half
-    B, H, Hkv, Nq, P, ps, mp, D = _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len)
+    dims = _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len)
     _need_gpu(block_table, kv_len)
     assert block_table.dtype == torch.int32 and kv_len.dtype == torch.int32
-    ws, ws_bytes = 0, 0
-    if workspace is not None:
-        _need_gpu(workspace)
-        ws, ws_bytes = _ptr(workspace), workspace.numel() * workspace.element_size()
-    check(load().lc_attn_decode_paged_f16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), B, H, Hkv, Nq, P, ps, mp,
-                                          D, ATTN_CAUSAL if causal else 0, ws or None, ws_bytes, _stream()), "lc_attn_decode_paged_f16")
+    check(load().lc_attn_decode_paged_f16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), *dims,
+                                          ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), "lc_attn_decode_paged_f16")
     return o
 
 
@@ -491,10 +495,7 @@ def attn_decode_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D) ->
 
 def attn_decode_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
     """The kernel attn_decode_paged runs for this shape under the current knobs: "attn_decode_paged_kernel<D,RT>", + " xS" with S > 1."""
-    buf = C.create_string_buffer(128)
-    check(load().lc_attn_decode_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, ATTN_CAUSAL if causal else 0, buf, 128),
-          "lc_attn_decode_paged_kernel_name")
-    return buf.value.decode()
+    return _decode_kernel_name("lc_attn_decode_paged_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
 
 
 def _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale):
@@ -523,16 +524,11 @@ def attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=N
     """Decode attention over a paged KV cache kept in fp8 (lc_attn_decode_paged_kv8): attn_decode_paged with k_pool8, v_pool8
     [num_pages,Hkv,page_size,D] of torch.float8_e4m3fn (or its bytes as uint8) and k_scale, v_scale DEVICE float32 [Hkv] tensors (None = 1.0):
     K = k_scale[g] K8, V = v_scale[g] V8.  The scales are read by the kernel only, like block_table and kv_len."""
-    B, H, Hkv, Nq, P, ps, mp, D = _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale)
+    dims = _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale)
     _need_gpu(q, k_pool8, v_pool8, o, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
-    ws, ws_bytes = 0, 0
-    if workspace is not None:
-        _need_gpu(workspace)
-        ws, ws_bytes = _ptr(workspace), workspace.numel() * workspace.element_size()
     check(load().lc_attn_decode_paged_kv8(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(block_table), _ptr(kv_len),
                                           _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
-                                          B, H, Hkv, Nq, P, ps, mp, D, ATTN_CAUSAL if causal else 0, ws or None, ws_bytes, _stream()),
-          "lc_attn_decode_paged_kv8")
+                                          *dims, ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), "lc_attn_decode_paged_kv8")
     return o
 
 
@@ -543,10 +539,7 @@ def attn_decode_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D
 
 def attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
     """The kernel attn_decode_paged_kv8 runs for this shape under the current knobs: "attn_decode_paged_kv8_kernel<D,RT>", + " xS" with S > 1."""
-    buf = C.create_string_buffer(128)
-    check(load().lc_attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, ATTN_CAUSAL if causal else 0, buf, 128),
-          "lc_attn_decode_paged_kv8_kernel_name")
-    return buf.value.decode()
+    return _decode_kernel_name("lc_attn_decode_paged_kv8_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
 
 
 def attn_fwd_bf16(q, k, v, o):

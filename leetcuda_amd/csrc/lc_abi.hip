@@ -72,38 +72,31 @@ int attn_name(int BH, int G, int N, int D, int flags, bool bf16, int bad_n, char
   return LC_OK;
 }
 
-// The checks shared by lc_attn_decode_f16 (ptrs: its Q, K, V, O) and its two query calls (ptrs = nullptr): shape, then head dim, in the order of
-// check_attn_args; then the plan.  (Flags and null pointers are the callers' business: they come first.)
-// kv_bytes: the size of a cache element (2: fp16; 1: the e4m3 pools of lc_attn_decode_paged_kv8)
-int decode_plan(const void* const* ptrs, int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, DecodePlan* p, int kv_bytes = 2) {
-  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
-  if (B <= 0 || Nq <= 0 || Ncap <= 0 || D <= 0) return LC_ERR_SHAPE;
-  if ((long)(H / Hkv) * Nq > 64) return LC_ERR_SHAPE;   // R = G x Nq query rows per K / V head: four row tiles of 16 (no chunked prefill against a cache)
-  // one head's Ncap rows (an upper bound of one page run) stay below 2 GiB: the kernel's 32-bit offsets (attn_span_fits at two bytes an element)
-  if ((size_t)Ncap * (size_t)D * (size_t)kv_bytes >= 0x80000000ull) return LC_ERR_SHAPE;
-  if ((size_t)B * Hkv * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x Hkv x S workgroups, S <= 64
-  if (ptrs)
-    for (int i = 0; i < 4; ++i)
-      if (!aligned16(ptrs[i])) return LC_ERR_SHAPE;
-  if (D != 64 && D != 128) return LC_ERR_HEADDIM;
-  return plan_attn_decode(read_knobs(), B, H, Hkv, Nq, Ncap, D, (flags & LC_ATTN_CAUSAL) != 0, p);
+// The three decode families (contiguous, paged, paged fp8) each state a DecodeCall; check_attn_decode (tu_plan.hip) checks and plans it; decode_run,
+// decode_bytes and decode_name run, size and name the plan.  (DecodeCall: B, H, Hkv, Nq, D, flags, kv_bytes, paged, Ncap, num_pages, page_size, max_pages)
+DecodeCall decode_flat(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags) { return DecodeCall{B, H, Hkv, Nq, D, flags, 2, false, Ncap, 0, 0, 0}; }
+DecodeCall decode_paged(int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, int kv_bytes) {
+  return DecodeCall{B, H, Hkv, Nq, D, flags, kv_bytes, true, 0, num_pages, page_size, max_pages};
 }
-
-// lc_attn_decode_paged_f16 and its two query calls: decode_plan's checks on Ncap = max_pages x page_size, with the page checks where Ncap's sit; the
-// plan is that of the contiguous call of that Ncap (same S, same workspace bytes) with the paging recorded.  ptrs: Q, Kpool, Vpool, O.
-// kv8: lc_attn_decode_paged_kv8 and its query calls — the same checks with the span of one-byte elements, the same plan with kv8 recorded.
-int decode_paged_plan(const void* const* ptrs, int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags,
-                      DecodePlan* p, bool kv8 = false) {
-  if (H <= 0 || Hkv < 1 || Hkv > H || H % Hkv != 0) return LC_ERR_SHAPE;
-  if (B <= 0 || Nq <= 0 || num_pages <= 0 || max_pages <= 0 || D <= 0) return LC_ERR_SHAPE;
-  if (page_size < 16 || (page_size & (page_size - 1)) != 0) return LC_ERR_SHAPE;   // a power of two >= 16: a 16-key load group never straddles a page
-  const long ncap = (long)max_pages * page_size;
-  if (ncap > 0x7fffffffL) return LC_ERR_SHAPE;
-  if (int rc = decode_plan(ptrs, B, H, Hkv, Nq, (int)ncap, D, flags, p, kv8 ? 1 : 2)) return rc;
-  p->kv8 = kv8;
-  p->page_size = page_size;
-  p->num_pages = num_pages;
-  p->max_pages = max_pages;
+// block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere)
+int decode_run(const DecodeCall& c, const void* Q, const void* K, const void* V, void* O, const int* kv_len, const int* block_table, const float* k_scale,
+               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream) {
+  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale};
+  DecodePlan p;
+  if (int rc = check_attn_decode(c, &a, &p)) return rc;
+  if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_decode(p, a, workspace);
+}
+size_t decode_bytes(const DecodeCall& c) {
+  DecodePlan p;
+  return check_attn_decode(c, nullptr, &p) == LC_OK ? decode_workspace_bytes(p) : 0;
+}
+int decode_name(const DecodeCall& c, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;   // (an unknown flag has the same status: which of the two is found first cannot be told)
+  DecodePlan p;
+  if (int rc = check_attn_decode(c, nullptr, &p)) return rc;
+  format_attn_decode(p, buf, buflen);
   return LC_OK;
 }
 
@@ -333,86 +326,44 @@ int lc_attn_fwd_f16_gqa(const void* Q, const void* K, const void* V, void* O, in
 
 int lc_attn_decode_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len, int B, int H, int Hkv, int Nq, int Ncap, int D,
                        int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
-  if (!Q || !K || !V || !O) return LC_ERR_ARG;
-  const void* ptrs[4] = {Q, K, V, O};
-  DecodePlan p;
-  if (int rc = decode_plan(ptrs, B, H, Hkv, Nq, Ncap, D, flags, &p)) return rc;
-  if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
-  if (int rc = launch_guard()) return rc;
-  return launch_attn_decode(p, DecodePtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(K), static_cast<const half_t*>(V),
-                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), nullptr}, workspace);
+  return decode_run(decode_flat(B, H, Hkv, Nq, Ncap, D, flags), Q, K, V, O, kv_len, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
-size_t lc_attn_decode_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D) {
-  DecodePlan p;
-  return decode_plan(nullptr, B, H, Hkv, Nq, Ncap, D, 0, &p) == LC_OK ? decode_workspace_bytes(p) : 0;
-}
+size_t lc_attn_decode_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D) { return decode_bytes(decode_flat(B, H, Hkv, Nq, Ncap, D, 0)); }
 
 int lc_attn_decode_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, char* buf, int buflen) {
-  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
-  if (!buf || buflen < 8) return LC_ERR_ARG;
-  DecodePlan p;
-  if (int rc = decode_plan(nullptr, B, H, Hkv, Nq, Ncap, D, flags, &p)) return rc;
-  format_attn_decode(p, buf, buflen);
-  return LC_OK;
+  return decode_name(decode_flat(B, H, Hkv, Nq, Ncap, D, flags), buf, buflen);
 }
 
 int lc_attn_decode_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* block_table, const int* kv_len, int B, int H,
                              int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
-  if (!Q || !Kpool || !Vpool || !O || !block_table || !kv_len) return LC_ERR_ARG;
-  const void* ptrs[4] = {Q, Kpool, Vpool, O};
-  DecodePlan p;
-  if (int rc = decode_paged_plan(ptrs, B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, &p)) return rc;
-  if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
-  if (int rc = launch_guard()) return rc;
-  return launch_attn_decode(p, DecodePtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(Kpool), static_cast<const half_t*>(Vpool),
-                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table}, workspace);
+  return decode_run(decode_paged(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, 2), Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr,
+                    workspace, workspace_bytes, stream);
 }
 
+// (the two query calls of a paged family take no num_pages: it decides nothing)
 size_t lc_attn_decode_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D) {
-  DecodePlan p;   // (num_pages decides nothing)
-  return decode_paged_plan(nullptr, B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, &p) == LC_OK ? decode_workspace_bytes(p) : 0;
+  return decode_bytes(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, 2));
 }
 
 int lc_attn_decode_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
-  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
-  if (!buf || buflen < 8) return LC_ERR_ARG;
-  DecodePlan p;
-  if (int rc = decode_paged_plan(nullptr, B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, &p)) return rc;
-  format_attn_decode(p, buf, buflen);
-  return LC_OK;
+  return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 2), buf, buflen);
 }
 
 int lc_attn_decode_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* block_table, const int* kv_len,
                              const float* k_scale, const float* v_scale, int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages,
                              int D, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
-  if (!Q || !Kpool8 || !Vpool8 || !O || !block_table || !kv_len) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
-  const void* ptrs[4] = {Q, Kpool8, Vpool8, O};
-  DecodePlan p;
-  if (int rc = decode_paged_plan(ptrs, B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, &p, true)) return rc;
-  if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
-  if (int rc = launch_guard()) return rc;
-  return launch_attn_decode(p, DecodePtrs{static_cast<const half_t*>(Q), static_cast<const half_t*>(Kpool8), static_cast<const half_t*>(Vpool8),
-                                          static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale},
-                            workspace);
+  return decode_run(decode_paged(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, 1), Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale,
+                    workspace, workspace_bytes, stream);
 }
 
 size_t lc_attn_decode_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D) {
-  DecodePlan p;   // (num_pages decides nothing)
-  return decode_paged_plan(nullptr, B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, &p, true) == LC_OK ? decode_workspace_bytes(p) : 0;
+  return decode_bytes(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, 1));
 }
 
 int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
-  if (flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
-  if (!buf || buflen < 8) return LC_ERR_ARG;
-  DecodePlan p;
-  if (int rc = decode_paged_plan(nullptr, B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, &p, true)) return rc;
-  format_attn_decode(p, buf, buflen);
-  return LC_OK;
+  return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1), buf, buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -125,39 +125,50 @@ struct AttnPlan {   // walk / nsplit: W4U; sched: W4I ("attn_w4i_sched"); nw: LO
 int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p);
 void format_attn(const AttnPlan& p, char* buf, int buflen);
 
-// ONE decision per decode-attention call (lc_attn_decode_f16; attn_decode.hip): attn_decode_kernel<D, RT> on B x Hkv x S workgroups, S > 1 followed by
-// attn_decode_combine_kernel<D>.  RT = row tiles of 16 that hold the R = (H / Hkv) x Nq query rows of a K / V head.  S, the KV ranges per (batch, K / V
-// head), is decided from (B x Hkv, ceil(Ncap / 64), rule_cus, "attn_decode_split") and NEVER from kv_len, which only the kernel reads: the smallest S
-// that gives every CU a workgroup, with at least 4 tiles of Ncap per range, at most 64; the knob forces 1 .. 64 (ranges may then be empty).
-// A paged call (lc_attn_decode_paged_f16; attn_decode_paged.hip) is the same decision with Ncap = max_pages x page_size: page_size > 0 names and
-// launches attn_decode_paged_kernel<D, RT>; RT, S and the workspace bytes are those of the contiguous call of that Ncap.
-// An fp8-cache call (lc_attn_decode_paged_kv8; attn_decode_paged_kv8.hip) is the paged decision again: kv8 names and launches
-// attn_decode_paged_kv8_kernel<D, RT> on e4m3 pools and decides nothing else.
-struct DecodePlan {
-  int B, H, Hkv, Nq, Ncap, D;
-  bool causal;
-  int RT, S;
-  int page_size, num_pages, max_pages;   // 0: a contiguous [B,Hkv,Ncap,D] cache
-  bool kv8;                              // paged only: the pools hold e4m3 bytes
+// What a caller of a decode-attention entry states (lc_attn_decode_f16 / _paged_f16 / _paged_kv8 and the two query calls of each): the ONE place that
+// says whether the cache is paged and how wide its elements are; the plan keeps it, as AttnPlan keeps its AttnCall.
+struct DecodeCall {
+  int B, H, Hkv, Nq, D, flags;
+  int kv_bytes;                          // bytes of a cache element: 2 (fp16) or 1 (e4m3; paged only)
+  bool paged;                            // false: a contiguous [B,Hkv,Ncap,D] cache; true: pools [num_pages,Hkv,page_size,D] + a block table
+  int Ncap;                              // contiguous only
+  int num_pages, page_size, max_pages;   // paged only (the query calls state num_pages = 1: it decides nothing)
 };
-int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p);   // checked arguments
+enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
+// ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
+// checks and plans it, launch_attn_decode launches the plan, format_attn_decode names it.  The plan: attn_decode_kernel<D, RT> (FLAT),
+// attn_decode_paged_kernel<D, RT> (PAGED) or attn_decode_paged_kv8_kernel<D, RT> (PAGED_KV8: e4m3 pools) on B x Hkv x S workgroups, S > 1 followed by
+// attn_decode_combine_kernel<D>.  RT = row tiles of 16 that hold the R = (H / Hkv) x Nq query rows of a K / V head.  S, the KV ranges per (batch,
+// K / V head), is decided from (B x Hkv, ceil(Ncap / 64), rule_cus, "attn_decode_split") and NEVER from kv_len, which only the kernel reads: the
+// smallest S that gives every CU a workgroup, with at least 4 tiles of Ncap per range, at most 64; the knob forces 1 .. 64 (ranges may then be
+// empty).  The cache kind decides the kernel and nothing else: RT, S and the workspace bytes of a paged call are those of the contiguous call of
+// Ncap = max_pages x page_size.
+struct DecodePlan {
+  DecodeCall call;     // what was planned
+  DecodeCache cache;
+  int Ncap, RT, S;     // Ncap: the call's, or max_pages x page_size
+};
+struct DecodePtrs {
+  const half_t* Q;
+  const void *K, *V;   // the cache or the pools; each unit casts once to the element type of its own kernel
+  half_t* O;
+  const int* kv_len;   // device int32[B]; FLAT: or nullptr
+  hipStream_t st;
+  const int* block_table;           // paged: device int32[B, max_pages]; else nullptr
+  const float *k_scale, *v_scale;   // PAGED_KV8: device float[Hkv] or nullptr = 1.0; else nullptr
+};
+// The checks of the three decode entry points, in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's
+// pointers (nullptr: a query call, which has none)
+int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p);
+int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p);   // checked arguments; nothing writes into a plan afterwards
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel)
 // bytes of fp32 partials a plan with S > 1 needs: S x B H Nq rows x (D + 1) floats; 0 for S = 1
 inline size_t decode_workspace_bytes(const DecodePlan& p) {
-  return p.S > 1 ? (size_t)p.S * ((size_t)p.B * p.H * p.Nq) * (size_t)(p.D + 1) * sizeof(float) : 0;
+  return p.S > 1 ? (size_t)p.S * ((size_t)p.call.B * p.call.H * p.call.Nq) * (size_t)(p.call.D + 1) * sizeof(float) : 0;
 }
-struct DecodePtrs {
-  const half_t *Q, *K, *V;
-  half_t* O;
-  const int* kv_len;   // device int32[B] or nullptr
-  hipStream_t st;
-  const int* block_table;   // paged: device int32[B, max_pages] (K, V: the pools); else nullptr
-  const float *k_scale, *v_scale;   // kv8 (K, V: the e4m3 pools' bytes): device float[Hkv] or nullptr = 1.0; else nullptr
-};
 int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace);   // tu_attn_decode.hip
-// the S range workgroups of a paged plan (tu_attn_decode_paged.hip; launch_attn_decode calls it and owns S, the partials and the combine)
-int launch_attn_decode_paged_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
-// the same of a kv8 plan (tu_attn_decode_paged_kv8.hip)
-int launch_attn_decode_paged_kv8_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+// the S range workgroups of a plan of cache kind C: tu_attn_decode_impl.h, instantiated once per kind in the unit that compiles that kind's kernels
+template <DecodeCache C>
+int launch_attn_decode_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 }  // namespace lc

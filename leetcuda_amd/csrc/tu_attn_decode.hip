@@ -1,43 +1,41 @@
-// tu_attn_decode.hip — translation unit of the decode attention kernels (attn_decode.hip: attn_decode_kernel<D, RT>, attn_decode_combine_kernel<D>)
-// and the launcher of a DecodePlan (lc_plan.h).  lc_attn_decode_f16 / lc_attn_decode_paged_f16 (lc_abi.hip) check and plan; this unit launches — see
-// lc_launch.h.  A plan with page_size > 0 runs attn_decode_paged_kernel<D, RT> (tu_attn_decode_paged.hip) in place of attn_decode_kernel<D, RT>,
-// one with kv8 set attn_decode_paged_kv8_kernel<D, RT> (tu_attn_decode_paged_kv8.hip)
+// tu_attn_decode.hip — translation unit of the contiguous decode kernels (attn_decode.hip: attn_decode_kernel<D, RT>, attn_decode_combine_kernel<D>)
+// and THE launcher of every DecodePlan (lc_plan.h): the three decode families of lc_abi.hip state a DecodeCall, check_attn_decode (tu_plan.hip)
+// checks and plans it, launch_attn_decode below owns S, the partials and the combine kernel and reaches the S range workgroups of the plan's cache
+// kind through launch_attn_decode_ranges<kind> — tu_attn_decode_impl.h, instantiated here for DecodeCache::FLAT and in tu_attn_decode_paged.hip /
+// tu_attn_decode_paged_kv8.hip for the other two, each next to its own kernels.
+#include <tuple>
+
 #include "attn_decode.hip"
 #include "lc_plan.h"
+
+#define DECODE_KERNEL attn_decode_kernel
+#define DECODE_CACHE DecodeCache::FLAT
+#define DECODE_KV_T half_t
+namespace lc {
+namespace {
+auto decode_mid(const DecodePtrs&) { return std::make_tuple(); }
+auto decode_tail(const DecodeCall&) { return std::make_tuple(); }
+}  // namespace
+}  // namespace lc
+#include "tu_attn_decode_impl.h"
 
 namespace lc {
 namespace {
 
-template <int D, int RT>
-int launch_decode_rt(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
-  const long rows = (long)p.B * p.H * p.Nq;
-  const int grid = p.B * p.Hkv * S;
-  return launch_attn_kernel(attn_decode_kernel<D, RT>, dim3(grid), dim3(256), DecodeLds<D, RT>::kTotal, a.st, a.Q, a.K, a.V, a.O, a.kv_len, part_o,
-                            part_lse, p.H, p.Hkv, p.Nq, p.Ncap, p.causal ? 1 : 0, S, attn_scale_log2e(D), rows);
-}
+using DecodeRanges = int (*)(const DecodePlan&, int, const DecodePtrs&, float*, float*);
+constexpr DecodeRanges kDecodeRanges[] = {launch_attn_decode_ranges<DecodeCache::FLAT>, launch_attn_decode_ranges<DecodeCache::PAGED>,
+                                          launch_attn_decode_ranges<DecodeCache::PAGED_KV8>};   // by DecodeCache
 
 template <int D>
-int launch_decode_d(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
-  int rc;
-  if (p.kv8) rc = launch_attn_decode_paged_kv8_ranges(p, S, a, part_o, part_lse);   // (tu_attn_decode_paged_kv8.hip)
-  else if (p.page_size > 0) rc = launch_attn_decode_paged_ranges(p, S, a, part_o, part_lse);   // (tu_attn_decode_paged.hip; the combine below is shared)
-  else
-    switch (p.RT) {
-      case 1: rc = launch_decode_rt<D, 1>(p, S, a, part_o, part_lse); break;
-      case 2: rc = launch_decode_rt<D, 2>(p, S, a, part_o, part_lse); break;
-      case 4: rc = launch_decode_rt<D, 4>(p, S, a, part_o, part_lse); break;
-      default: return LC_ERR_SHAPE;
-    }
-  if (rc != LC_OK || S == 1) return rc;
-  const long rows = (long)p.B * p.H * p.Nq;
+int launch_decode_combine(long rows, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
   constexpr int rows_per_block = 256 / (D / 4);
-  return launch_attn_kernel(attn_decode_combine_kernel<D>, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, a.st,
-                            (const float*)part_o, (const float*)part_lse, a.O, rows, S);
+  return launch_attn_kernel(attn_decode_combine_kernel<D>, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, a.st, part_o,
+                            part_lse, a.O, rows, S);
 }
 
 }  // namespace
 
-// The plan's launch; S > 1 needs decode_workspace_bytes(p) bytes: the caller's buffer (checked by lc_attn_decode_f16), else the stream's cached
+// The plan's launch; S > 1 needs decode_workspace_bytes(p) bytes: the caller's buffer (checked by the entry point), else the stream's cached
 // workspace; a stream that is being captured without a caller buffer and a failed lease run S = 1 (lc_plan.h: "a launch differs from its plan")
 int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace) {
   int S = p.S;
@@ -50,10 +48,12 @@ int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace
     }
     if (!part) S = 1;
   }
-  const long rows = (long)p.B * p.H * p.Nq;
+  const long rows = (long)p.call.B * p.call.H * p.call.Nq;
   float* part_o = S > 1 ? part : nullptr;
-  float* part_lse = S > 1 ? part + (size_t)S * rows * p.D : nullptr;
-  return p.D == 128 ? launch_decode_d<128>(p, S, a, part_o, part_lse) : launch_decode_d<64>(p, S, a, part_o, part_lse);
+  float* part_lse = S > 1 ? part + (size_t)S * rows * p.call.D : nullptr;
+  const int rc = kDecodeRanges[(int)p.cache](p, S, a, part_o, part_lse);
+  if (rc != LC_OK || S == 1) return rc;
+  return p.call.D == 128 ? launch_decode_combine<128>(rows, S, a, part_o, part_lse) : launch_decode_combine<64>(rows, S, a, part_o, part_lse);
 }
 
 }  // namespace lc

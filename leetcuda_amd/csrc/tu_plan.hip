@@ -683,29 +683,52 @@ int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p) {
   return LC_OK;
 }
 
-// The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).
-// Decode attention (attn_decode.hip).  The auto rule: a workgroup streams its range at a rate that does not depend on the grid, so the call is as
+// Decode attention (lc_plan.h DecodeCall / DecodePlan).  The auto rule: a workgroup streams its range at a rate that does not depend on the grid, so the call is as
 // fast as its longest range once every CU has a workgroup — the smallest S with B Hkv S >= CUs — and a range shorter than 4 tiles (one per wave) leaves
 // waves without work while the combine still reads S partials.
-int plan_attn_decode(const Knobs& k, int B, int H, int Hkv, int Nq, int Ncap, int D, bool causal, DecodePlan* p) {
-  const int R = (H / Hkv) * Nq;
-  *p = DecodePlan{B, H, Hkv, Nq, Ncap, D, causal, R <= 16 ? 1 : R <= 32 ? 2 : 4, 1, 0, 0, 0, false};
-  if (k.attn_decode_split > 0) {
-    p->S = k.attn_decode_split;
-    return LC_OK;
-  }
-  const long groups = (long)B * Hkv, tiles = ((long)Ncap + 63) / 64;
+int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
+  const int R = (c.H / c.Hkv) * c.Nq;
+  p->call = c;
+  p->cache = !c.paged ? DecodeCache::FLAT : c.kv_bytes == 1 ? DecodeCache::PAGED_KV8 : DecodeCache::PAGED;
+  p->Ncap = c.paged ? c.max_pages * c.page_size : c.Ncap;
+  p->RT = R <= 16 ? 1 : R <= 32 ? 2 : 4;
+  p->S = k.attn_decode_split;
+  if (p->S > 0) return LC_OK;
+  const long groups = (long)c.B * c.Hkv, tiles = ((long)p->Ncap + 63) / 64;
   long S = (rule_cus(k) + groups - 1) / groups;
   S = std::min(S, tiles / 4);
   p->S = (int)std::max(1L, std::min(S, 64L));
   return LC_OK;
 }
+int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
+  auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
+  if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
+  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
+  if (c.H <= 0 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return LC_ERR_SHAPE;
+  if (c.B <= 0 || c.Nq <= 0 || c.D <= 0) return LC_ERR_SHAPE;
+  long ncap = c.Ncap;
+  if (c.paged) {
+    if (c.num_pages <= 0 || c.max_pages <= 0) return LC_ERR_SHAPE;
+    if (c.page_size < 16 || (c.page_size & (c.page_size - 1)) != 0) return LC_ERR_SHAPE;   // a power of two >= 16: a 16-key load group never straddles a page
+    ncap = (long)c.max_pages * c.page_size;
+    if (ncap > 0x7fffffffL) return LC_ERR_SHAPE;
+  } else if (ncap <= 0) return LC_ERR_SHAPE;
+  if ((long)(c.H / c.Hkv) * c.Nq > 64) return LC_ERR_SHAPE;   // R = G x Nq query rows per K / V head: four row tiles of 16 (no chunked prefill against a cache)
+  // one head's Ncap rows (an upper bound of one page run) stay below 2 GiB: the kernel's 32-bit offsets (attn_span_fits at kv_bytes an element)
+  if ((size_t)ncap * (size_t)c.D * (size_t)c.kv_bytes >= 0x80000000ull) return LC_ERR_SHAPE;
+  if ((size_t)c.B * c.Hkv * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x Hkv x S workgroups, S <= 64
+  if (a && (!aligned16(a->Q) || !aligned16(a->K) || !aligned16(a->V) || !aligned16(a->O))) return LC_ERR_SHAPE;
+  if (c.D != 64 && c.D != 128) return LC_ERR_HEADDIM;
+  return plan_attn_decode(read_knobs(), c, p);
+}
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
-  const char* kern = p.kv8 ? "attn_decode_paged_kv8_kernel" : p.page_size > 0 ? "attn_decode_paged_kernel" : "attn_decode_kernel";
-  if (p.S > 1) snprintf(buf, buflen, "%s<%d,%d> x%d", kern, p.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)
-  else snprintf(buf, buflen, "%s<%d,%d>", kern, p.D, p.RT);
+  static const char* const kKernels[] = {"attn_decode_kernel", "attn_decode_paged_kernel", "attn_decode_paged_kv8_kernel"};   // by DecodeCache
+  const char* kern = kKernels[(int)p.cache];
+  if (p.S > 1) snprintf(buf, buflen, "%s<%d,%d> x%d", kern, p.call.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)
+  else snprintf(buf, buflen, "%s<%d,%d>", kern, p.call.D, p.RT);
 }
 
+// The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).
 void format_attn(const AttnPlan& p, char* buf, int buflen) {
   const int D = p.call.D;
   const bool v_transposed = p.call.vt;

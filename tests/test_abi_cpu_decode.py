@@ -4,10 +4,9 @@ workspace size of the named plan, the audit report of the new kernels — and a 
 tests/test_gpu_decode.py a mask one key too long or too short, top-left alignment, an ignored kv_len, the head map `h % Hkv` and "every batch
 reads batch 0" each leave the bound by >= 20 x on EVERY row they touch.
 
-This module also holds what both files share: the inputs, the visible-key count of a row and the oracle truth of a decode call
-(Oracle.attn_rows once per distinct count of a batch entry, on K / V expanded to H heads)."""
+The inputs, the visible-key count of a row and the oracle truth of a decode call (Oracle.attn_rows once per distinct count of a batch entry, on
+K / V expanded to H heads) are shared with that file: tests/decode_lib.py."""
 import ctypes as C
-import functools
 import json
 
 import numpy as np
@@ -15,152 +14,15 @@ import pytest
 import torch
 
 from leetcuda_amd import capi
-from tests import tol
-
-NCAP = 1000
-GRID_SHAPES = [(3, 8, 2), (2, 4, 1), (2, 4, 4)]                     # (B, H, Hkv)
-GRID_LENS = {3: (NCAP, 129, 65), 2: (65, NCAP)}                      # per-batch kv_len of the grid test, by B (B = 2 with Hkv = 4: reversed)
-GRID_NQ = (1, 4, 5, 16)
-SCORE = 12.0      # natural units: the dominant key of a pinned row (the construction of tests/test_gpu_causal_mask.py)
-TEETH = 20.0
-PIN_SHAPE = (3, 8, 2)
-PIN_NQ = 5
-PIN_LENS = (777, 129, 65)       # all < NCAP: position L_b exists, so "the first invisible key" does for every row
-PLACES = ("last", "first_invisible", "key0", "tile_seam", "range_seam")
-
-
-def decode_inputs(B, H, Hkv, Nq, Ncap, D, seed):
-    """fp16 randn q [B,H,Nq,D], k, v [B,Hkv,Ncap,D] on the CPU (the GPU tests move them over: both files test the same inputs)"""
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(B, H, Nq, D, generator=g).half(), torch.randn(B, Hkv, Ncap, D, generator=g).half(),
-            torch.randn(B, Hkv, Ncap, D, generator=g).half())
-
-
-def visible(L, Nq, Ncap, causal, i):
-    """number of keys query i of a batch entry with kv_len L sees: keys 0 .. visible - 1 (lc_abi.h: bottom-right aligned)"""
-    L = min(max(int(L), 0), Ncap)
-    return max(0, L - Nq + i + 1) if causal else L
-
-
-def rt_of(H, Hkv, Nq):
-    R = (H // Hkv) * Nq
-    return 1 if R <= 16 else 2 if R <= 32 else 4
-
-
-def decode_truth(oracle, q, k, v, lens, causal, nk_of=None, kv_head=None, kv_batch=None):
-    """(truth fp32 [B,H,Nq,D], nk int [B,Nq]): the oracle on every row.  lens: per-batch kv_len (None: Ncap).  The keyword arguments restate a
-    WRONG kernel for the tests of the inputs: nk_of(b, i) -> visible keys, kv_head(h) -> K / V head, kv_batch(b) -> batch entry read."""
-    B, H, Nq, D = q.shape
-    Hkv, Ncap = k.shape[1], k.shape[2]
-    G = H // Hkv
-    heads = [kv_head(h) if kv_head else h // G for h in range(H)]
-    truth = np.zeros((B, H, Nq, D), np.float32)
-    nks = np.zeros((B, Nq), np.int64)
-    for b in range(B):
-        L = Ncap if lens is None else lens[b]
-        for i in range(Nq):
-            nks[b, i] = nk_of(b, i) if nk_of else visible(L, Nq, Ncap, causal, i)
-        bb = kv_batch(b) if kv_batch else b
-        kb, vb = k[bb][heads], v[bb][heads]                     # [H, Ncap, D]: expanded to the query heads
-        for nk in sorted(set(int(x) for x in nks[b])):
-            rows = [i for i in range(Nq) if nks[b, i] == nk]
-            if nk == 0:
-                continue                                        # no visible key: exactly 0
-            o = oracle.attn_rows(q[b][:, rows].contiguous(), kb[:, :nk].contiguous(), vb[:, :nk].contiguous(), H, len(rows), nk, D)
-            truth[b][:, rows] = o
-    return truth, nks
-
-
-def check_decode(out, truth, nks, what=""):
-    """every row under tol.attn_close with N = the row's visible keys; rows without a visible key are exactly 0.  Returns the worst
-    |err| / bound (for the docstrings)."""
-    out = np.asarray(out, np.float32)
-    worst = 0.0
-    B, H, Nq, D = truth.shape
-    for b in range(B):
-        for i in range(Nq):
-            nk = int(nks[b, i])
-            o, t = out[b, :, i], truth[b, :, i]
-            if nk == 0:
-                assert (o == 0).all(), (what, "row without a visible key is not 0", b, i, float(np.abs(o).max()))
-                continue
-            assert np.isfinite(o).all(), (what, "non-finite", b, i)
-            ok, err, excess = tol.attn_close(o, t, N=nk)
-            bound = tol.attn_max_abs(nk) + tol.ATTN_RTOL_F16 * np.abs(t.astype(np.float64))
-            worst = max(worst, float((np.abs(o.astype(np.float64) - t) / bound).max()))
-            assert ok, (what, f"batch {b} query {i} nk {nk}: max |err| {err:.3e}, excess over the bound {excess:.3e}")
-    return worst
-
-
-def pin_target(place, L, Nq, Ncap, causal, r, split):
-    """the key that scores SCORE for row r = g Nq + i of a K / V head (None: the row keeps a random query)"""
-    i = r % Nq
-    lim = visible(L, Nq, Ncap, causal, i)
-    if place == "last":
-        return lim - 1 if lim >= 1 else None
-    if place == "first_invisible":
-        return lim if lim < Ncap else None
-    if place == "key0":
-        return 0 if lim >= 1 else None
-    if place == "tile_seam":                        # either side of the last tile seam below the row's limit
-        p = 64 * ((lim - 1) // 64) if lim >= 1 else 0
-        if p == 0:
-            return None
-        return p - 1 if r % 2 == 0 else p
-    if place == "range_seam":                       # either side of a seam between two KV ranges of the kernel's partition (split ranges)
-        T = (L + 63) // 64
-        seams = sorted({64 * (s * T // split) for s in range(1, split)} - {0})
-        seams = [p for p in seams if p < lim]
-        if not seams:
-            return None
-        p = seams[(r // 2) % len(seams)]
-        return p - 1 if r % 2 == 0 else p
-    raise KeyError(place)
-
-
-@functools.lru_cache(maxsize=16)
-def pinned_inputs(D, place, causal, split=3):
-    """(q, k, v, lens): per row ONE key outweighs the rest — K random +-1, Q_row = (SCORE / sqrt(D)) K[target], V randn; the target of
-    `first_invisible` carries a large distinctive V row (+-8).  Rows without a target (no visible key, no seam below the limit) keep randn."""
-    B, H, Hkv = PIN_SHAPE
-    Nq, G = PIN_NQ, PIN_SHAPE[1] // PIN_SHAPE[2]
-    g = torch.Generator().manual_seed(7919 * D + 31 * PLACES.index(place) + int(causal))
-    k = (torch.randint(0, 2, (B, Hkv, NCAP, D), generator=g) * 2 - 1).float()
-    v = torch.randn(B, Hkv, NCAP, D, generator=g)
-    q = torch.randn(B, H, Nq, D, generator=g)
-    big = torch.tensor([8.0, -8.0]).repeat(D // 2)
-    for b in range(B):
-        for h in range(H):
-            kvh, gq = h // G, h % G
-            for i in range(Nq):
-                t = pin_target(place, PIN_LENS[b], Nq, NCAP, causal, gq * Nq + i, split)
-                if t is None:
-                    continue
-                q[b, h, i] = (SCORE / D ** 0.5) * k[b, kvh, t]
-                if place == "first_invisible":
-                    v[b, kvh, t] = big
-    return q.half(), k.half(), v.half(), PIN_LENS
-
+from tests.decode_lib import NCAP_RAGGED as NCAP
+from tests.decode_lib import (PIN_LENS, PIN_NQ, PIN_SHAPE, PLACES, SCORE, TEETH, _moved, auto_split, decode_inputs, decode_truth, pin_target,
+                              pinned_inputs, reset_knobs, rt_of, visible)
+from tests.decode_lib import name_flat as _name
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _name(B, H, Hkv, Nq, Ncap, D, flags=0):
-    buf = C.create_string_buffer(128)
-    rc = capi.load().lc_attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, flags, buf, 128)
-    return rc, buf.value.decode()
-
-
-def auto_split(groups, ncap, cus):
-    """the documented rule, restated: the smallest S that gives every CU a workgroup, >= 4 tiles of Ncap per range, <= 64"""
-    tiles = (ncap + 63) // 64
-    return max(1, min(-(-cus // groups), tiles // 4, 64))
-
-
 @pytest.fixture
 def knobs(built):
-    capi.load()
-    yield
-    capi.tune("attn_decode_split", 0)
-    capi.tune("rule_cus", 0)
+    yield from reset_knobs()
 
 
 def test_decode_errors_and_their_order(built):
@@ -288,13 +150,6 @@ def test_audit_knows_the_decode_kernels_and_reports_no_scratch(built):
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # a test of the GPU tests' inputs
-
-def _moved(truth, nks, wrong):
-    """[B, H, Nq]: largest |wrong - truth| / bound over a row's columns, the bound being that of the row's visible keys"""
-    atol = np.array([[tol.attn_max_abs(int(n)) for n in row] for row in nks]).reshape(nks.shape[0], 1, nks.shape[1], 1)
-    bound = atol + tol.ATTN_RTOL_F16 * np.abs(truth.astype(np.float64))
-    return (np.abs(wrong.astype(np.float64) - truth) / bound).max(axis=-1)
-
 
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
 @pytest.mark.parametrize("D", [64, 128])

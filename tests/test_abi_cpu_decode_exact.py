@@ -1,10 +1,11 @@
-"""Inputs, truths, bounds, fault locator and teeth tests of tests/test_gpu_decode_exact.py: decode attention (attn_decode_kernel<D,RT>,
+"""The teeth tests of the inputs of tests/test_gpu_decode_exact.py; the inputs, truths, bounds and the fault locator themselves, which this
+docstring describes, are in tests/decode_lib.py (there pinned_inputs, PIN_LENS and PLACES carry the prefix exact_ / EXACT_).  Decode attention (attn_decode_kernel<D,RT>,
 attn_decode_combine_kernel<D> and attn_decode_paged_kernel<D,RT>) on inputs whose answer is exact, pinned to one key or moved by a score
 step.  No call here reaches a device.  Ncap = 1024, D in {64, 128}; one launch carries one batch entry per length; every (batch entry, K / V
 head) pair has its own seed, so a head or batch slip cannot cancel.  Row r = g Nq + i of a K / V head is query head kvh G + g, token i.
 
 Truths are fp64 torch straight from the definition (bottom-right aligned mask: token i of entry b sees keys 0 .. L_b - Nq + i; head map
-h // G; zeros for a row without a visible key), anchored to the project's oracle (test_abi_cpu_decode.decode_truth) on a handful of rows per
+h // G; zeros for a row without a visible key), anchored to the project's oracle (decode_lib.decode_truth) on a handful of rows per
 class to 1e-6.  Three input classes, each blind where another sees:
 
   uniform   even K / V heads: Q = 0, K random +-1; odd K / V heads: Q random +-1, K = 0.  Every score is exactly 0, every visible key has
@@ -18,10 +19,10 @@ class to 1e-6.  Three input classes, each blind where another sees:
                       most ~2^-18 relative (lse <= 10, 8 ulps of it are 2^-19 absolute, as much again for exp2) and the combine's error is
                       below 2^-18 max|v| = 2^-17; the floor of ulp16(2^-6) = 2^-16 covers it beside the output's rounding.
             A key counted 0 or 2 times moves a column by |v - E| / (nk -+ 1).  Cannot see: which key carries which weight, a wrong rescale.
-  pinned    test_abi_cpu_decode.pinned_inputs' construction for any (H, Hkv, Nq) and any lengths: K random +-1, Q_row = (12 / sqrt(D)) K[target],
+  pinned    decode_lib.pinned_inputs' construction for any (H, Hkv, Nq) and any lengths: K random +-1, Q_row = (12 / sqrt(D)) K[target],
             V randn; key `target` scores 12 for its row and every other key at most 12 |cos| <= 12.  Places (pin_target, unchanged): last,
             first_invisible (its target t carries the V row 8 K[t]: +-8 with the key's own signs — with one fixed +-8 pattern, as in
-            test_abi_cpu_decode.py, token i + 1 sees the target of token i under the causal mask, at Nq = 64 nearly every visible V row is
+            decode_lib.pinned_inputs, token i + 1 sees the target of token i under the causal mask, at Nq = 64 nearly every visible V row is
             that pattern and the row sits on it before the mask is wrong), key0, tile_seam, range_seam — and step_seam: key 64 t + 31 for even r, 64 t + 32
             for odd r, t the last tile that holds both below the row's limit: the seam between the two 32-key pipeline steps of
             attn_decode_kernel<128,4>, the only instantiation with STEP = 32.  Rows without a target keep randn.  Bound: check_decode.
@@ -56,388 +57,21 @@ The fault locator names kernel, batch entry, K / V head, group member g, token i
 closest one-fault hypothesis (the mean recomputed under: limit one key short / long, the limit of token i +- 1, a key block of 16 / 32 / 64
 dropped / doubled, a wave's tiles dropped, a range dropped / doubled, K / V head h % Hkv, batch 0); a CPU test feeds it each injected fault.
 """
-import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from tests import tol
-from tests.test_abi_cpu_decode import SCORE, TEETH, decode_truth, pin_target, rt_of, visible
-from tests.test_abi_cpu_decode_paged import gather, paginate
-from tests.test_gpu_attn_exact import STEP_C, V8, V16, _draw, _pm1, round_once, ulp
-
-NCAP = 1024
-DS = (64, 128)
-LENS = (1024, 1000, 577, 130, 65, 64, 33, 32, 31, 16, 1, 0)
-GRID = ((2, 2, 1), (8, 1, 1), (6, 2, 5), (2, 2, 17), (8, 2, 8), (6, 2, 11), (8, 2, 9), (6, 1, 8), (7, 1, 9), (2, 2, 64))      # (H, Hkv, Nq)
-ROW_SHAPES = ((8, 1, 1), (2, 2, 17), (8, 2, 9), (7, 1, 9), (2, 2, 64))                # R, RT = (8, 1), (17, 2), (36, 4), (63, 4), (64, 4)
-PIN_LENS = (1000, 577, 130, 65, 33)
-STEP_LENS = (1024, 1000, 577, 130)
-PLACES = ("last", "first_invisible", "key0", "tile_seam", "step_seam", "range_seam")
-UNIFORM_SPLITS = (1, 2, 3, 8, 16, 64)
-PINNED_SPLITS = (1, 3, 8)
-STEP_SPLITS = (1, 2, 4, 8)
-BLOCK_LENS = (1024, 1000, 577, 130)
-PAGED_SHAPES = ((8, 1, 1), (8, 2, 9))                                                 # RT = 1 and RT = 4
-PAGE_SIZES = (16, 64)
-FLOOR = 2.0 ** -6
-
-
-def ulp16(x):
-    return ulp(x, False)
-
-
-def step_of(D, H, Hkv, Nq):
-    """keys per pipeline step of attn_decode_kernel<D, RT>"""
-    return 32 if (D == 128 and rt_of(H, Hkv, Nq) == 4) else 64
-
-
-def nk_table(lens, Nq, causal):
-    """int64 [B, Nq]: visible keys of token i of batch entry b"""
-    return np.array([[visible(L, Nq, NCAP, causal, i) for i in range(Nq)] for L in lens], np.int64)
-
-
-def _seed(cls, D, H, Hkv, Nq, b, kvh, extra=0):
-    return ((((("uniform", "pinned", "step").index(cls) * 7 + D // 64) * 131 + H) * 17 + Hkv) * 67 + Nq) * 4099 + 61 * b + kvh + 1000003 * extra
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# the truth of any input: fp64 torch from the definition
-
-def weights64(q, k, lens, causal):
-    """(p [B,H,Nq,Ncap] fp64: exp(score - row max) on the visible keys, 0 elsewhere; nks [B,Nq])"""
-    B, H, Nq, D = q.shape
-    G = H // k.shape[1]
-    nks = nk_table(lens, Nq, causal)
-    heads = torch.arange(H) // G
-    s = q.double() @ k.double()[:, heads].transpose(-2, -1) / D ** 0.5                       # [B, H, Nq, Ncap]
-    vis = torch.arange(NCAP).view(1, 1, 1, NCAP) < torch.from_numpy(nks).view(B, 1, Nq, 1)
-    s = s.masked_fill(~vis, -float("inf"))
-    mx = s.max(dim=-1, keepdim=True).values
-    p = torch.exp(s - torch.where(torch.isinf(mx), torch.zeros_like(mx), mx))
-    return p, nks
-
-
-def attend64(p, v, H):
-    """[B,H,Nq,D] fp64 numpy: rows of p normalised against V; a row whose weights are all 0 is zeros"""
-    G = H // v.shape[1]
-    l = p.sum(-1, keepdim=True)
-    w = torch.where(l > 0, p / l.clamp(min=1e-300), torch.zeros_like(p))
-    return (w @ v.double()[:, torch.arange(H) // G]).numpy()
-
-
-def truth64(q, k, v, lens, causal):
-    p, nks = weights64(q, k, lens, causal)
-    return attend64(p, v, q.shape[1]), nks
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# uniform
-
-@functools.lru_cache(maxsize=4)
-def uniform_inputs(D, H, Hkv, Nq):
-    """(q [B,H,Nq,D], k, v [B,Hkv,Ncap,D]) fp16 on the CPU, B = len(LENS); the same tensors serve causal and non-causal launches"""
-    B, G = len(LENS), H // Hkv
-    q = torch.zeros(B, H, Nq, D)
-    k = torch.zeros(B, Hkv, NCAP, D)
-    v = torch.zeros(B, Hkv, NCAP, D)
-    for b in range(B):
-        for kvh in range(Hkv):
-            g = torch.Generator().manual_seed(_seed("uniform", D, H, Hkv, Nq, b, kvh))
-            v[b, kvh] = _draw(g, V16, (NCAP, D))
-            if kvh % 2 == 0:
-                k[b, kvh] = _pm1(g, (NCAP, D))
-            else:
-                q[b, kvh * G:(kvh + 1) * G] = _pm1(g, (G, Nq, D))
-    return q.half(), k.half(), v.half()
-
-
-def prefix_sums(v):
-    """fp64 numpy [B,Hkv,Ncap+1,D]: P[n] = the sum of V[0 : n] (exact)"""
-    c = v.double().cumsum(dim=2)
-    return torch.cat([torch.zeros_like(c[:, :, :1]), c], dim=2).numpy()
-
-
-def uniform_means(P, nks, H):
-    """E [B,H,Nq,D]: the mean of V[0 : nk] of the row's K / V head, zeros where nk = 0"""
-    B, Hkv = P.shape[:2]
-    G = H // Hkv
-    n = np.clip(nks, 0, NCAP)
-    sums = P[np.arange(B)[:, None, None], (np.arange(H) // G)[None, :, None], n[:, None, :]]       # [B, H, Nq, D]
-    return sums / np.maximum(n, 1)[:, None, :, None]
-
-
-@functools.lru_cache(maxsize=4)
-def uniform_truth(D, H, Hkv, Nq, causal):
-    """(E [B,H,Nq,D], nks [B,Nq], prefix sums) of a launch over LENS; shared, never written to"""
-    P = prefix_sums(uniform_inputs(D, H, Hkv, Nq)[2])
-    nks = nk_table(LENS, Nq, causal)
-    return uniform_means(P, nks, H), nks, P
-
-
-def uniform_bound(E, split):
-    return ulp16(E) if split == 1 else ulp16(np.maximum(np.abs(E), FLOOR))
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# pinned
-
-def target_of(place, L, Nq, causal, r, split):
-    if place != "step_seam":
-        return pin_target(place, L, Nq, NCAP, causal, r, split)
-    lim = visible(L, Nq, NCAP, causal, r % Nq)
-    if lim < 33:
-        return None                                     # no tile holds keys 31 and 32 of it below the limit
-    t = (lim - 33) // 64
-    return 64 * t + (31 if r % 2 == 0 else 32)
-
-
-@functools.lru_cache(maxsize=4)
-def pinned_inputs(D, place, causal, H, Hkv, Nq, split=3, lens=PIN_LENS):
-    """(q, k, v, targets): fp16 CPU tensors and targets[b][h][i] (None: the row keeps its random query)"""
-    B, G = len(lens), H // Hkv
-    q = torch.empty(B, H, Nq, D)
-    k = torch.empty(B, Hkv, NCAP, D)
-    v = torch.empty(B, Hkv, NCAP, D)
-    targets = [[[None] * Nq for _ in range(H)] for _ in range(B)]
-    for b in range(B):
-        for kvh in range(Hkv):
-            g = torch.Generator().manual_seed(_seed("pinned", D, H, Hkv, Nq, b, kvh, 1 + 2 * PLACES.index(place) + int(causal)))
-            k[b, kvh] = _pm1(g, (NCAP, D))
-            v[b, kvh] = torch.randn(NCAP, D, generator=g)
-            q[b, kvh * G:(kvh + 1) * G] = torch.randn(G, Nq, D, generator=g)
-            for r in range(G * Nq):
-                t = target_of(place, lens[b], Nq, causal, r, split)
-                if t is None:
-                    continue
-                h, i = kvh * G + r // Nq, r % Nq
-                targets[b][h][i] = t
-                q[b, h, i] = (SCORE / D ** 0.5) * k[b, kvh, t]
-                if place == "first_invisible":
-                    v[b, kvh, t] = 8.0 * k[b, kvh, t]
-    return q.half(), k.half(), v.half(), targets
-
-
-def pinned_split_key(place, split):
-    """the inputs depend on S only where the targets do"""
-    return split if (place == "range_seam" and split > 1) else 3
-
-
-@functools.lru_cache(maxsize=2)
-def pinned_truth(D, place, causal, H, Hkv, Nq, split=3):
-    q, k, v, _ = pinned_inputs(D, place, causal, H, Hkv, Nq, split)
-    return truth64(q, k, v, PIN_LENS, causal)
-
-
-def decode_bound(truth, nks):
-    """check_decode's bound as an array [B,H,Nq,D]"""
-    atol = np.array([[tol.attn_max_abs(int(n)) for n in row] for row in nks])[:, None, :, None]
-    return atol + tol.ATTN_RTOL_F16 * np.abs(truth)
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# step
-
-def step_tile(D, H, Hkv, Nq, b, kvh, L):
-    T = -(-L // 64)
-    hi = max((L - Nq + 1) // 64, 1)                    # the whole window below the smallest causal limit of the entry
-    lo = min(-(-T // 4), hi - 1)
-    g = torch.Generator().manual_seed(_seed("step", D, H, Hkv, Nq, b, kvh, 7))
-    return lo + int(torch.randint(0, hi - lo, (1,), generator=g))
-
-
-@functools.lru_cache(maxsize=4)
-def step_inputs(D, H, Hkv, Nq):
-    """(q, k, v, tiles [B][Hkv]) fp16 on the CPU, B = len(STEP_LENS)"""
-    B, G = len(STEP_LENS), H // Hkv
-    q = torch.empty(B, H, Nq, D)
-    k = torch.zeros(B, Hkv, NCAP, D)
-    v = torch.empty(B, Hkv, NCAP, D)
-    c = torch.tensor(STEP_C)[torch.arange(G * Nq) % 3].view(G, Nq, 1)
-    tiles = []
-    for b, L in enumerate(STEP_LENS):
-        tiles.append([])
-        for kvh in range(Hkv):
-            g = torch.Generator().manual_seed(_seed("step", D, H, Hkv, Nq, b, kvh))
-            v[b, kvh] = _draw(g, V8, (NCAP, D))
-            u, w = _pm1(g, (D,)), _draw(g, V8, (D,))
-            t = step_tile(D, H, Hkv, Nq, b, kvh, L)
-            tiles[-1].append(t)
-            k[b, kvh, 64 * t + 24:64 * t + 64] = u
-            v[b, kvh, 64 * t + 24:64 * t + 64] = w
-            q[b, kvh * G:(kvh + 1) * G] = (c / D ** 0.5) * u
-    return q.half(), k.half(), v.half(), tiles
-
-
-@functools.lru_cache(maxsize=2)
-def step_truth(D, H, Hkv, Nq, causal):
-    q, k, v, _ = step_inputs(D, H, Hkv, Nq)
-    return truth64(q, k, v, STEP_LENS, causal)
-
-
-def step_bound(truth, nks):
-    """tol.attn_close(N = nk, rtol = tol.ATTN_RTOL_SPIKE) as an array"""
-    atol = np.array([[tol.attn_max_abs(int(n)) for n in row] for row in nks])[:, None, :, None]
-    return atol + tol.ATTN_RTOL_SPIKE * np.abs(truth)
-
-
-def emulate_kernel(s, v, lims, L, S, STEP, fault=None):
-    """One (batch entry, K / V head) the way the kernel walks it, in fp64 and natural units: s [R,Ncap] scores, v [Ncap,D], lims [R].
-    fault: None, "alpha_l", "alpha_o", ("mine", w), "combine".  Returns (out [R,D], applies [R]: the dropped factor differed from 1 on
-    something non-zero)."""
-    R, D = s.shape[0], v.shape[1]
-    ninf = -float("inf")
-    s = s.masked_fill(torch.arange(NCAP).view(1, -1) >= lims.view(-1, 1), ninf)
-    T = -(-L // 64)
-    applies = torch.zeros(R, dtype=torch.bool)
-    parts, lses = [], []
-    for si in range(S):
-        t0, t1 = si * T // S, (si + 1) * T // S
-        M = torch.full((4, R), ninf, dtype=torch.float64)
-        Lw = torch.zeros(4, R, dtype=torch.float64)
-        Ow = torch.zeros(4, R, D, dtype=torch.float64)
-        for w in range(4):
-            m, l, o = M[w].clone(), Lw[w].clone(), Ow[w].clone()
-            for t in range(t0 + w, t1, 4):
-                for a in range(64 * t, 64 * t + 64, STEP):
-                    blk = s[:, a:a + STEP]
-                    mn = torch.maximum(m, blk.max(dim=1).values)
-                    mu = torch.where(torch.isinf(mn), torch.zeros_like(mn), mn)
-                    alpha, p = torch.exp(m - mu), torch.exp(blk - mu.view(-1, 1))
-                    if fault in ("alpha_l", "alpha_o"):
-                        applies |= (alpha != 1) & (l > 0)
-                    l = (l if fault == "alpha_l" else l * alpha) + p.sum(dim=1)
-                    o = (o if fault == "alpha_o" else o * alpha.view(-1, 1)) + p @ v[a:a + STEP]
-                    m = mn
-            M[w], Lw[w], Ow[w] = m, l, o
-        mm = M.max(dim=0).values
-        mu = torch.where(torch.isinf(mm), torch.zeros_like(mm), mm)
-        f = torch.exp(M - mu)
-        ls = (Lw * f).sum(dim=0)
-        mine = f.clone()
-        if isinstance(fault, tuple):
-            w = fault[1]
-            whole = torch.zeros(R, dtype=torch.bool)    # `mine` of wave w is judged on the rows that see the wave's first tile of the range whole
-            if t0 + w < t1:
-                whole = (s[:, 64 * (t0 + w):64 * (t0 + w) + 64] > ninf).all(dim=1)
-            hit = whole & (f[w] != 1) & (Lw[w] > 0)
-            mine[w] = torch.where(hit, torch.ones_like(f[w]), f[w])
-            applies |= hit
-        o = (Ow * mine.unsqueeze(-1)).sum(dim=0)
-        inv = torch.where(ls > 0, 1 / ls.clamp(min=1e-300), torch.zeros_like(ls))
-        parts.append(o * inv.view(-1, 1))
-        lses.append(torch.where(ls > 0, mm + torch.log(ls.clamp(min=1e-300)), torch.full_like(ls, ninf)))
-    if S == 1:
-        return parts[0].numpy(), applies.numpy()
-    part, lse = torch.stack(parts), torch.stack(lses)                                   # [S, R, D], [S, R]
-    mx = lse.max(dim=0).values
-    wgt = torch.exp(lse - torch.where(torch.isinf(mx), torch.zeros_like(mx), mx))
-    wgt = torch.where(torch.isinf(lse), torch.zeros_like(wgt), wgt)
-    if fault == "combine":
-        live = ~torch.isinf(lse)
-        n = live.sum(dim=0)
-        off = ((wgt / wgt.sum(dim=0).clamp(min=1e-300) - 1 / n.clamp(min=1)).abs() * live).max(dim=0).values
-        applies |= (n >= 2) & (off >= COMBINE_OFF) & (s.max(dim=1).values > 0)      # (a row that sees no step key is `uniform`'s business)
-        wgt = live.double()
-    ws = wgt.sum(dim=0)
-    out = (part * wgt.unsqueeze(-1)).sum(dim=0) * torch.where(ws > 0, 1 / ws.clamp(min=1e-300), torch.zeros_like(ws)).view(-1, 1)
-    return out.numpy(), applies.numpy()
-
-
-COMBINE_OFF = 1.0 / 16      # "all combine weights equal" is judged on rows where some range's true share of the weight is this far from 1 / ranges
-STEP_FAULTS = ("alpha_l", "alpha_o", ("mine", 0), ("mine", 1), ("mine", 2), ("mine", 3), "combine")
-
-
-# ------------------------------------------------------------------------------------------------------------------------------------
-# the judge and the fault locator
-
-def uniform_hypotheses(P, lens, H, Hkv, Nq, causal, S, b, h, i):
-    """(name, the mean [D] a kernel with that ONE fault would give row (b, h, i)) for every candidate fault"""
-    G = H // Hkv
-    kvh, L = h // G, min(max(int(lens[b]), 0), NCAP)
-    nk = visible(L, Nq, NCAP, causal, i)
-    tot = P[b, kvh, nk]
-
-    def mean(x, n):
-        return x / n if n > 0 else np.zeros_like(x)
-
-    if nk >= 1:
-        yield "limit one key short", mean(P[b, kvh, nk - 1], nk - 1)
-    if nk < NCAP:
-        yield "limit one key long", mean(P[b, kvh, nk + 1], nk + 1)
-    for d in (-1, 1):
-        n2 = min(visible(L, Nq, NCAP, causal, i + d), NCAP)
-        if n2 != nk:
-            yield f"the limit of token {i + d} (wrong r % Nq)", mean(P[b, kvh, n2], n2)
-    for size in (16, 32, 64):
-        for t in range(-(-nk // size)):
-            a, e = size * t, min(size * t + size, nk)
-            seg = P[b, kvh, e] - P[b, kvh, a]
-            yield f"{size}-key block {t} dropped", mean(tot - seg, nk - (e - a))
-            yield f"{size}-key block {t} doubled", mean(tot + seg, nk + (e - a))
-    T = -(-L // 64)
-    for s in range(S):
-        t0, t1 = s * T // S, (s + 1) * T // S
-        a, e = min(64 * t0, nk), min(64 * t1, nk)
-        if S > 1 and e > a:
-            seg = P[b, kvh, e] - P[b, kvh, a]
-            yield f"range {s} of {S} dropped", mean(tot - seg, nk - (e - a))
-            yield f"range {s} of {S} doubled", mean(tot + seg, nk + (e - a))
-        for w in range(4):
-            seg, cnt = np.zeros_like(tot), 0
-            for t in range(t0 + w, t1, 4):
-                a, e = min(64 * t, nk), min(64 * t + 64, nk)
-                seg, cnt = seg + P[b, kvh, e] - P[b, kvh, a], cnt + e - a
-            if cnt:
-                yield f"wave {w}'s tiles dropped" + (f" in range {s} of {S}" if S > 1 else ""), mean(tot - seg, nk - cnt)
-    if h % Hkv != kvh:
-        yield f"K / V head h % Hkv = {h % Hkv}", mean(P[b, h % Hkv, nk], nk)
-    if b != 0:
-        yield "batch entry 0's cache", mean(P[0, kvh, nk], nk)
-
-
-def locate_uniform(row, P, lens, H, Hkv, Nq, causal, S, b, h, i):
-    """(name, residual): the one-fault hypothesis closest to an output row (largest |difference| over its columns)"""
-    best = ("none of the one-fault hypotheses", float("inf"))
-    for name, hyp in uniform_hypotheses(P, lens, H, Hkv, Nq, causal, S, b, h, i):
-        res = float(np.nan_to_num(np.abs(hyp - row), nan=np.inf).max())
-        if res < best[1]:
-            best = (name, res)
-    return best
-
-
-def judge(kernel, cls, out, truth, bound, nks, Hkv, strict=False, hint=None):
-    """out, truth [B,H,Nq,D] fp64 numpy: rows without a visible key exactly 0, every other element finite and inside `bound` (strict: |err|
-    < bound).  Returns the worst |err| / bound; a failure names kernel, batch entry, K / V head, g, token, nk, the share of wrong elements
-    and hint(b, h, i)."""
-    B, H, Nq, D = truth.shape
-    G = H // Hkv
-    zero = np.broadcast_to((nks == 0)[:, None, :, None], truth.shape)
-    finite = np.isfinite(out)
-    err = np.abs(out - truth)
-    with np.errstate(invalid="ignore"):
-        bad = ~finite | ((err >= bound) if strict else (err > bound))
-        ratio = np.where(zero | ~finite, 0.0, err / bound)
-    wrong = np.where(zero, out != 0, bad)
-    if wrong.any():
-        score = np.where(wrong, np.where(zero | ~finite, np.inf, err / bound), -1.0)
-        b, h, i, d = (int(x) for x in np.unravel_index(np.argmax(score), score.shape))
-        msg = (f"{kernel} [{cls}]: batch entry {b}, K / V head {h // G}, g {h % G} (query head {h}), token {i}, nk {int(nks[b, i])}, column {d}: "
-               f"got {out[b, h, i, d]!r}, want {truth[b, h, i, d]!r} (bound {float(np.broadcast_to(bound, truth.shape)[b, h, i, d]):.3e}); wrong: "
-               f"{wrong.mean():.2%} of all elements, {int(wrong.any(axis=-1).sum())} of {B * H * Nq} rows, {wrong[b, h, i].mean():.0%} of this row"
-               + ("; " + hint(b, h, i) if hint else ""))
-        raise AssertionError(msg)
-    return float(ratio.max())
-
-
-def uniform_hint(out, P, lens, H, Hkv, Nq, causal, S):
-    def hint(b, h, i):
-        name, res = locate_uniform(out[b, h, i], P, lens, H, Hkv, Nq, causal, S, b, h, i)
-        return f"closest one-fault hypothesis: {name} (residual {res:.2e})"
-    return hint
-
+from tests.decode_lib import EXACT_PIN_LENS as PIN_LENS
+from tests.decode_lib import EXACT_PLACES as PLACES
+from tests.decode_lib import NCAP_POW2 as NCAP
+from tests.decode_lib import (BLOCK_LENS, DS, FLOOR, GRID, LENS, PAGE_SIZES, PINNED_SPLITS, ROW_SHAPES, SCORE, STEP_FAULTS, STEP_LENS, STEP_SPLITS, TEETH,
+                              UNIFORM_SPLITS, attend64, decode_bound, decode_truth, emulate_kernel, gather, judge, locate_uniform, paginate,
+                              pinned_split_key, pinned_truth, prefix_sums, rt_of, step_bound, step_inputs, step_of, step_truth, target_of, truth64,
+                              ulp16, uniform_bound, uniform_hint, uniform_hypotheses, uniform_inputs, uniform_means, uniform_truth, visible, weights64)
+from tests.decode_lib import exact_pinned_inputs as pinned_inputs
+from tests.test_gpu_attn_exact import STEP_C, V8, V16, round_once
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the inputs are what the docstring says

@@ -5,9 +5,8 @@ new kernels, the exactness of the quantisation helpers — and a test of the GPU
 ignores k_scale, ignores v_scale, swaps the two, uses head 0's scales for every head, decodes the bytes as e4m3fnuz (bias 8), swaps the two
 fp16 chunks of one fp8 V chunk or takes K bytes 8 s .. 8 s + 7 in the wrong k-step leaves the bound by >= 20 x on EVERY row it touches.
 
-This module also holds what tests/test_gpu_decode_kv8.py shares: `quantize` / `dequant`, the per-head scales and the float64 reference."""
+`quantize` / `dequant`, the per-head scales and the float64 reference are shared with tests/test_gpu_decode_kv8.py: tests/decode_lib.py."""
 import ctypes as C
-import functools
 import json
 
 import numpy as np
@@ -15,91 +14,15 @@ import pytest
 import torch
 
 from leetcuda_amd import capi
-from tests.test_abi_cpu_decode import TEETH, auto_split, decode_inputs, decode_truth, rt_of, visible
-from tests.test_abi_cpu_decode_paged import PIN_LENS, PIN_NQ, PIN_SHAPE, _moved, _wrong_kernel, paginate, seam_inputs
-
-NAN_BYTE = 0x7F
-
-
-def _e4m3_table(bias, nan_codes):
-    """float32 [256]: the value of every code of a 1-4-3 format with this exponent bias"""
-    out = np.zeros(256, np.float32)
-    for c in range(256):
-        e, m = (c >> 3) & 15, c & 7
-        mag = m * 2.0 ** (1 - bias - 3) if e == 0 else (1 + m / 8) * 2.0 ** (e - bias)
-        out[c] = -mag if c & 0x80 else mag
-    for c in nan_codes:
-        out[c] = np.nan
-    return torch.from_numpy(out)
-
-
-OCP = _e4m3_table(7, (0x7F, 0xFF))        # OCP e4m3fn: what the kernel decodes (torch.float8_e4m3fn)
-FNUZ = _e4m3_table(8, (0x80,))            # e4m3fnuz: what gfx942-era code decodes; half the value of every normal code, 0x80 = NaN
-FINITE_CODES = torch.tensor([c for c in range(256) if c & 0x7F != 0x7F], dtype=torch.uint8)
-
-# power-of-two scales, 2^-5 .. 2^2, different between K / V heads and between K and V (the first Hkv of each are used)
-K_SCALES = (2.0 ** -3, 2.0 ** -1, 2.0 ** -4, 2.0 ** -2)
-V_SCALES = (2.0 ** -2, 2.0 ** -4, 2.0 ** 0, 2.0 ** -3)
-
-
-def scales(values, Hkv):
-    return torch.tensor(values[:Hkv], dtype=torch.float32)
-
-
-def _per_head(scale, x):
-    """a float or a float32 [Hkv] tensor, broadcast over [*, Hkv, rows, D]"""
-    return scale.view(1, -1, 1, 1) if torch.is_tensor(scale) else scale
-
-
-def quantize(x_fp16, scale):
-    """uint8, the shape of x: the e4m3fn bytes of x / scale (round to nearest even, saturating at +-448)"""
-    y = (x_fp16.float() / _per_head(scale, x_fp16)).clamp(-448.0, 448.0)
-    return y.to(torch.float8_e4m3fn).view(torch.uint8)
-
-
-def dequant(codes, scale, table=OCP):
-    """fp16: value(code) x scale.  Exact for a power-of-two scale in 2^-5 .. 2^2 (test_dequant_is_exact_...)"""
-    return (table[codes.long()] * _per_head(scale, codes)).half()
-
-
-def dequant64(codes, scale):
-    """float64: value(code) x scale with the scale as the kernel holds it (float32), the product exact"""
-    s = scale.view(1, -1, 1, 1).double() if torch.is_tensor(scale) else float(np.float32(scale))
-    return OCP[codes.long()].double() * s
-
-
-def softmax64(q, k64, v64, lens, causal):
-    """(out float64 [B,H,Nq,D], nk int [B,Nq]): the definition in float64 on the logical cache k64, v64 [B,Hkv,Ncap,D]; decode_truth's mask"""
-    B, H, Nq, D = q.shape
-    Hkv, Ncap = k64.shape[1], k64.shape[2]
-    G = H // Hkv
-    out = np.zeros((B, H, Nq, D))
-    nks = np.zeros((B, Nq), np.int64)
-    for b in range(B):
-        for i in range(Nq):
-            nk = nks[b, i] = visible(lens[b], Nq, Ncap, causal, i)
-            if nk == 0:
-                continue
-            for h in range(H):
-                s = (k64[b, h // G, :nk] @ q[b, h, i].double()) / D ** 0.5
-                p = torch.softmax(s, dim=0)
-                out[b, h, i] = (p @ v64[b, h // G, :nk]).numpy()
-    return out, nks
-
+from tests.decode_lib import (FINITE_CODES, FNUZ, K_SCALES, NAN_BYTE, OCP, PIN_LENS, PIN_NQ, PIN_SHAPE, TEETH, V_SCALES, _moved, _wrong_kernel,
+                              auto_split, decode_inputs, decode_truth, dequant, dequant64, paginate, quantize, reset_knobs, rt_of, scales,
+                              seam_inputs_kv8, softmax64)
+from tests.decode_lib import name_kv8 as _name
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _name(B, H, Hkv, Nq, ps, mp, D, flags=0):
-    buf = C.create_string_buffer(128)
-    rc = capi.load().lc_attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, ps, mp, D, flags, buf, 128)
-    return rc, buf.value.decode()
-
-
 @pytest.fixture
 def knobs(built):
-    capi.load()
-    yield
-    capi.tune("attn_decode_split", 0)
-    capi.tune("rule_cus", 0)
+    yield from reset_knobs()
 
 
 def test_kv8_errors_and_their_order(built):
@@ -308,21 +231,6 @@ def test_the_float64_reference_agrees_with_the_oracle(oracle):
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # a test of the GPU tests' inputs
-
-PIN_K_SCALES = (2.0, 4.0)           # K = +-1 is +-0.5 / +-0.25 in e4m3: a lost or foreign k_scale FLATTENS the softmax (12 -> 6, 3, 1.5 ...)
-PIN_V_SCALES = (2.0 ** -2, 2.0 ** -3)
-
-
-@functools.lru_cache(maxsize=8)
-def seam_inputs_kv8(D, causal):
-    """(q, k8, v8, k_scale, v_scale, lens): tests/test_abi_cpu_decode_paged.py seam_inputs with the cache quantised.  K = +-1 is exact in
-    e4m3 under PIN_K_SCALES, so the dominant score stays SCORE; V is randn rounded to e4m3"""
-    q, k, v, lens = seam_inputs(D, causal)
-    ks, vs = scales(PIN_K_SCALES, PIN_SHAPE[2]), scales(PIN_V_SCALES, PIN_SHAPE[2])
-    k8, v8 = quantize(k, ks), quantize(v, vs)
-    assert torch.equal(dequant(k8, ks), k)
-    return q, k8, v8, ks, vs, lens
-
 
 def _swap_d(x, bit):
     """x[..., d ^ bit]"""

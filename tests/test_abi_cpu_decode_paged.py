@@ -4,10 +4,9 @@ workspace bytes against the contiguous call of Ncap = max_pages x page_size, the
 and a test of the GPU tests' pinned page-seam inputs: on them a kernel that ignores the table, is off by one page, reads table row 0 for every
 batch entry, ignores the K / V head in the page base or takes the in-page offset modulo 16 leaves the bound by >= 20 x on EVERY row it touches.
 
-This module also holds what tests/test_gpu_decode_paged.py shares: `paginate` (a contiguous cache scattered over a pool, NaN wherever the kernel
-must not read) and its inverse `gather`.  Inputs, truth and the row check come from tests/test_abi_cpu_decode.py."""
+`paginate` (a contiguous cache scattered over a pool, NaN wherever the kernel must not read), its inverse `gather`, the inputs, truth and row
+check are shared with tests/test_gpu_decode_paged.py: tests/decode_lib.py."""
 import ctypes as C
-import functools
 import json
 
 import numpy as np
@@ -15,99 +14,15 @@ import pytest
 import torch
 
 from leetcuda_amd import capi
-from tests import tol
-from tests.test_abi_cpu_decode import SCORE, TEETH, auto_split, decode_inputs, decode_truth, rt_of, visible
-
-NCAP = 1024
-PIN_SHAPE = (3, 8, 2)
-PIN_NQ = 5
-PIN_LENS = (777, 129, 65)
-
-
-def paginate(k, v, lens, page_size, seed, spare=3, fill=float("nan")):
-    """(k_pool, v_pool [P,Hkv,page_size,D], table int32 [B,max_pages]) of a contiguous [B,Hkv,Ncap,D] cache, P = B max_pages + spare.
-    Pages are placed by a seeded random permutation of the pool: a sequence's pages are scattered, non-monotone and interleaved with the other
-    batch entries'.  Every pool row of a logical position >= L_b is `fill` (NaN), every table entry at a position >= ceil(L_b / page_size) names
-    a spare page that is `fill` throughout — a valid id: nothing here feeds an out-of-range page."""
-    B, Hkv, Ncap, D = k.shape
-    assert Ncap % page_size == 0 and spare >= 1
-    mp = Ncap // page_size
-    P = B * mp + spare
-    perm = torch.randperm(P, generator=torch.Generator().manual_seed(seed))
-    pools = [torch.full((P, Hkv, page_size, D), fill, dtype=k.dtype) for _ in range(2)]
-    table = torch.empty(B, mp, dtype=torch.int32)
-    tail = torch.arange(Ncap).view(1, 1, Ncap, 1) >= torch.tensor([min(max(int(x), 0), Ncap) for x in lens]).view(B, 1, 1, 1)
-    for pool, x in zip(pools, (k, v)):
-        x = x.masked_fill(tail, fill)
-        for b in range(B):
-            for p in range(mp):
-                pool[perm[b * mp + p]] = x[b, :, p * page_size:(p + 1) * page_size]
-    for b in range(B):
-        used = -(-min(max(int(lens[b]), 0), Ncap) // page_size)
-        for p in range(mp):
-            table[b, p] = perm[b * mp + p] if p < used else perm[B * mp + (b + p) % spare]
-    return pools[0], pools[1], table
-
-
-def gather(pool, table, batch_of=None, page_of=None, head_of=None, row_of=None):
-    """the contiguous [B,Hkv,Ncap,D] view a kernel sees through `table`.  The keyword arguments restate a WRONG kernel: batch_of(b) -> table row,
-    page_of(b, p) -> pool page of logical page p (instead of table[b][p]), head_of(h) -> K / V head slab, row_of(j) -> row inside the page"""
-    B, mp = table.shape
-    P, Hkv, ps, D = pool.shape
-    rows = torch.tensor([row_of(j) if row_of else j for j in range(ps)])
-    heads = torch.tensor([head_of(h) if head_of else h for h in range(Hkv)])
-    out = torch.empty(B, Hkv, mp * ps, D, dtype=pool.dtype)
-    for b in range(B):
-        tb = batch_of(b) if batch_of else b
-        for p in range(mp):
-            pid = page_of(b, p) if page_of else int(table[tb, p])
-            out[b, :, p * ps:(p + 1) * ps] = pool[pid][heads][:, rows]
-    return out
-
-
-def seam_target(L, Nq, Ncap, causal, r):
-    """the key that scores SCORE for row r = g Nq + i of a K / V head: one key before (r even) or at (r odd) a 16-key page boundary below the
-    row's limit, the boundary varying with r.  Boundaries are 16 j with j % 4 in {2, 3}: both sides of each have an offset >= 16 inside a
-    64-key page, where "offset modulo 16" loses them.  None: no such boundary below the limit."""
-    lim = visible(L, Nq, Ncap, causal, r % Nq)
-    seams = [16 * j for j in range(1, (lim + 15) // 16) if j % 4 in (2, 3) and 16 * j < lim]
-    if not seams:
-        return None
-    p = seams[(7 * (r // 2) + 3) % len(seams)]
-    return p - 1 if r % 2 == 0 else p
-
-
-@functools.lru_cache(maxsize=8)
-def seam_inputs(D, causal):
-    """(q, k, v, lens) at Ncap = 1024: K random +-1, Q_row = (SCORE / sqrt(D)) K[target], V randn — the construction of pinned_inputs"""
-    B, H, Hkv = PIN_SHAPE
-    Nq, G = PIN_NQ, H // Hkv
-    g = torch.Generator().manual_seed(104729 * D + int(causal))
-    k = (torch.randint(0, 2, (B, Hkv, NCAP, D), generator=g) * 2 - 1).float()
-    v = torch.randn(B, Hkv, NCAP, D, generator=g)
-    q = torch.randn(B, H, Nq, D, generator=g)
-    for b in range(B):
-        for h in range(H):
-            for i in range(Nq):
-                t = seam_target(PIN_LENS[b], Nq, NCAP, causal, (h % G) * Nq + i)
-                if t is not None:
-                    q[b, h, i] = (SCORE / D ** 0.5) * k[b, h // G, t]
-    return q.half(), k.half(), v.half(), PIN_LENS
-
+from tests.decode_lib import NCAP_POW2 as NCAP
+from tests.decode_lib import (PIN_NQ, PIN_SHAPE, SCORE, TEETH, _wrong_kernel, auto_split, decode_inputs, decode_truth, gather, paginate,
+                              reset_knobs, rt_of, seam_inputs, seam_target, visible)
+from tests.decode_lib import name_paged as _name
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _name(B, H, Hkv, Nq, ps, mp, D, flags=0):
-    buf = C.create_string_buffer(128)
-    rc = capi.load().lc_attn_decode_paged_kernel_name(B, H, Hkv, Nq, ps, mp, D, flags, buf, 128)
-    return rc, buf.value.decode()
-
-
 @pytest.fixture
 def knobs(built):
-    capi.load()
-    yield
-    capi.tune("attn_decode_split", 0)
-    capi.tune("rule_cus", 0)
+    yield from reset_knobs()
 
 
 def test_paged_errors_and_their_order(built):
@@ -276,32 +191,6 @@ def test_paginate_and_gather_are_inverse_and_poison_what_must_not_be_read():
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 # a test of the GPU tests' inputs
-
-def _moved(truth, nks, wrong):
-    """[B, H, Nq]: largest |wrong - truth| / bound over a row's columns, the bound being that of the row's visible keys"""
-    atol = np.array([[tol.attn_max_abs(int(n)) for n in row] for row in nks]).reshape(nks.shape[0], 1, nks.shape[1], 1)
-    bound = atol + tol.ATTN_RTOL_F16 * np.abs(truth.astype(np.float64))
-    return (np.abs(wrong.astype(np.float64) - truth) / bound).max(axis=-1)
-
-
-def _wrong_kernel(oracle, q, kw, vw, lens, causal, truth, nks):
-    """[B, H, Nq] ratio of a kernel that sees the cache (kw, vw).  A row whose visible keys hold a non-finite K or V row gets inf: the kernel's
-    score or P V product is NaN there, which check_decode refuses outright (the oracle is only asked about finite inputs)."""
-    B, H, Nq, _ = q.shape
-    G = H // kw.shape[1]
-    poisoned = np.zeros((B, H, Nq), bool)
-    for b in range(B):
-        bad = ~(torch.isfinite(kw[b]).all(dim=-1) & torch.isfinite(vw[b]).all(dim=-1))       # [Hkv, Ncap]
-        first_bad = [int(torch.nonzero(bad[kh])[0]) if bad[kh].any() else NCAP for kh in range(kw.shape[1])]
-        for h in range(H):
-            for i in range(Nq):
-                poisoned[b, h, i] = first_bad[h // G] < nks[b, i]
-    clean = lambda x: torch.where(torch.isfinite(x), x, torch.zeros_like(x))      # noqa: E731
-    wrong, _ = decode_truth(oracle, q, clean(kw), clean(vw), lens, causal)
-    ratio = _moved(truth, nks, wrong)
-    ratio[poisoned] = np.inf
-    return ratio
-
 
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
 @pytest.mark.parametrize("D", [64, 128])

@@ -1,59 +1,24 @@
 """Decode attention over a KV cache on the GPU (lc_attn_decode_f16 / capi.attn_decode): every row of every case against the CPU oracle
-(tests/test_abi_cpu_decode.py decode_truth) under tol.attn_close with N = the row's visible keys; rows without a visible key exactly 0.
+(tests/decode_lib.py decode_truth) under tol.attn_close with N = the row's visible keys; rows without a visible key exactly 0.
 The shapes are small (Ncap = 1000) so that every row is checked; the split path is reached through "attn_decode_split" (ranges may be
-empty).  Inputs, truth and the pinned construction are shared with tests/test_abi_cpu_decode.py, which proves on the CPU that the pinned
-inputs have teeth."""
+empty).  Inputs, truth and the pinned construction (tests/decode_lib.py) are shared with tests/test_abi_cpu_decode.py, which proves on the CPU
+that the pinned inputs have teeth."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-from tests.test_abi_cpu_decode import GRID_LENS, GRID_NQ, GRID_SHAPES, NCAP, PLACES, check_decode, decode_inputs, decode_truth, pinned_inputs, rt_of
+from tests.decode_lib import NCAP_RAGGED as NCAP
+from tests.decode_lib import (GRID_NQ, GRID_SHAPES, PLACES, _capi, _lens_of, _oracle, check_decode, decode_inputs, decode_truth, forced_split,
+                              pinned_inputs, rt_of)
+from tests.decode_lib import run_flat as _run
 
 pytestmark = pytest.mark.gpu
 
 
-def _capi():
-    from leetcuda_amd import capi
-    capi.require_production()
-    return capi
-
-
-def _oracle():
-    from tests import oracle_lib
-    return oracle_lib.load()
-
-
-def _lens_of(B, Hkv):
-    lens = GRID_LENS[B]
-    return tuple(reversed(lens)) if (B, Hkv) == (2, 4) else lens
-
-
-def _dev_lens(lens):
-    return None if lens is None else torch.tensor(list(lens), dtype=torch.int32, device="cuda")
-
-
-def _run(capi, q, k, v, lens, causal, split=0, workspace=None, o=None):
-    """one call under a forced split; returns O (a NaN-prefilled tensor unless given)"""
-    qg, kg, vg = (x if x.is_cuda else x.cuda() for x in (q, k, v))
-    if o is None:
-        o = torch.full_like(qg, float("nan"))
-    capi.tune("attn_decode_split", split)
-    try:
-        capi.attn_decode(qg, kg, vg, o, _dev_lens(lens) if not torch.is_tensor(lens) else lens, causal=causal, workspace=workspace)
-    finally:
-        capi.tune("attn_decode_split", 0)
-    torch.cuda.synchronize()
-    return o
-
-
 def _want(capi, B, H, Hkv, Nq, Ncap, D, split):
-    capi.tune("attn_decode_split", split)
-    try:
-        return capi.attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D)
-    finally:
-        capi.tune("attn_decode_split", 0)
+    return forced_split(split, lambda: capi.attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D))
 
 
 @functools.lru_cache(maxsize=8)

@@ -2,7 +2,7 @@
 every (D, RT) instantiation of attn_decode_kernel, attn_decode_combine_kernel under split counts from 1 up to more ranges than tiles, and
 attn_decode_paged_kernel — on EVERY element of a NaN-prefilled O that sits in the middle of a NaN-filled buffer (a guard of 64 D halves on
 each side must stay NaN; rows without a visible key must be exactly 0; everything else finite and inside the class's bound).  Inputs, truths,
-bounds, the fault locator and the CPU proof that the inputs have teeth live in tests/test_abi_cpu_decode_exact.py; its docstring describes
+bounds and the fault locator live in tests/decode_lib.py, the CPU proof that the inputs have teeth in tests/test_abi_cpu_decode_exact.py; its docstring describes
 the classes, what each cannot see, and the assumption behind `uniform`'s S > 1 bound (device log2f / exp2 within 8 fp32 ulps).
 
 Every case asserts the kernel name first (attn_decode_kernel<D,RT> with the ` xS` suffix), forces the split through "attn_decode_split"
@@ -35,22 +35,18 @@ import pytest
 import torch
 
 from tests import tol
-from tests.test_abi_cpu_decode import check_decode, rt_of
-from tests.test_abi_cpu_decode_exact import (GRID, LENS, NCAP, PAGE_SIZES, PAGED_SHAPES, PIN_LENS, PINNED_SPLITS, PLACES, ROW_SHAPES, STEP_LENS,
-                                             STEP_SPLITS, UNIFORM_SPLITS, decode_bound, judge, pinned_inputs, pinned_split_key, pinned_truth,
-                                             step_bound, step_inputs, step_truth, uniform_bound, uniform_hint, uniform_inputs, uniform_truth)
-from tests.test_abi_cpu_decode_paged import gather, paginate
+from tests.decode_lib import EXACT_PIN_LENS as PIN_LENS
+from tests.decode_lib import EXACT_PLACES as PLACES
+from tests.decode_lib import NCAP_POW2 as NCAP
+from tests.decode_lib import (GRID, LENS, PAGE_SIZES, PAGED_SHAPES, PINNED_SPLITS, ROW_SHAPES, STEP_LENS, STEP_SPLITS, UNIFORM_SPLITS, _capi, check_decode,
+                              decode_bound, gather, judge, paginate, pinned_split_key, pinned_truth, rt_of, step_bound, step_inputs, step_truth,
+                              uniform_bound, uniform_hint, uniform_inputs, uniform_truth)
+from tests.decode_lib import exact_pinned_inputs as pinned_inputs
 from tests.test_gpu_attn_exact import round_once
 
 pytestmark = pytest.mark.gpu
 
 MASKS = (False, True)
-
-
-def _capi():
-    from leetcuda_amd import capi
-    capi.require_production()
-    return capi
 
 
 def _id(x):

@@ -1,79 +1,30 @@
 """Decode attention over a paged fp8 (e4m3) KV cache on the GPU (lc_attn_decode_paged_kv8 / capi.attn_decode_paged_kv8).  Every e4m3 value is
 an fp16 value and the kernel converts exactly, so with power-of-two scales correctness is (a) BIT equality with capi.attn_decode_paged — an
 existing, separately tested call — on the dequantised fp16 pool under the same split, and (b) every row against the CPU oracle on the
-dequantised logical cache (tests/test_abi_cpu_decode.py decode_truth / check_decode, tol.attn_close with N = the row's visible keys).
+dequantised logical cache (tests/decode_lib.py decode_truth / check_decode, tol.attn_close with N = the row's visible keys).
 Non-power-of-two scales are checked against a float64 softmax on the exactly dequantised values under the same bound.  Ncap = 1024 throughout;
 pools come from `paginate` on the quantised cache: scattered pages, the NaN code 0x7f in every pool byte of a position >= L_b and in the spare
-page every unused table entry names.  Helpers and scales: tests/test_abi_cpu_decode_kv8.py."""
+page every unused table entry names.  Helpers and scales: tests/decode_lib.py."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-from tests.test_abi_cpu_decode import GRID_SHAPES, check_decode, decode_inputs, decode_truth, pinned_inputs, rt_of
-from tests.test_abi_cpu_decode_kv8 import (FINITE_CODES, K_SCALES, NAN_BYTE, V_SCALES, dequant, dequant64, quantize, scales, seam_inputs_kv8,
-                                           softmax64)
-from tests.test_abi_cpu_decode_paged import NCAP, paginate
+from tests.decode_lib import NCAP_POW2 as NCAP
+from tests.decode_lib import (FINITE_CODES, GRID_SHAPES, K_SCALES, NAN_BYTE, V_SCALES, _capi, _cuda, _dev_lens, _lens_of, _oracle, check_decode,
+                              decode_inputs, decode_truth, dequant, dequant64, forced_split, paginate, pinned_inputs, quantize, rt_of, scales,
+                              seam_inputs_kv8, softmax64)
+from tests.decode_lib import run_kv8 as _run_kv8
+from tests.decode_lib import run_paged as _run_f16
 
 pytestmark = pytest.mark.gpu
-
-
-def _capi():
-    from leetcuda_amd import capi
-    capi.require_production()
-    return capi
-
-
-def _oracle():
-    from tests import oracle_lib
-    return oracle_lib.load()
-
-
-def _dev_lens(lens):
-    return lens if torch.is_tensor(lens) else torch.tensor(list(lens), dtype=torch.int32, device="cuda")
-
-
-def _cuda(*xs):
-    return tuple(x if x is None or x.is_cuda else x.cuda() for x in xs)
-
-
-def _run_kv8(capi, q, kp8, vp8, table, lens, ks, vs, causal, split=0, workspace=None, o=None):
-    """one fp8 call under a forced split; returns O (NaN-prefilled unless given)"""
-    qg, kg, vg, tg, ksg, vsg = _cuda(q, kp8, vp8, table, ks, vs)
-    if o is None:
-        o = torch.full_like(qg, float("nan"))
-    capi.tune("attn_decode_split", split)
-    try:
-        capi.attn_decode_paged_kv8(qg, kg, vg, o, tg, _dev_lens(lens), ksg, vsg, causal=causal, workspace=workspace)
-    finally:
-        capi.tune("attn_decode_split", 0)
-    torch.cuda.synchronize()
-    return o
-
-
-def _run_f16(capi, q, kp, vp, table, lens, causal, split=0):
-    """the fp16 paged call (capi.attn_decode_paged) under the same forced split"""
-    qg, kg, vg, tg = _cuda(q, kp, vp, table)
-    o = torch.full_like(qg, float("nan"))
-    capi.tune("attn_decode_split", split)
-    try:
-        capi.attn_decode_paged(qg, kg, vg, o, tg, _dev_lens(lens), causal=causal)
-    finally:
-        capi.tune("attn_decode_split", 0)
-    torch.cuda.synchronize()
-    return o
 
 
 def _pools(k8, v8, lens, ps, seed, ks, vs, spare=3, fill=NAN_BYTE):
     """(kp8, vp8, table, the dequantised fp16 pools) on the GPU; the fp16 pools hold NaN exactly where the fp8 ones hold the NaN code"""
     kp8, vp8, table = paginate(k8, v8, lens, ps, seed=seed, spare=spare, fill=fill)
     return _cuda(kp8, vp8, table, dequant(kp8, ks), dequant(vp8, vs))
-
-
-def _lens_of(B, Hkv):
-    lens = {3: (1000, 129, 65), 2: (65, 1000)}[B]
-    return tuple(reversed(lens)) if (B, Hkv) == (2, 4) else lens
 
 
 @functools.lru_cache(maxsize=4)
@@ -94,11 +45,8 @@ def _grid_pool(D, shape, Nq, causal, ps):
 
 
 def _names(capi, B, H, Hkv, Nq, ps, D, split):
-    capi.tune("attn_decode_split", split)
-    try:
-        return capi.attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, ps, NCAP // ps, D), capi.attn_decode_paged_kernel_name(B, H, Hkv, Nq, ps, NCAP // ps, D)
-    finally:
-        capi.tune("attn_decode_split", 0)
+    return forced_split(split, lambda: (capi.attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, ps, NCAP // ps, D),
+                                        capi.attn_decode_paged_kernel_name(B, H, Hkv, Nq, ps, NCAP // ps, D)))
 
 
 @pytest.mark.parametrize("split", [0, 1, 3, 8])
@@ -352,7 +300,7 @@ def test_pinned_page_seam_inputs(D, causal, ps, split):
 
 @functools.lru_cache(maxsize=4)
 def _pinned_case(D, place, causal):
-    """tests/test_abi_cpu_decode.py pinned_inputs (Ncap 1000, every L_b below it) in a logical cache of 1024, quantised; the truth is the
+    """tests/decode_lib.py pinned_inputs (Ncap 1000, every L_b below it) in a logical cache of 1024, quantised; the truth is the
     oracle's on the dequantised cache"""
     q, k, v, lens = pinned_inputs(D, place, causal)
     pad = lambda x: torch.cat([x, torch.zeros(*x.shape[:2], NCAP - x.shape[2], x.shape[3], dtype=x.dtype)], dim=2)      # noqa: E731

@@ -1,7 +1,7 @@
 """Decode attention over a PAGED KV cache on the GPU (lc_attn_decode_paged_f16 / capi.attn_decode_paged).  Correctness is (a) every row against
-the CPU oracle on the logical cache (tests/test_abi_cpu_decode.py decode_truth / check_decode, tol.attn_close with N = the row's visible keys)
+the CPU oracle on the logical cache (tests/decode_lib.py decode_truth / check_decode, tol.attn_close with N = the row's visible keys)
 and (b) BIT equality with capi.attn_decode — an existing, separately tested call — on the gathered contiguous cache of Ncap = max_pages x
-page_size under the same split.  Ncap = 1024 throughout; pools come from tests/test_abi_cpu_decode_paged.py `paginate`: scattered pages, NaN in
+page_size under the same split.  Ncap = 1024 throughout; pools come from tests/decode_lib.py `paginate`: scattered pages, NaN in
 every pool row of a position >= L_b and in the spare page every unused table entry names.  No test feeds an out-of-range page id."""
 import functools
 
@@ -9,69 +9,18 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_abi_cpu_decode import GRID_SHAPES, check_decode, decode_inputs, decode_truth, rt_of
-from tests.test_abi_cpu_decode_paged import NCAP, gather, paginate, seam_inputs
+from tests.decode_lib import NCAP_POW2 as NCAP
+from tests.decode_lib import (GRID_SHAPES, _capi, _cuda, _dev_lens, _lens_of, _oracle, check_decode, decode_inputs, decode_truth, forced_split, gather,
+                              paginate, rt_of, seam_inputs)
+from tests.decode_lib import run_flat as _run_flat
+from tests.decode_lib import run_paged as _run_paged
 
 pytestmark = pytest.mark.gpu
 
 
-def _capi():
-    from leetcuda_amd import capi
-    capi.require_production()
-    return capi
-
-
-def _oracle():
-    from tests import oracle_lib
-    return oracle_lib.load()
-
-
-def _dev_lens(lens):
-    return lens if torch.is_tensor(lens) else torch.tensor(list(lens), dtype=torch.int32, device="cuda")
-
-
-def _cuda(*xs):
-    return tuple(x if x.is_cuda else x.cuda() for x in xs)
-
-
-def _run_paged(capi, q, kp, vp, table, lens, causal, split=0, workspace=None, o=None):
-    """one paged call under a forced split; returns O (NaN-prefilled unless given)"""
-    qg, kg, vg, tg = _cuda(q, kp, vp, table)
-    if o is None:
-        o = torch.full_like(qg, float("nan"))
-    capi.tune("attn_decode_split", split)
-    try:
-        capi.attn_decode_paged(qg, kg, vg, o, tg, _dev_lens(lens), causal=causal, workspace=workspace)
-    finally:
-        capi.tune("attn_decode_split", 0)
-    torch.cuda.synchronize()
-    return o
-
-
-def _run_flat(capi, q, k, v, lens, causal, split=0):
-    """the contiguous call (capi.attn_decode) under the same forced split"""
-    qg, kg, vg = _cuda(q, k, v)
-    o = torch.full_like(qg, float("nan"))
-    capi.tune("attn_decode_split", split)
-    try:
-        capi.attn_decode(qg, kg, vg, o, _dev_lens(lens), causal=causal)
-    finally:
-        capi.tune("attn_decode_split", 0)
-    torch.cuda.synchronize()
-    return o
-
-
 def _names(capi, B, H, Hkv, Nq, ps, D, split):
-    capi.tune("attn_decode_split", split)
-    try:
-        return capi.attn_decode_paged_kernel_name(B, H, Hkv, Nq, ps, NCAP // ps, D), capi.attn_decode_kernel_name(B, H, Hkv, Nq, NCAP, D)
-    finally:
-        capi.tune("attn_decode_split", 0)
-
-
-def _lens_of(B, Hkv):
-    lens = {3: (1000, 129, 65), 2: (65, 1000)}[B]
-    return tuple(reversed(lens)) if (B, Hkv) == (2, 4) else lens
+    return forced_split(split, lambda: (capi.attn_decode_paged_kernel_name(B, H, Hkv, Nq, ps, NCAP // ps, D),
+                                        capi.attn_decode_kernel_name(B, H, Hkv, Nq, NCAP, D)))
 
 
 @functools.lru_cache(maxsize=4)

@@ -137,15 +137,14 @@ def run_decode(spec, shape, opts):
                 ke, ve = ks.repeat_interleave(H // kvh, dim=1), vs.repeat_interleave(H // kvh, dim=1)
                 name = "torch sdpa (K / V expanded)"
                 step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ke, ve)  # noqa: E731
-        elif kv8:
-            name = capi.attn_decode_paged_kv8_kernel_name(B, H, kvh, nq, page, N // page, D, causal=causal)
-            step = lambda: capi.attn_decode_paged_kv8(q, k_pool, v_pool, o, table, lens, k_scale, v_scale, causal=causal)  # noqa: E731
-        elif page:
-            name = capi.attn_decode_paged_kernel_name(B, H, kvh, nq, page, N // page, D, causal=causal)
-            step = lambda: capi.attn_decode_paged(q, k_pool, v_pool, o, table, lens, causal=causal)  # noqa: E731
-        else:
-            name = capi.attn_decode_kernel_name(B, H, kvh, nq, N, D, causal=causal)
-            step = lambda: capi.attn_decode(q, k, v, o, lens, causal=causal)  # noqa: E731
+        else:                                           # the cache kind of the spec -> (name function, its shape arguments, step)
+            paged = (B, H, kvh, nq, page, N // max(page, 1), D)
+            name_of, shape_args, step = {
+                "kv8": (capi.attn_decode_paged_kv8_kernel_name, paged, lambda: capi.attn_decode_paged_kv8(q, k_pool, v_pool, o, table, lens, k_scale, v_scale, causal=causal)),
+                "paged": (capi.attn_decode_paged_kernel_name, paged, lambda: capi.attn_decode_paged(q, k_pool, v_pool, o, table, lens, causal=causal)),
+                "flat": (capi.attn_decode_kernel_name, (B, H, kvh, nq, N, D), lambda: capi.attn_decode(q, k, v, o, lens, causal=causal)),
+            }["kv8" if kv8 else "paged" if page else "flat"]
+            name = name_of(*shape_args, causal=causal)
         ms = timed(step)
     finally:
         capi.tune("attn_decode_split", 0)
