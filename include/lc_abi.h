@@ -403,7 +403,7 @@ int lc_attn_decode_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_siz
  * Every e4m3 value is an fp16 value and the kernel converts exactly, so with power-of-two scales that keep the dequantised values normal fp16
  * numbers the output is BIT-IDENTICAL to lc_attn_decode_paged_f16 on the dequantised fp16 pool (same Q, table, kv_len, flags and S).
  * Not here: a contiguous fp8 entry (a contiguous cache with Ncap a power of two is a pool with num_pages = B), per-token or per-page scales,
- * a quantise-and-append kernel, e5m2, fp8 Q.
+ * e5m2, fp8 Q.  (What writes these pools: lc_kv_append_paged_kv8 below.)
  * The name call never launches: "attn_decode_paged_kv8_kernel<D,RT>", with S > 1 followed by " xS". */
 int lc_attn_decode_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O,
                              const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
@@ -413,6 +413,48 @@ int lc_attn_decode_paged_kv8(const void* Q, const void* Kpool8, const void* Vpoo
 size_t lc_attn_decode_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D);
 int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
                                          int flags, char* buf, int buflen);
+
+/* EXTENSION: the write side of the paged KV cache (kv_append_paged.hip): the K and V rows of the Nq newest tokens of
+ * every sequence go into the pools that lc_attn_decode_paged_f16 / lc_attn_decode_paged_kv8 read, through the same block table and the same
+ * kv_len array, in ONE launch for K and V.  One decoding step is: bump kv_len on the device, append, decode — on one stream, capturable as one
+ * graph.  A prefill is the same call with Nq = the prompt length.
+ * Knew, Vnew: [B,Hkv,Nq,D] fp16, dense, 16-byte aligned: the rows of the Nq newest tokens.  Never written.
+ * Kpool, Vpool (fp16) / Kpool8, Vpool8 (OCP e4m3fn bytes): [num_pages,Hkv,page_size,D], the layout of the decode calls, 16-byte aligned.
+ * block_table: DEVICE int32[B,max_pages]; kv_len: DEVICE int32[B]; k_scale, v_scale (fp8 call): DEVICE float[Hkv], or NULL = 1.0.  All of them
+ * are read by the kernel only, never by the host: a captured graph may be replayed after they were rewritten in place.
+ * Where a token goes: kv_len[b] is the length AFTER the append — the value the decode call of the same step is handed.  L = kv_len[b] clamped to
+ * [0, max_pages x page_size] (the decode kernels' clamp); token i of batch entry b has position p = L - Nq + i, the position the bottom-right
+ * causal mask of lc_attn_decode_* gives query i.  p < 0: the token is not written, so a batch of LEFT-PADDED prompts of different lengths fills
+ * its caches in one call with Nq = the longest prompt.  Otherwise it goes to page block_table[b][p / page_size], row p % page_size, of every
+ * K / V head.  A page id outside [0, num_pages) DROPS the token — unlike the read side, which clamps: a write to a clamped page would corrupt
+ * another sequence's cache.  Table entries of pages that hold none of the Nq positions are never read.  Nothing but the target rows of the two
+ * pools is written (Hkv x D elements per written token and pool).  Two batch entries that name the same page and row: which one lands is
+ * unspecified.
+ * MEMORY SAFETY: as on the read side the host cannot check the table; num_pages must be the true page count of BOTH pools.
+ * fp8: the code of element x of K / V head g is e4m3fn_rne(clamp(fp32(x) / scale[g], -448, 448)): the fp32 quotient is the correctly rounded
+ * IEEE division (not a multiplication by a reciprocal), the conversion rounds to nearest even onto e4m3fn, subnormals included; +-inf gives
+ * +-448, -0 gives 0x80, NaN gives a NaN code (code & 0x7f == 0x7f).  Scales are expected positive and finite.
+ * Checks, all before any device work: flags != 0 (no flag is defined), then a NULL Knew / Vnew / pool / block_table / kv_len: LC_ERR_ARG; then
+ * LC_ERR_SHAPE for non-positive B / Hkv / Nq / num_pages / max_pages / D, page_size not a power of two >= 16, max_pages x page_size not an
+ * int, max_pages x page_size x D x (element bytes) >= 2 GiB (the decode calls' bound: every pool geometry append accepts, decode accepts), a
+ * grid of B x Hkv x ceil(Nq D / 2048) workgroups that does not fit an int, Knew / Vnew / pools not 16-byte aligned; then D not in {64, 128}:
+ * LC_ERR_HEADDIM.  Nq is NOT bounded by the decode kernels' 64 rows: a prefill writes whole prompts.  No workspace.
+ * Kernels: kv_append_paged_kernel<D>, kv_append_paged_kv8_kernel<D>.  The name calls never launch, take no num_pages (it decides nothing) and
+ * return the status the run call gives that shape; a NULL buffer or buflen < 8: LC_ERR_ARG.
+ * Not here: per-token or per-page scales, pools laid out [P,page_size,Hkv,D], a [B,Nq,Hkv,D] source, rotary embedding, an append to a
+ * contiguous cache, ragged Nq per sequence other than by left padding. */
+int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
+                           const int* block_table, const int* kv_len,
+                           int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
+                           int flags, void* stream);
+int lc_kv_append_paged_kv8(const void* Knew, const void* Vnew, void* Kpool8, void* Vpool8,
+                           const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                           int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
+                           int flags, void* stream);
+int lc_kv_append_paged_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                   int flags, char* buf, int buflen);
+int lc_kv_append_paged_kv8_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                       int flags, char* buf, int buflen);
 
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */

@@ -29,7 +29,8 @@ ORACLE_NAME = "liblc_oracle.so"
 # Translation units whose audit report is a file of its own next to isa_audit.json (same rules, same refusal to link on a violation).
 # isa_audit.json is read by name patterns and entry counts: "attn_decode" is counted as the eight kernels of tu_attn_decode.hip, and the
 # paged kernels' names (attn_decode_paged_kernel<D, RT>) contain that string.
-AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_attn_decode_paged_kv8": "isa_audit_decode_paged_kv8.json"}
+AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_attn_decode_paged_kv8": "isa_audit_decode_paged_kv8.json",
+                    "tu_kv_append": "isa_audit_kv_append.json"}
 
 
 def _newer(target: Path, sources) -> bool:

@@ -61,6 +61,10 @@ SYMBOLS = {
     "lc_attn_decode_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_decode_paged_kv8_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "lc_attn_decode_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_kv_append_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "lc_kv_append_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "lc_kv_append_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_kv_append_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -540,6 +544,69 @@ def attn_decode_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D
 def attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
     """The kernel attn_decode_paged_kv8 runs for this shape under the current knobs: "attn_decode_paged_kv8_kernel<D,RT>", + " xS" with S > 1."""
     return _decode_kernel_name("lc_attn_decode_paged_kv8_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
+
+
+def _kv_append_args(k_new, v_new, k_pool, v_pool, block_table, kv_len, k_scale=None, v_scale=None, kv8=False):
+    """The dtype and shape checks of kv_append_paged / kv_append_paged_kv8 (no GPU needed): fp16 k_new, v_new [B,Hkv,Nq,D]; pools
+    [num_pages,Hkv,page_size,D] of fp16 (kv8: float8_e4m3fn or uint8); int32 block_table [B,max_pages] and kv_len [B]; kv8: float32 [Hkv] scales
+    or None.  Returns B, Hkv, Nq, num_pages, page_size, max_pages, D."""
+    import torch
+    pool_types = (torch.float8_e4m3fn, torch.uint8) if kv8 else (torch.half,)
+    if k_new.dtype != torch.half or v_new.dtype != torch.half:
+        raise TypeError(f"k_new / v_new must be float16, got {k_new.dtype} / {v_new.dtype}")
+    if k_pool.dtype not in pool_types or v_pool.dtype not in pool_types:
+        raise TypeError(f"k_pool / v_pool must be {' or '.join(str(t) for t in pool_types)}, got {k_pool.dtype} / {v_pool.dtype}")
+    if k_new.dim() != 4 or k_pool.dim() != 4:
+        _shape_err("4-D [B,Hkv,Nq,D] / [num_pages,Hkv,page_size,D] tensors expected")
+    B, Hkv, Nq, D = k_new.shape
+    if tuple(v_new.shape) != (B, Hkv, Nq, D) or k_pool.shape[1] != Hkv or k_pool.shape[3] != D or tuple(v_pool.shape) != tuple(k_pool.shape):
+        _shape_err(f"k_new {tuple(k_new.shape)} v_new {tuple(v_new.shape)} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)}")
+    if block_table is None or block_table.dim() != 2 or block_table.shape[0] != B:
+        _shape_err(f"block_table {None if block_table is None else tuple(block_table.shape)} for batch {B}")
+    if kv_len is None or tuple(kv_len.shape) != (B,):
+        _shape_err(f"kv_len {None if kv_len is None else tuple(kv_len.shape)} for batch {B}")
+    if block_table.dtype != torch.int32 or kv_len.dtype != torch.int32:
+        raise TypeError(f"block_table / kv_len must be int32, got {block_table.dtype} / {kv_len.dtype}")
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            continue
+        if s.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {s.dtype}")
+        if tuple(s.shape) != (Hkv,):
+            _shape_err(f"{name} {tuple(s.shape)} for {Hkv} K/V heads")
+    return B, Hkv, Nq, k_pool.shape[0], k_pool.shape[2], block_table.shape[1], D
+
+
+def kv_append_paged(k_new, v_new, k_pool, v_pool, block_table, kv_len):
+    """Append to a paged KV cache (lc_kv_append_paged_f16): k_new, v_new [B,Hkv,Nq,D] fp16, the rows of the Nq newest tokens of every sequence, go
+    into k_pool, v_pool [num_pages,Hkv,page_size,D] fp16 through block_table (DEVICE int32 [B,max_pages]) and kv_len (DEVICE int32 [B], the
+    lengths AFTER the append: what the decode call of the same step is handed).  Token i of entry b lands at position kv_len[b] - Nq + i; a
+    negative position is not written (left-padded prompts), a page id outside the pool drops the token.  Returns the pools."""
+    dims = _kv_append_args(k_new, v_new, k_pool, v_pool, block_table, kv_len)
+    _need_gpu(k_new, v_new, k_pool, v_pool, block_table, kv_len)
+    check(load().lc_kv_append_paged_f16(_ptr(k_new), _ptr(v_new), _ptr(k_pool), _ptr(v_pool), _ptr(block_table), _ptr(kv_len), *dims, 0, _stream()),
+          "lc_kv_append_paged_f16")
+    return k_pool, v_pool
+
+
+def kv_append_paged_kv8(k_new, v_new, k_pool8, v_pool8, block_table, kv_len, k_scale=None, v_scale=None):
+    """Quantise and append to a paged KV cache kept in fp8 (lc_kv_append_paged_kv8): kv_append_paged with k_pool8, v_pool8 of torch.float8_e4m3fn
+    (or its bytes as uint8) and k_scale, v_scale DEVICE float32 [Hkv] tensors (None = 1.0): the code of x is e4m3fn(clamp(x / scale, +-448)),
+    round to nearest even — the pools attn_decode_paged_kv8 reads with the same scales."""
+    dims = _kv_append_args(k_new, v_new, k_pool8, v_pool8, block_table, kv_len, k_scale, v_scale, kv8=True)
+    _need_gpu(k_new, v_new, k_pool8, v_pool8, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    check(load().lc_kv_append_paged_kv8(_ptr(k_new), _ptr(v_new), _ptr(k_pool8), _ptr(v_pool8), _ptr(block_table), _ptr(kv_len),
+                                        _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
+                                        *dims, 0, _stream()), "lc_kv_append_paged_kv8")
+    return k_pool8, v_pool8
+
+
+def kv_append_paged_kernel_name(B, Hkv, Nq, page_size, max_pages, D, kv8=False) -> str:
+    """The kernel kv_append_paged (kv8: kv_append_paged_kv8) runs for this shape: "kv_append_paged_kernel<D>" / "kv_append_paged_kv8_kernel<D>"."""
+    symbol = "lc_kv_append_paged_kv8_kernel_name" if kv8 else "lc_kv_append_paged_kernel_name"
+    buf = C.create_string_buffer(128)
+    check(getattr(load(), symbol)(B, Hkv, Nq, page_size, max_pages, D, 0, buf, 128), symbol)
+    return buf.value.decode()
 
 
 def attn_fwd_bf16(q, k, v, o):

@@ -100,6 +100,23 @@ int decode_name(const DecodeCall& c, char* buf, int buflen) {
   return LC_OK;
 }
 
+// The two append-to-cache entries (fp16 and fp8 pools) each state an AppendCall; check_kv_append (tu_plan.hip) checks it; append_run and append_name
+// run and name it.  (AppendCall: B, Hkv, Nq, D, flags, kv_bytes, num_pages, page_size, max_pages)
+int append_run(const AppendCall& c, const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len,
+               const float* k_scale, const float* v_scale, void* stream) {
+  const AppendPtrs a{static_cast<const half_t*>(Knew), static_cast<const half_t*>(Vnew), Kpool, Vpool, block_table, kv_len, k_scale, v_scale,
+                     static_cast<hipStream_t>(stream)};
+  if (int rc = check_kv_append(c, &a)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_kv_append(c, a);
+}
+int append_name(const AppendCall& c, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  if (int rc = check_kv_append(c, nullptr)) return rc;
+  format_kv_append(c, buf, buflen);
+  return LC_OK;
+}
+
 // warmup + iters calls of `launch` (returns a status) between two events (lc_hgemm_time, lc_attn_time): ms per timed call
 template <typename Launch>
 int time_launches(int warmup, int iters, void* stream, float* ms_per_launch, Launch launch) {
@@ -364,6 +381,28 @@ size_t lc_attn_decode_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, i
 
 int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
   return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1), buf, buflen);
+}
+
+int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,
+                           int Nq, int num_pages, int page_size, int max_pages, int D, int flags, void* stream) {
+  return append_run(AppendCall{B, Hkv, Nq, D, flags, 2, num_pages, page_size, max_pages}, Knew, Vnew, Kpool, Vpool, block_table, kv_len, nullptr, nullptr,
+                    stream);
+}
+
+int lc_kv_append_paged_kv8(const void* Knew, const void* Vnew, void* Kpool8, void* Vpool8, const int* block_table, const int* kv_len,
+                           const float* k_scale, const float* v_scale, int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
+                           int flags, void* stream) {
+  return append_run(AppendCall{B, Hkv, Nq, D, flags, 1, num_pages, page_size, max_pages}, Knew, Vnew, Kpool8, Vpool8, block_table, kv_len, k_scale,
+                    v_scale, stream);
+}
+
+// (the name calls take no num_pages: it decides nothing)
+int lc_kv_append_paged_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
+  return append_name(AppendCall{B, Hkv, Nq, D, flags, 2, 1, page_size, max_pages}, buf, buflen);
+}
+
+int lc_kv_append_paged_kv8_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
+  return append_name(AppendCall{B, Hkv, Nq, D, flags, 1, 1, page_size, max_pages}, buf, buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -171,4 +171,26 @@ int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace
 template <DecodeCache C>
 int launch_attn_decode_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
+// What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
+// DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on
+// B x Hkv x ceil(Nq / (2048 / D)) workgroups, no workspace.
+struct AppendCall {
+  int B, Hkv, Nq, D, flags;
+  int kv_bytes;                          // bytes of a pool element: 2 (fp16) or 1 (e4m3)
+  int num_pages, page_size, max_pages;   // (the name calls state num_pages = 1: it decides nothing)
+};
+struct AppendPtrs {
+  const half_t *Knew, *Vnew;             // [B,Hkv,Nq,D] fp16
+  void *Kpool, *Vpool;                   // [num_pages,Hkv,page_size,D] of kv_bytes an element
+  const int *block_table, *kv_len;       // device int32[B, max_pages], int32[B] (the lengths AFTER the append)
+  const float *k_scale, *v_scale;        // kv_bytes = 1: device float[Hkv] or nullptr = 1.0; else nullptr
+  hipStream_t st;
+};
+inline int kv_append_tokens_per_block(int D) { return D == 64 ? 32 : 16; }   // 2048 / D for the head dims there are; the grid bound's figure for the rest
+// The checks of the two append entry points, in the order that decides which status a doubly-bad call gets.  a: the run call's pointers (nullptr:
+// a name call, which has none)
+int check_kv_append(const AppendCall& c, const AppendPtrs* a);
+void format_kv_append(const AppendCall& c, char* buf, int buflen);   // "kv_append_paged_kernel<128>" / "kv_append_paged_kv8_kernel<128>"
+int launch_kv_append(const AppendCall& c, const AppendPtrs& a);      // tu_kv_append.hip; checked arguments
+
 }  // namespace lc

@@ -728,6 +728,29 @@ void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   else snprintf(buf, buflen, "%s<%d,%d>", kern, p.call.D, p.RT);
 }
 
+// Append to the paged cache (lc_plan.h AppendCall).  The page geometry and the span bound are check_attn_decode's, so that every pool an append
+// accepts is one the decode call of the same step accepts; Nq is not bounded by the decode kernel's row tiles: a prefill writes whole prompts.
+int check_kv_append(const AppendCall& c, const AppendPtrs* a) {
+  auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
+  if (c.flags != 0) return LC_ERR_ARG;   // no flag is defined
+  if (a && (!a->Knew || !a->Vnew || !a->Kpool || !a->Vpool || !a->block_table || !a->kv_len)) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
+  if (c.B <= 0 || c.Hkv <= 0 || c.Nq <= 0 || c.num_pages <= 0 || c.max_pages <= 0 || c.D <= 0) return LC_ERR_SHAPE;
+  if (c.page_size < 16 || (c.page_size & (c.page_size - 1)) != 0) return LC_ERR_SHAPE;
+  const long ncap = (long)c.max_pages * c.page_size;
+  if (ncap > 0x7fffffffL) return LC_ERR_SHAPE;
+  // one (page, head) run stays below 2 GiB — the kernel's 32-bit offsets inside a run — by the decode calls' bound on Ncap rows
+  if ((size_t)ncap * (size_t)c.D * (size_t)c.kv_bytes >= 0x80000000ull) return LC_ERR_SHAPE;
+  // 1-D grid of B x Hkv x ceil(Nq / tokens per workgroup) workgroups (each factor < 2^31: no product here overflows 64 bits)
+  const size_t bh = (size_t)c.B * c.Hkv;
+  if (bh > 0x7fffffffull || bh * (((size_t)c.Nq - 1) / kv_append_tokens_per_block(c.D) + 1) > 0x7fffffffull) return LC_ERR_SHAPE;
+  if (a && (!aligned16(a->Knew) || !aligned16(a->Vnew) || !aligned16(a->Kpool) || !aligned16(a->Vpool))) return LC_ERR_SHAPE;
+  if (c.D != 64 && c.D != 128) return LC_ERR_HEADDIM;
+  return LC_OK;
+}
+void format_kv_append(const AppendCall& c, char* buf, int buflen) {
+  snprintf(buf, buflen, c.kv_bytes == 1 ? "kv_append_paged_kv8_kernel<%d>" : "kv_append_paged_kernel<%d>", c.D);
+}
+
 // The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).
 void format_attn(const AttnPlan& p, char* buf, int buflen) {
   const int D = p.call.D;

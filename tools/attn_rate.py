@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P[:kv8]] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P[:kv8][:append[:torch]]] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
           causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
           instead of this library (context only); kvh = K: grouped-query attention, K / V tensors with K heads through lc_attn_fwd_f16_gqa
           (FLOPs counted as for the H query heads); kvh = K with expand: what a caller without that entry does — repeat_interleave K and V
@@ -17,6 +17,10 @@ usage: attn_rate.py [--seconds S] [--rounds R] spec...
           lc_attn_decode_paged_f16 and a block table (combinable with q, len, dsplit, causal; N % P == 0)
           kv8 (with page): that pool quantised to e4m3 with one scale per K / V head (amax / 448), through lc_attn_decode_paged_kv8; its
           K / V GB/s count one byte per element
+          append (with page): instead of the decode call, the APPEND of the q = Nq newest tokens of every sequence (positions L - Nq .. L - 1)
+          to that pool through lc_kv_append_paged_f16 (kv8: lc_kv_append_paged_kv8); append:torch: the same job in torch ops — an index_put_
+          of the rows into the pool viewed as rows (indices computed outside the timing), preceded for kv8 by
+          (x.float() / s).clamp(-448, 448).to(torch.float8_e4m3fn).  Their GB/s count the bytes read + written
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
 cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
 causal: half of that, the flash-attn convention) and the median time per call."""
@@ -41,6 +45,10 @@ while args and args[0].startswith("--"):
 import os  # noqa: E402
 if os.environ.get("LC_AB_LIB"):    # A/B of two builds on one box: point the ctypes view at another copy of the library
     capi.LIB_PATH = Path(os.environ["LC_AB_LIB"]).resolve()
+    import ctypes  # noqa: E402
+    other = ctypes.CDLL(str(capi.LIB_PATH))             # an older build lacks the entries added since: the specs that need one fail, the rest run
+    for missing in [s for s in capi.SYMBOLS if not hasattr(other, s)]:
+        del capi.SYMBOLS[missing]
 capi.load()
 KNOBS = {"bigd_stagger": "attn_bigd_stagger", "bigd_map": "attn_bigd_map", "nw": "attn_nw", "walk": "attn_walk", "d512": "attn_d512", "d1024": "attn_d1024", "sched": "attn_w4i_sched", "split": "attn_split",
          "order": "attn_causal_order", "dsplit": "attn_decode_split"}
@@ -86,6 +94,47 @@ def opt_int(opts, key, default):
     return next((int(o.split("=")[1]) for o in opts if o.startswith(key + "=")), default)
 
 
+def run_append(spec, shape, use_torch, kv8, pool, lens):
+    """(name, bytes read + written in GB/s, ms per call) of appending the q = Nq newest tokens of every sequence to the spec's pools: through
+    lc_kv_append_paged_f16 / _kv8, or (torch) an index_put_ of the rows into the pool viewed as rows — the row indices computed once, outside
+    the timing — preceded for fp8 by the quantisation in torch ops"""
+    B, kvh, nq, N, D, L, page = shape
+    k_pool, v_pool, table, k_scale, v_scale = pool
+    akey = ("append", B, kvh, nq, D)
+    if akey not in cache:
+        for old_key in [x for x in cache if x[0] == "append"]:
+            del cache[old_key]
+        g = torch.Generator(device="cuda").manual_seed(nq)
+        cache[akey] = tuple(torch.randn(B, kvh, nq, D, device="cuda", generator=g).half() for _ in range(2))
+    k_new, v_new = cache[akey]
+    if use_torch:
+        pos = torch.arange(L - nq, L, device="cuda")                                                          # [nq]
+        pid = table.long()[:, pos // page]                                                                     # [B, nq]
+        idx = ((pid.view(B, 1, nq) * kvh + torch.arange(kvh, device="cuda").view(1, kvh, 1)) * page + (pos % page).view(1, 1, nq)).reshape(-1)
+        as_rows = (lambda x: x.view(torch.uint8).view(-1, D)) if kv8 else (lambda x: x.view(-1, D))
+        k_rows, v_rows = as_rows(k_pool), as_rows(v_pool)
+        if kv8:
+            ks, vs = k_scale.view(1, kvh, 1, 1), v_scale.view(1, kvh, 1, 1)
+            quant = lambda x, s: (x.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8).view(-1, D)  # noqa: E731
+
+            def step():
+                k_rows.index_put_((idx,), quant(k_new, ks))
+                v_rows.index_put_((idx,), quant(v_new, vs))
+        else:
+            def step():
+                k_rows.index_put_((idx,), k_new.view(-1, D))
+                v_rows.index_put_((idx,), v_new.view(-1, D))
+        name = "torch index_put_" + (" after quantise" if kv8 else "")
+    else:
+        name = capi.kv_append_paged_kernel_name(B, kvh, nq, page, N // page, D, kv8=kv8)
+        if kv8:
+            step = lambda: capi.kv_append_paged_kv8(k_new, v_new, k_pool, v_pool, table, lens, k_scale, v_scale)  # noqa: E731
+        else:
+            step = lambda: capi.kv_append_paged(k_new, v_new, k_pool, v_pool, table, lens)  # noqa: E731
+    ms = timed(step)
+    return name, 2.0 * B * kvh * nq * D * (2 + (1 if kv8 else 2)) / ms * 1e-6, ms
+
+
 def run_decode(spec, shape, opts):
     """(name, K / V GB/s, ms per call) of one decode call"""
     B, H, N, D = shape
@@ -123,6 +172,10 @@ def run_decode(spec, shape, opts):
                 pools = [(pool.float() / s.view(1, kvh, 1, 1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn) for pool, s in zip(pools, sc)]
             cache[pkey] = (pools[0], pools[1], perm.view(B, mp).to(torch.int32).contiguous(), sc[0], sc[1])
         k_pool, v_pool, table, k_scale, v_scale = cache[pkey]
+    if "append" in opts:
+        if not page or L < nq or causal or "sdpa" in opts:
+            raise SystemExit(f"{spec}: append needs page=P and len >= q, and takes neither causal nor sdpa")
+        return run_append(spec, (B, kvh, nq, N, D, L, page), "torch" in opts, kv8, cache[pkey], lens)
     capi.tune("attn_decode_split", split)
     try:
         if "sdpa" in opts:
@@ -207,6 +260,6 @@ for s in args:
     v, t = sorted(res[s]), sorted(times[s])
     if any(o.startswith("q=") for o in s.split(":")):     # decode: res holds K / V GB/s
         print(f"RATE {s:40s} {names[s]:38s} median {t[len(t) // 2] * 1e3:8.1f} us  best {t[0] * 1e3:8.1f}  worst {t[-1] * 1e3:8.1f}  "
-              f"K/V {v[len(v) // 2]:7.0f} GB/s", flush=True)
+              f"{'R+W' if 'append' in s.split(':') else 'K/V'} {v[len(v) // 2]:7.0f} GB/s", flush=True)
         continue
     print(f"RATE {s:34s} {names[s]:44s} median {v[len(v) // 2]:7.1f}  best {v[-1]:7.1f}  worst {v[0]:7.1f} TFLOP/s  {t[len(t) // 2] * 1e3:9.1f} us", flush=True)
