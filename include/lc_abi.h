@@ -146,7 +146,7 @@ const char* lc_build_info(int* is_diag);
  *   "attn_causal_order" grid order of the causal merged-phase kernel: 0 = auto (longest query block first up to 8 rounds of blocks per CU,
  *                  head-major beyond), 1 = longest block first, 2 = head-major (same bits)
  *   "attn_split"   split-KV of the merged-phase kernel (attn_w4u.hip WALK 3) for grids that do not fill the GPU: 0 = auto (a cost model
- *                  over B x H, N, D and the CU count picks 1 / 2 / 4 / 8 / 16 KV ranges per 256-row query block, lc_abi.hip attn_split_auto),
+ *                  over B x H, N, D and the CU count picks 1 / 2 / 4 / 8 / 16 KV ranges per 256-row query block, tu_plan.hip attn_split_auto),
  *                  1 = off: the merged-phase kernel itself on any grid (also switches off the small-grid substitution below), 2 / 4 / 8 / 16 = that
  *                  factor on any grid (N / 64 divisible by it, >= 2 tiles per range).  Partials live in a
  *                  cached per-stream workspace (a few MiB, never freed); while a stream is being captured the unsplit kernel runs

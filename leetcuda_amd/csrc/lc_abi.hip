@@ -1,6 +1,6 @@
-// lc_abi.hip — the C-ABI of libleetcuda_amd.so (declared in include/lc_abi.h): argument checks, the knob and entry-table calls,
-// HIP-event timing helpers.  What a call runs is decided in tu_plan.hip (lc_plan.h) and launched by tu_core.hip and the other
-// tu_*.hip units (lc_launch.h); this unit holds no kernel.
+// lc_abi.hip — the C-ABI of libleetcuda_amd.so (declared in include/lc_abi.h): each entry point states its call, has it checked and planned, asks the
+// launch guard and launches the plan; the knob and entry-table calls; HIP-event timing helpers.  What a call runs is decided in tu_plan.hip (lc_plan.h) and
+// launched by tu_core.hip and the other tu_*.hip units (lc_launch.h); this unit holds no launch decision and no kernel.
 // Host side of the reference's L2 layer (the `void f(torch::Tensor...)` wrappers at the tail of every
 // reference .cu, e.g. kernels/hgemm/mma/basic/hgemm_mma_stage.cu:2331-2412 and
 // kernels/flash-attn/mma/basic/flash_attn_mma_split_q.cu:701-815) re-expressed on raw pointers.
@@ -15,8 +15,6 @@
 using namespace lc;
 
 namespace {
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // one HGEMM call on one knob snapshot (lc_hgemm_f16, lc_hgemm_call)
 int hgemm_f16(const Knobs& k, const void* A, const void* B, void* C, int M, int N, int K, int layout, int variant, int swizzle_stride, void* stream) {
@@ -115,6 +113,16 @@ int append_name(const AppendCall& c, char* buf, int buflen) {
   if (int rc = check_kv_append(c, nullptr)) return rc;
   format_kv_append(c, buf, buflen);
   return LC_OK;
+}
+
+// The two fp8 GEMM entries each state a GemmFp8Call (M, N, K, swizzle_stride, mx); check_gemm_fp8 (tu_plan.hip) checks and plans it.  PA / PB: the block-scaled call
+int gemm_fp8_run(const GemmFp8Call& c, const void* A, const void* PA, const void* B, const void* PB, void* C, float alpha, void* stream) {
+  const GemmFp8Ptrs a{static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), static_cast<half_t*>(C), static_cast<const uint32_t*>(PA),
+                      static_cast<const uint32_t*>(PB), alpha, static_cast<hipStream_t>(stream)};
+  GemmFp8Plan p;
+  if (int rc = check_gemm_fp8(c, &a, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_gemm_fp8_plan(p, a);
 }
 
 // warmup + iters calls of `launch` (returns a status) between two events (lc_hgemm_time, lc_attn_time): ms per timed call
@@ -236,43 +244,18 @@ int lc_hgemm_f16(const void* A, const void* B, void* C, int M, int N, int K, int
   return hgemm_f16(read_knobs(), A, B, C, M, N, K, layout, variant, swizzle_stride, stream);
 }
 
-int lc_gemm_fp8_e4m3(const void* A, const void* B, void* C, int M, int N, int K, float alpha,
-                     int swizzle_stride, void* stream) {
-  if (!A || !B || !C) return LC_ERR_ARG;
-  if (M <= 0 || N <= 0 || K <= 0) return LC_ERR_SHAPE;
-  if (M % BM || N % BN || K % 128 || !aligned16(A) || !aligned16(B) || !aligned16(C)) return LC_ERR_SHAPE;
-  if (int rc = launch_guard()) return rc;
-  const int tiles_m = M / BM, tiles_n = N / BN;
-  const int pw = panel_tiles(g_tune_hgemm_raster, swizzle_stride, tiles_n, BN, ((size_t)M + N) * K);   // (fp8: one byte per element)
-  const int mx = g_tune_fp8_mx;   // read once per launch
-  if (mx == 3 && gemm_fp8_w4k_fits(K))
-    return launch_gemm_fp8_w4k(static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), static_cast<half_t*>(C), M, N, K, alpha,
-                               tiles_m, tiles_n, pw, static_cast<hipStream_t>(stream));
-  return launch_gemm_fp8(static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), static_cast<half_t*>(C), M, N, K,
-                         alpha, tiles_m, tiles_n, pw, mx == 3 ? 1 : mx, static_cast<hipStream_t>(stream));
+int lc_gemm_fp8_e4m3(const void* A, const void* B, void* C, int M, int N, int K, float alpha, int swizzle_stride, void* stream) {
+  return gemm_fp8_run(GemmFp8Call{M, N, K, swizzle_stride, false}, A, nullptr, B, nullptr, C, alpha, stream);
 }
 
 int lc_mxfp8_pack_scales(const void* S, void* P, int rows, int K, void* stream) {
-  if (!S || !P) return LC_ERR_ARG;
-  if (rows <= 0 || K <= 0) return LC_ERR_SHAPE;
-  if (rows % BM || K % 128 || ((uintptr_t)P & 7)) return LC_ERR_SHAPE;
+  if (int rc = check_mx_pack_scales(S, P, rows, K)) return rc;
   if (int rc = launch_guard()) return rc;
   return launch_mx_pack_scales(static_cast<const uint8_t*>(S), static_cast<uint32_t*>(P), rows, K, static_cast<hipStream_t>(stream));
 }
 
-int lc_gemm_mxfp8(const void* A, const void* PA, const void* B, const void* PB, void* C, int M, int N, int K, float alpha,
-                  int swizzle_stride, void* stream) {
-  if (!A || !B || !C || !PA || !PB) return LC_ERR_ARG;
-  if (M <= 0 || N <= 0 || K <= 0) return LC_ERR_SHAPE;
-  if (M % BM || N % BN || K % 128 || !aligned16(A) || !aligned16(B) || !aligned16(C) || ((uintptr_t)PA & 7) || ((uintptr_t)PB & 7))
-    return LC_ERR_SHAPE;
-  if (!gemm_fp8_w4k_fits(K)) return LC_ERR_SHAPE;   // 32-bit DMA offsets (K < 8 Mi)
-  if (int rc = launch_guard()) return rc;
-  const int tiles_m = M / BM, tiles_n = N / BN;
-  const int pw = panel_tiles(g_tune_hgemm_raster, swizzle_stride, tiles_n, BN, ((size_t)M + N) * K);
-  return launch_gemm_mxfp8(static_cast<const uint8_t*>(A), static_cast<const uint32_t*>(PA), static_cast<const uint8_t*>(B),
-                           static_cast<const uint32_t*>(PB), static_cast<half_t*>(C), M, N, K, alpha, tiles_m, tiles_n, pw,
-                           static_cast<hipStream_t>(stream));
+int lc_gemm_mxfp8(const void* A, const void* PA, const void* B, const void* PB, void* C, int M, int N, int K, float alpha, int swizzle_stride, void* stream) {
+  return gemm_fp8_run(GemmFp8Call{M, N, K, swizzle_stride, true}, A, PA, B, PB, C, alpha, stream);
 }
 
 int lc_hgemm_entry_count(void) { return kNumHgemmEntries; }
@@ -295,26 +278,8 @@ int lc_hgemm_call(const char* entry, const void* A, const void* B, void* C, int 
   if (e->variant == -2) return lc_vendor_init();
   if (e->variant == -3) return lc_vendor_destroy();
   if (e->variant == -1) return lc_hgemm_vendor_f16(A, B, C, M, N, K, e->layout, stream);
-  int variant = e->variant;
   const Knobs k = read_knobs();
-  // the cross-check kernels need 256-multiples and K % 64 == 0; every reference entry must still accept the reference's own
-  // legal shapes (multiples of 128 / K of 32, hgemm_mma_stage.cu:650,675), so fall back per shape: AUTO serves those with the
-  // flagship kernel + border strips, the 128-tile kernel or the edge kernel (plan_hgemm)
-  const bool al = aligned16(A) && aligned16(B) && aligned16(C);
-  const bool tiles256 = (M % BM == 0) && (N % BN == 0) && (K % BK == 0) && al;
-  const bool tiles128 = (M % BM1 == 0) && (N % BN1 == 0) && (K % 32 == 0) && K >= BK && al;
-  if (is_tile256_variant(variant) && !tiles256) variant = LC_HGEMM_AUTO;
-  if (variant == LC_HGEMM_MFMA128 && !tiles128) variant = LC_HGEMM_GENERIC;
-  // Round 6: the entry names that map to the cross-check kernels keep them where those kernels are within a few per cent of the flagship
-  // (large grids: the reference bench's rows stay distinct there), but a 256 x 256 tile on a grid of at most half a CU's worth of tiles
-  // per CU — 2048^3: 64 workgroups, 330 TFLOP/s where LC_HGEMM_AUTO reaches 818 in the reference's own unmodified sweep
-  // (profiles/r6Z_f1_hgemm_default_sweep.log) — serves nobody: such calls, and 128-tile names on shapes the mid-size kernel serves, run
-  // what LC_HGEMM_AUTO runs.
-  if (is_tile256_variant(variant) && variant != LC_HGEMM_MFMA256W4Y && 2L * (M / BM) * (N / BN) <= rule_cus(k)) variant = LC_HGEMM_AUTO;
-  HgemmPlan p;
-  if (variant == LC_HGEMM_MFMA128 && M > 0 && N > 0 && K > 0 && plan_hgemm(k, M, N, K, e->layout == LC_LAYOUT_NN, LC_HGEMM_AUTO, al, &p) == LC_OK &&
-      p.fam == HFam::MID)
-    variant = LC_HGEMM_AUTO;
+  const int variant = hgemm_entry_variant(k, *e, M, N, K, aligned16(A) && aligned16(B) && aligned16(C));   // (the name's own, or what serves the shape)
   const int stride = (e->nargs == 6 && swizzle) ? swizzle_stride : 1;
   return hgemm_f16(k, A, B, C, M, N, K, e->layout, variant, stride, stream);
 }

@@ -1,6 +1,6 @@
 // lc_knobs.inc — THE list of run-time tuning knobs (lc_tune_set / lc_tune_get): experiments and A/B benches, never required for correctness.
 // One row per knob, in the order lc_tune_key reports them:
-//     LC_KNOB(name, default, validator, diagnosis-only)        read where it is used (a launcher, the fp8 entry points)
+//     LC_KNOB(name, default, validator, diagnosis-only)        steers only the inside of a kernel: read by its launcher
 //     LC_KNOB_SNAP(name, default, validator, diagnosis-only)   decides which kernel runs: a field of the per-call snapshot `Knobs`
 // The including site defines LC_KNOB (and LC_KNOB_SNAP where the two differ) and gets both undefined again.  The storage
 // (tune_t g_tune_<name>), its default, the snapshot field and its by-name fill (read_knobs) and the registry row (kKnobs, key = #name) all
@@ -17,7 +17,7 @@ LC_KNOB(attn_bigd_map, 0, ok_02, false)                   // block -> query bloc
 LC_KNOB(attn_bigd_stagger, 0, ok_02, false)               // attn_bigd4 (D = 1024): the KV walk of the workgroups on XCD x starts x eighths of the sequence in: 0 = auto (with the round-robin block map), 1 = off, 2 = on (results agree to rounding)
 LC_KNOB_SNAP(attn_d1024, 0, ok_span8, false)              // attn_bigd4's DMA spread in eighths of a phase: 0 = default (8), 2 / 4 / 6 (A/B knob)
 LC_KNOB_SNAP(attn_w4i_sched, 1, ok_01, false)             // schedule of attn_fwd_w4i_kernel's generated phase statements (tools/gen_attn_w4i.py NSCHED; same bits)
-LC_KNOB(fp8_mx, 3, ok_03, false)                          // fp8 GEMM: 3 = MX K=128 MFMA, generated loop (gemm_fp8_w4k.hip); 1 = MX K=64, 4-wave kernel; 2 = MX K=64, 8-wave kernel; 0 = plain K=16 MFMA
+LC_KNOB_SNAP(fp8_mx, 3, ok_03, false)                     // fp8 GEMM (plan_gemm_fp8): 3 = MX K=128 MFMA, generated loop (gemm_fp8_w4k.hip); 1 = MX K=64, 4-wave kernel; 2 = MX K=64, 8-wave kernel; 0 = plain K=16 MFMA
 LC_KNOB_SNAP(attn_d512, 0, ok_04, false)                  // D = 256 / 512 / 1024: 0 = auto, 1 = column-split kernel, 2 = attn_bigd3, 3 = D = 256 / 512 on the other MFMA shape than auto (attn_bigd2 <-> attn_bigd7 / attn_bigd6), 4 = auto but attn_bigd7 on any grid
 LC_KNOB_SNAP(w4y_sched, 2, ok_w4y_sched, false)           // hgemm_w4y_kernel loop schedule 0..2 (lc_tune_set "w4y_sched"; same bits; 0 / 1: k-step outer; 2 (default): the pair loop, hgemm_w4y_loop_pair.inc — both k-steps of an accumulator block back to back, the DMA pieces spread evenly — fewer joules per MFMA at the power cap, profiles/mfma_pair_probe.log, profiles/hgemm_pair_ab.log)
 LC_KNOB(hgemm_persist, 1, ok_01, false)                   // 1 (default) = hgemm_w4y_kernel as a persistent workgroup per CU when the tiles divide evenly (lc_tune_set "hgemm_persist")

@@ -1,5 +1,5 @@
 // lc_launch.h — pieces shared by the translation units of libleetcuda_amd.so (lc_abi.hip + the tu_*.hip files that
-// hold the kernels and the launch planning, built in parallel by leetcuda_amd/build.py).
+// hold the kernels and the launch planning, built in parallel by leetcuda_amd/build.py).  A launcher runs the plan it is handed (lc_plan.h), no other kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -193,7 +193,7 @@ inline bool stream_is_capturing(hipStream_t st) {
 using tune_t = std::atomic<int>;
 extern tune_t g_tune_attn_bigd_stagger;   // attn_bigd4: the KV walk of XCD x starts x eighths in: 0 = auto (with the round-robin map), 1 = off, 2 = on
 extern tune_t g_tune_attn_bigd_map;     // query-block map of attn_bigd4 / attn_bigd6: 0 = auto (D = 1024 round-robin over the XCDs, D = 512 XCD-contiguous), 1 = contiguous, 2 = round-robin
-extern tune_t g_tune_hgemm_persist;   // 1 (default) = hgemm_w4y_kernel as a persistent workgroup per CU when the tiles divide evenly (tu_w4.hip)
+extern tune_t g_tune_hgemm_persist;   // 1 (default) = hgemm_w4y_kernel as a persistent workgroup per CU when the tiles divide evenly (persist_walk)
 extern tune_t g_tune_hgemm_stagger;   // K-loop stagger of hgemm_w4y_kernel: 0 = auto (by XCD, step K / 64 / 8), 1 << 27 (exactly) = off, else cx | cm << 4 | cn << 8 | step << 12 | mask << 20 with mask < 128 (hgemm_w4y.hip)
 // the kernel argument of the K-loop stagger for a K walk of kt tiles: auto (knob 0) = by XCD, the eight start tiles spread evenly
 // over the K range (L2 sharing inside an XCD stays intact, fabric bytes unchanged: profiles/r3q_hgemm_stagger_ab.log).  The mask
@@ -206,6 +206,14 @@ inline int stagger_arg(int kt) {
   if (knob != 0) return knob;
   const int step = kt / 8;
   return 1 | (step < 1 ? 1 : step > 255 ? 255 : step) << 12 | 7 << 20;
+}
+// The persistent walk of hgemm_w4y_kernel and gemm_fp8_w4k_kernel (lc_tune_set "hgemm_persist" = 1): one workgroup per CU walks the nblk block ids, only when every
+// workgroup gets the same number of tiles (a ragged walk would leave CUs idle for a whole tile).  grid: the workgroups; nblk: the kernels' last argument, 0 = not persistent
+struct PersistWalk { int grid, nblk; };
+inline PersistWalk persist_walk(int nblk) {
+  const int ncu = device_cu_count();
+  const bool persist = g_tune_hgemm_persist != 0 && nblk > ncu && nblk % ncu == 0;
+  return PersistWalk{persist ? ncu : nblk, persist ? nblk : 0};
 }
 
 // launchers living in their own translation units
@@ -322,15 +330,7 @@ int launch_attn_bigd6(const AttnPtrs& a, int BH, int N, bool bf16);
 // tu_attn_big7.hip: D = 256, 64 query rows per wave on v_mfma_f32_16x16x32 (attn_bigd7.hip), N % 256 == 0, V as [B,H,N,D]; fp16 or bf16
 int launch_attn_bigd7(const AttnPtrs& a, int BH, int N, bool bf16);
 int launch_attn_bigd7_vt(const AttnPtrs& a, int BH, int N);   // V as [B,H,D,N], fp16
-// tu_fp8.hip: fp8 e4m3 GEMM, mx = 1 (MX, 4 waves) / 2 (MX, 8 waves) / 0 (plain K = 16)
-int launch_gemm_fp8(const uint8_t* A, const uint8_t* B, half_t* C, int M, int N, int K, float alpha, int tiles_m,
-                    int tiles_n, int panel_w, int mx, hipStream_t st);
-// tu_fp8k.hip: the K = 128 MX form (gemm_fp8_w4k.hip): unit scales / real E8M0 block scales packed by launch_mx_pack_scales
-bool gemm_fp8_w4k_fits(int K);
-int launch_gemm_fp8_w4k(const uint8_t* A, const uint8_t* B, half_t* C, int M, int N, int K, float alpha, int tiles_m, int tiles_n,
-                        int panel_w, hipStream_t st);
-int launch_gemm_mxfp8(const uint8_t* A, const uint32_t* PA, const uint8_t* B, const uint32_t* PB, half_t* C, int M, int N, int K,
-                      float alpha, int tiles_m, int tiles_n, int panel_w, hipStream_t st);
+// tu_fp8.hip, tu_fp8k.hip run a GemmFp8Plan (lc_plan.h launch_gemm_fp8_plan); tu_fp8k.hip: the scales of the K = 128 MX form as its kernel reads them
 int launch_mx_pack_scales(const uint8_t* S, uint32_t* P, int rows, int K, hipStream_t st);
 
 }  // namespace lc

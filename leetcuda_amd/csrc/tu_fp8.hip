@@ -1,27 +1,23 @@
 // tu_fp8.hip — translation unit of the fp8 GEMM kernels (gemm_fp8.hip) — see lc_launch.h
-#include "lc_launch.h"
+#include "lc_plan.h"
 #include "gemm_fp8.hip"
 
 namespace lc {
-int launch_gemm_fp8(const uint8_t* A, const uint8_t* B, half_t* C, int M, int N, int K, float alpha, int tiles_m,
-                    int tiles_n, int pw, int mx, hipStream_t st) {
-  // MX + 4-wave kernel (mx = 1) unless a buffer offset could reach 2 GiB; mx = 2: MX 8-wave kernel; 0: plain K = 16
-  if (mx == 1 && (size_t)K * 260 < ((size_t)1 << 31)) {   // (a wave's pieces reach 232 rows past its base)
-    auto kern = gemm_fp8_w4_kernel;
-    if (int rc = set_dyn_lds(kern, W4B_LDS)) return rc;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(256), W4B_LDS, st, A, B, C, M, N, K, alpha, tiles_m,
-                       tiles_n, pw, stagger_arg(K / BK8));   // K-loop stagger as hgemm_w4y (lc_launch.h)
-  } else if (mx) {
-    auto kern = gemm_fp8_pingpong2_kernel<true>;
-    if (int rc = set_dyn_lds(kern, HGEMM256_LDS)) return rc;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), HGEMM256_LDS, st, A, B, C, M, N, K, alpha, tiles_m,
-                       tiles_n, pw);
-  } else {
-    auto kern = gemm_fp8_pingpong2_kernel<false>;
-    if (int rc = set_dyn_lds(kern, HGEMM256_LDS)) return rc;
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), HGEMM256_LDS, st, A, B, C, M, N, K, alpha, tiles_m,
-                       tiles_n, pw);
-  }
+// one workgroup per 256 x 256 tile of the plan; extra: the kernel's arguments behind the panel width
+template <typename KernelT, typename... Extra>
+static int launch_tiles(KernelT kern, int threads, int lds, const GemmFp8Plan& p, const GemmFp8Ptrs& a, Extra... extra) {
+  if (int rc = set_dyn_lds(kern, lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(threads), lds, a.st, a.A, a.B, a.C, p.call.M, p.call.N, p.call.K, a.alpha, p.tiles_m,
+                     p.tiles_n, p.panel_w, extra...);
   return check_launch();
+}
+
+int launch_gemm_fp8_plan(const GemmFp8Plan& p, const GemmFp8Ptrs& a) {
+  switch (p.kern) {
+    case Fp8Kern::W4: return launch_tiles(gemm_fp8_w4_kernel, 256, W4B_LDS, p, a, stagger_arg(p.call.K / BK8));   // K-loop stagger as hgemm_w4y (lc_launch.h)
+    case Fp8Kern::PINGPONG2_MX: return launch_tiles(gemm_fp8_pingpong2_kernel<true>, 512, HGEMM256_LDS, p, a);
+    case Fp8Kern::PINGPONG2: return launch_tiles(gemm_fp8_pingpong2_kernel<false>, 512, HGEMM256_LDS, p, a);
+    default: return launch_gemm_fp8_w4k_plan(p, a);   // tu_fp8k.hip
+  }
 }
 }  // namespace lc

@@ -1,33 +1,21 @@
 // tu_fp8k.hip — translation unit of the K = 128 MX fp8 GEMM kernel (gemm_fp8_w4k.hip) — see lc_launch.h
-#include "lc_launch.h"
+#include "lc_plan.h"
 #include "gemm_fp8_w4k.hip"
 
 namespace lc {
-namespace {
 template <bool MX>
-int launch_w4k(const uint8_t* A, const uint8_t* B, half_t* C, int M, int N, int K, float alpha, int tiles_m, int tiles_n, int pw,
-               const uint32_t* PA, const uint32_t* PB, hipStream_t st) {
+static int launch_w4k(const GemmFp8Plan& p, const GemmFp8Ptrs& a) {
   auto kern = gemm_fp8_w4k_kernel<MX>;
   if (int rc = set_dyn_lds(kern, W4B_LDS)) return rc;
-  // persistent workgroups under hgemm_w4y's rule (lc_tune_set "hgemm_persist"): one per CU when every one gets the same number of tiles
-  const int nblk = tiles_m * tiles_n, ncu = device_cu_count();
-  const bool persist = g_tune_hgemm_persist != 0 && nblk > ncu && nblk % ncu == 0;
-  hipLaunchKernelGGL(kern, dim3(persist ? ncu : nblk), dim3(256), W4B_LDS, st, A, B, C, M, N, K, alpha, tiles_m, tiles_n, pw,
-                     stagger_arg(K / BK8K), persist ? nblk : 0, PA, PB);
+  const PersistWalk w = persist_walk(p.tiles_m * p.tiles_n);   // persistent workgroups under hgemm_w4y's rule (lc_launch.h)
+  hipLaunchKernelGGL(kern, dim3(w.grid), dim3(256), W4B_LDS, a.st, a.A, a.B, a.C, p.call.M, p.call.N, p.call.K, a.alpha, p.tiles_m, p.tiles_n,
+                     p.panel_w, stagger_arg(p.call.K / BK8K), w.nblk, a.PA, a.PB);
   return check_launch();
 }
-}  // namespace
 
-bool gemm_fp8_w4k_fits(int K) { return (size_t)K * 260 < ((size_t)1 << 31); }   // 32-bit DMA offsets: a wave's pieces reach 232 rows past its base
-
-int launch_gemm_fp8_w4k(const uint8_t* A, const uint8_t* B, half_t* C, int M, int N, int K, float alpha, int tiles_m, int tiles_n, int pw,
-                        hipStream_t st) {
-  return launch_w4k<false>(A, B, C, M, N, K, alpha, tiles_m, tiles_n, pw, nullptr, nullptr, st);
-}
-
-int launch_gemm_mxfp8(const uint8_t* A, const uint32_t* PA, const uint8_t* B, const uint32_t* PB, half_t* C, int M, int N, int K, float alpha,
-                      int tiles_m, int tiles_n, int pw, hipStream_t st) {
-  return launch_w4k<true>(A, B, C, M, N, K, alpha, tiles_m, tiles_n, pw, PA, PB, st);
+int launch_gemm_fp8_w4k_plan(const GemmFp8Plan& p, const GemmFp8Ptrs& a) {
+  if (p.kern == Fp8Kern::W4K) return launch_w4k<false>(p, a);
+  return p.kern == Fp8Kern::W4K_MX ? launch_w4k<true>(p, a) : LC_ERR_ARG;
 }
 
 int launch_mx_pack_scales(const uint8_t* S, uint32_t* P, int rows, int K, hipStream_t st) {

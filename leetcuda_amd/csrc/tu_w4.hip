@@ -27,12 +27,8 @@ int launch_w4x_one(const half_t* A, const half_t* B, half_t* C, int M, int N, in
   if constexpr (Y < 0) {
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), W4B_LDS, st, A, B, C, M, N, K, tiles_m, tiles_n, pw);
   } else {
-    // lc_tune_set "hgemm_persist" = 1: one workgroup per CU walks the block ids (hgemm_w4y.hip); only when every workgroup gets the
-    // same number of tiles (a ragged walk would leave CUs idle for a whole tile)
-    const int ncu = device_cu_count();
-    const bool persist = g_tune_hgemm_persist != 0 && nblk > ncu && nblk % ncu == 0;
-    hipLaunchKernelGGL(kern, dim3(persist ? ncu : nblk), dim3(256), W4B_LDS, st, A, B, C, M, N, K, tiles_m, tiles_n, pw,
-                       stagger_arg(K / BK), persist ? nblk : 0);
+    const PersistWalk w = persist_walk(nblk);   // one workgroup per CU walks the block ids (hgemm_w4y.hip), or one per block (lc_launch.h)
+    hipLaunchKernelGGL(kern, dim3(w.grid), dim3(256), W4B_LDS, st, A, B, C, M, N, K, tiles_m, tiles_n, pw, stagger_arg(K / BK), w.nblk);
   }
   return check_launch();
 }
