@@ -154,7 +154,8 @@ const char* lc_build_info(int* is_diag);
  *                  128-row workgroups fill twice the CUs (+ 9 ... 12 %)
  *   "attn_decode_split" KV ranges per (batch, K / V head) of lc_attn_decode_f16: 0 = auto (the smallest S that gives every CU a workgroup, at least 4
  *                  tiles of 64 cache positions of Ncap per range, at most 64), 1 .. 64 = exactly that many (ranges may be empty: the small test
- *                  shapes reach the split path that way); the name call reports it as " xS"
+ *                  shapes reach the split path that way); the name call reports it as " xS".  The paged, fp8 and chunk entries read the
+ *                  same knob (a chunk call counts its row blocks among the workgroups the rule hands out)
  *   "attn_bigd_map" block -> query block map of the D = 1024 / D = 512 kernels: 1 = every XCD owns consecutive query blocks of a head (its 32
  *                  CUs share one pass over the head's K / V: the fewest fabric bytes), 2 = round-robin over the XCDs (every XCD streams every
  *                  head: ~2 x the fabric bytes, but the 8 XCDs walk the same heads out of the Infinity Cache); 0 = auto: 2 for D = 1024
@@ -332,7 +333,7 @@ int lc_attn_kernel_name_gqa(int BH, int G, int N, int D, int flags, char* buf, i
  * split-KV form legal while `stream` is being captured.  Without it the split-KV form keeps its partials in the stream's cached workspace
  * (lc_workspace_bytes); a stream that is being captured then runs the one-launch form (S = 1).
  * Restrictions: D in {64, 128} (else LC_ERR_HEADDIM); R = G x Nq query rows per K / V head, 1 <= R <= 64 (else LC_ERR_SHAPE: chunked
- * prefill against a cache is out of scope); LC_ATTN_V_TRANSPOSED and unknown flag bits: LC_ERR_ARG; Hkv < 1, Hkv > H, H % Hkv != 0,
+ * prefill against a cache is lc_attn_chunk_f16 below); LC_ATTN_V_TRANSPOSED and unknown flag bits: LC_ERR_ARG; Hkv < 1, Hkv > H, H % Hkv != 0,
  * non-positive dims, one head's Ncap x D x 2 >= 2 GiB, pointers not 16-byte aligned: LC_ERR_SHAPE.  Checks in lc_attn_fwd_f16_gqa's order
  * (flags / null pointer, then shape, then head dim; then a non-NULL workspace that is too small or not 16-byte aligned: LC_ERR_ARG), all
  * before any device work.
@@ -455,6 +456,50 @@ int lc_kv_append_paged_kernel_name(int B, int Hkv, int Nq, int page_size, int ma
                                    int flags, char* buf, int buflen);
 int lc_kv_append_paged_kv8_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D,
                                        int flags, char* buf, int buflen);
+
+/* EXTENSION: chunked-prefill attention over the three KV caches (attn_chunk.hip): lc_attn_decode_f16,
+ * lc_attn_decode_paged_f16 and lc_attn_decode_paged_kv8 with the bound R = (H / Hkv) x Nq <= 64 REMOVED — what attends over a chunk of a prompt
+ * that lc_kv_append_paged_* just wrote (chunked prefill, prefill behind a shared or cached prefix, speculative verification with many draft
+ * tokens, MQA with G = 64 and Nq >= 2), with no gather of the pages and no mask built by hand.
+ * Every argument, argument for argument, is that of the decode entry of the same cache kind, and so is everything its comment says: Q, O
+ * [B,H,Nq,D] fp16; kv_len is the length AFTER the chunk was appended; LC_ATTN_CAUSAL is bottom-right aligned (query i sees keys j <= L_b - Nq + i);
+ * a row with no visible key gets O = 0; D in {64, 128}; page ids are clamped in the kernel; nothing is read at logical positions >= L_b or in
+ * table entries at positions >= ceil(L_b / page_size); the workspace rules and the capture / failed-lease fallback to S = 1; the checks and
+ * their order, with ONE difference: R > 64 is not an error (R is computed in 64 bits), and the grid bound is B x Hkv x RB x 64 <= 2^31 - 1 with
+ * RB = ceil(R / 64).
+ * R <= 64 through a chunk entry IS the decode call: same plan, same kernel name, same bits.  A caller needs one call site.
+ * R > 64: attn_chunk_kernel<D> / attn_chunk_paged_kernel<D> / attn_chunk_paged_kv8_kernel<D> (four row tiles of 16, the decode body) on
+ * B x Hkv x RB x S workgroups, block rb of a (batch, K / V head) owning rows 64 rb .. of its [R,D] matrix; S > 1: + attn_decode_combine_kernel<D>
+ * over S x B H Nq x (D + 1) floats.  S follows the decode rule with B x Hkv x RB groups; "attn_decode_split" forces it.  With LC_ATTN_CAUSAL a
+ * block walks only the keys some row of it can see (below L_blk = clamp(L_b - Nq + i_max + 1, 0, L_b), i_max the block's last token, Nq - 1
+ * where the block straddles a head boundary): a block of a call with Nq % 64 == 0 computes, bit for bit, what the decode call computes on its
+ * 64 query rows with kv_len = L_blk.  The bit-identity notes of the paged and fp8 decode calls (against the gathered / dequantised cache at equal
+ * S) hold for the chunk calls.
+ * Each row block streams its visible K / V again (only L2 shares the reads): expect a rate well below lc_attn_fwd_f16_gqa's causal kernel at
+ * large Nq; the call serves what that kernel cannot (Nq != Nk, paged and fp8 caches).
+ * The name calls never launch: R > 64: "attn_chunk_kernel<D>", "attn_chunk_paged_kernel<D>", "attn_chunk_paged_kv8_kernel<D>", with S > 1
+ * followed by " xS"; R <= 64: the decode entry's name. */
+int lc_attn_chunk_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len,
+                      int B, int H, int Hkv, int Nq, int Ncap, int D, int flags,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_chunk_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D);
+int lc_attn_chunk_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, char* buf, int buflen);
+int lc_attn_chunk_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                            const int* block_table, const int* kv_len,
+                            int B, int H, int Hkv, int Nq,
+                            int num_pages, int page_size, int max_pages, int D, int flags,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_chunk_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D);
+int lc_attn_chunk_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                    int flags, char* buf, int buflen);
+int lc_attn_chunk_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O,
+                            const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                            int B, int H, int Hkv, int Nq,
+                            int num_pages, int page_size, int max_pages, int D, int flags,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_chunk_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D);
+int lc_attn_chunk_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                        int flags, char* buf, int buflen);
 
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */

@@ -61,6 +61,15 @@ SYMBOLS = {
     "lc_attn_decode_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_decode_paged_kv8_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "lc_attn_decode_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_chunk_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_chunk_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "lc_attn_chunk_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_chunk_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_chunk_paged_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "lc_attn_chunk_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_chunk_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_chunk_paged_kv8_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "lc_attn_chunk_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
     "lc_kv_append_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
@@ -451,7 +460,7 @@ def _decode_kernel_name(symbol, *shape, causal) -> str:
     return buf.value.decode()
 
 
-def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None):
+def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None, *, _entry="lc_attn_decode_f16"):
     """Decode attention over a KV cache (lc_attn_decode_f16): q, o [B,H,Nq,D] fp16; k, v [B,Hkv,Ncap,D] fp16; kv_len None (= Ncap) or a
     DEVICE int32 [B] tensor of valid cache lengths, read by the kernel; causal: query i sees keys j <= kv_len[b] - Nq + i.  workspace: None or
     a device tensor of at least attn_decode_workspace_bytes(...) bytes (makes the split-KV form legal under graph capture)."""
@@ -462,8 +471,8 @@ def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None):
     if kv_len is not None:
         _need_gpu(kv_len)
         assert kv_len.dtype == torch.int32
-    check(load().lc_attn_decode_f16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, *dims,
-                                    ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), "lc_attn_decode_f16")
+    check(getattr(load(), _entry)(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, *dims,
+                                  ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
     return o
 
 
@@ -477,7 +486,7 @@ def attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False) -> str:
     return _decode_kernel_name("lc_attn_decode_kernel_name", B, H, Hkv, Nq, Ncap, D, causal=causal)
 
 
-def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None):
+def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None, *, _entry="lc_attn_decode_paged_f16"):
     """Decode attention over a paged KV cache (lc_attn_decode_paged_f16): q, o [B,H,Nq,D] fp16; k_pool, v_pool [num_pages,Hkv,page_size,D]
     fp16, page_size a power of two >= 16; block_table a DEVICE int32 [B,max_pages] tensor of pool page ids; kv_len a DEVICE int32 [B] tensor;
     both are read by the kernel only (page ids are clamped to the pool there).  causal, workspace: as attn_decode."""
@@ -487,8 +496,8 @@ def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, w
     dims = _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len)
     _need_gpu(block_table, kv_len)
     assert block_table.dtype == torch.int32 and kv_len.dtype == torch.int32
-    check(load().lc_attn_decode_paged_f16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), *dims,
-                                          ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), "lc_attn_decode_paged_f16")
+    check(getattr(load(), _entry)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), *dims,
+                                  ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
     return o
 
 
@@ -524,15 +533,16 @@ def _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale):
     return dims
 
 
-def attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=None, v_scale=None, causal=False, workspace=None):
+def attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=None, v_scale=None, causal=False, workspace=None, *,
+                          _entry="lc_attn_decode_paged_kv8"):
     """Decode attention over a paged KV cache kept in fp8 (lc_attn_decode_paged_kv8): attn_decode_paged with k_pool8, v_pool8
     [num_pages,Hkv,page_size,D] of torch.float8_e4m3fn (or its bytes as uint8) and k_scale, v_scale DEVICE float32 [Hkv] tensors (None = 1.0):
     K = k_scale[g] K8, V = v_scale[g] V8.  The scales are read by the kernel only, like block_table and kv_len."""
     dims = _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale)
     _need_gpu(q, k_pool8, v_pool8, o, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
-    check(load().lc_attn_decode_paged_kv8(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(block_table), _ptr(kv_len),
-                                          _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
-                                          *dims, ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), "lc_attn_decode_paged_kv8")
+    check(getattr(load(), _entry)(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(block_table), _ptr(kv_len),
+                                  _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
+                                  *dims, ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
     return o
 
 
@@ -544,6 +554,56 @@ def attn_decode_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D
 def attn_decode_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
     """The kernel attn_decode_paged_kv8 runs for this shape under the current knobs: "attn_decode_paged_kv8_kernel<D,RT>", + " xS" with S > 1."""
     return _decode_kernel_name("lc_attn_decode_paged_kv8_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
+
+
+# Chunked-prefill attention (lc_attn_chunk_*; DESIGN.md section 4.3i): the decode calls with R = (H / Hkv) x Nq unbounded.  The arguments and the
+# Python-side checks are those of attn_decode*; R <= 64 is the decode call itself (same plan, name and bits).
+
+def attn_chunk(q, k, v, o, kv_len=None, causal=False, workspace=None):
+    """attn_decode without the bound R = (H / Hkv) x Nq <= 64 (lc_attn_chunk_f16): a chunk of Nq query tokens per sequence over a contiguous
+    cache; kv_len is the length AFTER the chunk was appended, causal is bottom-right aligned."""
+    return attn_decode(q, k, v, o, kv_len, causal=causal, workspace=workspace, _entry="lc_attn_chunk_f16")
+
+
+def attn_chunk_workspace_bytes(B, H, Hkv, Nq, Ncap, D) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs (0: one launch, no workspace)."""
+    return int(load().lc_attn_chunk_workspace_bytes(B, H, Hkv, Nq, Ncap, D))
+
+
+def attn_chunk_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False) -> str:
+    """The kernel attn_chunk runs: R > 64: "attn_chunk_kernel<D>", + " xS" with S > 1 KV ranges; R <= 64: attn_decode_kernel_name's."""
+    return _decode_kernel_name("lc_attn_chunk_kernel_name", B, H, Hkv, Nq, Ncap, D, causal=causal)
+
+
+def attn_chunk_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None):
+    """attn_decode_paged without the bound on R (lc_attn_chunk_paged_f16): what follows kv_append_paged of a chunk of a prompt."""
+    return attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=causal, workspace=workspace, _entry="lc_attn_chunk_paged_f16")
+
+
+def attn_chunk_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs: those of attn_chunk at Ncap = max_pages x page_size."""
+    return int(load().lc_attn_chunk_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D))
+
+
+def attn_chunk_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
+    """R > 64: "attn_chunk_paged_kernel<D>", + " xS" with S > 1; R <= 64: attn_decode_paged_kernel_name's."""
+    return _decode_kernel_name("lc_attn_chunk_paged_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
+
+
+def attn_chunk_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=None, v_scale=None, causal=False, workspace=None):
+    """attn_decode_paged_kv8 without the bound on R (lc_attn_chunk_paged_kv8): what follows kv_append_paged_kv8 of a chunk of a prompt."""
+    return attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale, causal=causal, workspace=workspace,
+                                 _entry="lc_attn_chunk_paged_kv8")
+
+
+def attn_chunk_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs: those of attn_chunk_paged for the same shape."""
+    return int(load().lc_attn_chunk_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D))
+
+
+def attn_chunk_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
+    """R > 64: "attn_chunk_paged_kv8_kernel<D>", + " xS" with S > 1; R <= 64: attn_decode_paged_kv8_kernel_name's."""
+    return _decode_kernel_name("lc_attn_chunk_paged_kv8_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
 
 
 def _kv_append_args(k_new, v_new, k_pool, v_pool, block_table, kv_len, k_scale=None, v_scale=None, kv8=False):

@@ -79,6 +79,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
                                                           half_t* __restrict__ O, const int* __restrict__ kv_len, float* __restrict__ part_o,
                                                           float* __restrict__ part_lse, int H, int Hkv, int Nq, int Ncap, int causal, int S,
                                                           float sl2, long total_rows) {
+  constexpr bool CHUNK = false;
   constexpr bool PAGED = false;
   const DecodePaging pg{};
   constexpr bool KV8 = false;

@@ -4,6 +4,11 @@
 // the two consumers and applies the per-head scales in fp32.  The including kernel has the template parameters D, RT, the parameters Q, K, V, O,
 // kv_len, part_o, part_lse, H, Hkv, Nq, Ncap, causal, S, sl2, total_rows, a `constexpr bool PAGED` with a `const DecodePaging pg` (PAGED = false:
 // unused) and a `constexpr bool KV8` with a `const DecodeKv8 kv8` (KV8 = false: unused) in scope.  See attn_decode.hip for the design.
+// A `constexpr bool CHUNK` is in scope too.  CHUNK = false: the workgroup holds all R <= 64 rows of its (batch, K / V head).  CHUNK = true (the
+// attn_chunk_*_kernel<D> of attn_chunk.hip, RT = 4; DESIGN.md §4.3i): R is unbounded, the grid has RB = ceil(R / 64) row blocks per (batch, K / V
+// head), ((b Hkv + kvh) RB + rb) S + s, and this workgroup owns rows 64 rb ... of the [R, D] matrix; causal, it walks only the keys below L_blk,
+// the largest limit of its rows.  With CHUNK = false the block offset `rbase` is the constant 0 and the walked length `Lw` is L_b: the nine
+// decode kernels' code does not depend on the parameter (DESIGN.md §4.3i compares their assembly).
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -26,13 +31,31 @@
   const int tid = threadIdx.x, lane = tid & 63, w = wave_id();
   const int i16 = lane & 15, h = lane >> 4;
   // (integer division runs on the vector ALU: readfirstlane tells hipcc that the quotients are wave-uniform — scalar addressing, a scalar tile loop)
-  const int bk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)S)), s_idx = (int)blockIdx.x - bk * S;
+  const int bks = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / (unsigned)S)), s_idx = (int)blockIdx.x - bks * S;
+  int bk = bks, rbase = 0;   // rbase: the first row of this workgroup's row block (CHUNK = false: 0, the only block)
+  if constexpr (CHUNK) {
+    const int RB = __builtin_amdgcn_readfirstlane(((H / Hkv) * Nq + 63) / 64);
+    bk = __builtin_amdgcn_readfirstlane(bks / RB);
+    rbase = 64 * (bks - bk * RB);
+  }
   const int b = __builtin_amdgcn_readfirstlane(bk / Hkv), kvh = bk - b * Hkv;
   const int G = __builtin_amdgcn_readfirstlane(H / Hkv), R = G * Nq;
   int Lb = kv_len ? kv_len[b] : Ncap;
   Lb = __builtin_amdgcn_readfirstlane(Lb);   // (a vector load of a uniform address: tell hipcc that the tile loop is wave-uniform)
   Lb = Lb < 0 ? 0 : (Lb > Ncap ? Ncap : Lb);
-  const int T = (Lb + DEC_KVB - 1) / DEC_KVB;
+  // the keys this workgroup walks: all L_b — CHUNK and causal: those below L_blk = the limit of the row block's last token i_max (Nq - 1 where
+  // the block straddles a head boundary); the tiles, the range partition and the source clamp follow it, the mask keeps using L_b
+  int Lw = Lb;
+  if constexpr (CHUNK) {
+    if (causal) {
+      const int span = (R - rbase < 64 ? R - rbase : 64) - 1;   // last row of the block - first
+      const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nq);
+      const int imax = i0 + span >= Nq ? Nq - 1 : i0 + span;
+      const int v = Lb - Nq + imax + 1;
+      Lw = v < 0 ? 0 : (v > Lb ? Lb : v);
+    }
+  }
+  const int T = (Lw + DEC_KVB - 1) / DEC_KVB;
   // (T < 2^24 tiles — one head's cache is below 2 GiB — and S <= 64: the products fit 32 bits)
   const int t0 = __builtin_amdgcn_readfirstlane((int)((unsigned)(s_idx * T) / (unsigned)S));
   const int t1 = __builtin_amdgcn_readfirstlane((int)((unsigned)((s_idx + 1) * T) / (unsigned)S));
@@ -46,7 +69,7 @@
   // ---- Q -> LDS (rows >= R: row R - 1)
   for (int c = tid; c < 16 * RT * CH; c += 256) {
     const int r = c / CH, ch = c % CH;
-    const int rs = r < R ? r : R - 1;
+    const int rs = rbase + r < R ? rbase + r : R - 1;
     *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Qg + (long)rs * D + ch * 8);
   }
   __syncthreads();
@@ -55,7 +78,7 @@
   int lim[RT];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
-    int r = 16 * rt + i16;
+    int r = rbase + 16 * rt + i16;
     r = r < R ? r : R - 1;
     int v = causal ? Lb - Nq + (r % Nq) + 1 : Lb;
     lim[rt] = v < 0 ? 0 : v;
@@ -79,7 +102,7 @@
   for (int db = 0; db < DB; ++db) tr_off[db] = dec_v_off<D>(4 * h + q4, 2 * db + (p4 >> 1)) + 8 * (p4 & 1);
 
   u32x4_t kf[NKB][KR], vf[VLR];
-  const int last = Lb - 1;   // (>= 0 whenever a tile exists)
+  const int last = Lw - 1;   // (>= 0 whenever a tile exists)
   // step u of this wave: keys key0(u) ... key0(u) + STEP - 1 of tile t0 + w + 4 (u / SPT)
   auto key0 = [&](int u) { return (t0 + w + DEC_WAVES * (u / SPT)) * DEC_KVB + (u % SPT) * STEP; };
   // PAGED: the pool page of each 16-key block of a step.  A block's keys share a page (page_size % 16 == 0), and so do the 4 or 8 key rows of a
@@ -311,7 +334,7 @@
   // ---- wave 0 writes: fp16 O (S == 1) or the normalised fp32 partial + the row's log2-domain log-sum-exp
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
-    const int r = 16 * rt + i16;
+    const int r = rbase + 16 * rt + i16;
     if (r >= R) continue;   // padding rows store nothing
     float inv = lt[rt] > 0.f ? 1.f / lt[rt] : 0.f;
     if constexpr (KV8) inv *= vsc;

@@ -27,6 +27,7 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kv8_kernel(const half_t
                                                                     float* __restrict__ part_o, float* __restrict__ part_lse, int H, int Hkv,
                                                                     int Nq, int Ncap, int causal, int S, float sl2, long total_rows,
                                                                     int num_pages, int lps, int max_pages) {
+  constexpr bool CHUNK = false;
   constexpr bool PAGED = true;
   constexpr bool KV8 = true;
   const DecodePaging pg{block_table, num_pages, lps, max_pages};

@@ -72,9 +72,12 @@ int attn_name(int BH, int G, int N, int D, int flags, bool bf16, int bad_n, char
 
 // The three decode families (contiguous, paged, paged fp8) each state a DecodeCall; check_attn_decode (tu_plan.hip) checks and plans it; decode_run,
 // decode_bytes and decode_name run, size and name the plan.  (DecodeCall: B, H, Hkv, Nq, D, flags, kv_bytes, paged, Ncap, num_pages, page_size, max_pages)
-DecodeCall decode_flat(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags) { return DecodeCall{B, H, Hkv, Nq, D, flags, 2, false, Ncap, 0, 0, 0}; }
-DecodeCall decode_paged(int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, int kv_bytes) {
-  return DecodeCall{B, H, Hkv, Nq, D, flags, kv_bytes, true, 0, num_pages, page_size, max_pages};
+// chunk: the lc_attn_chunk_* entries — the same call with R = (H / Hkv) x Nq unbounded
+DecodeCall decode_flat(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, bool chunk = false) {
+  return DecodeCall{B, H, Hkv, Nq, D, flags, 2, false, Ncap, 0, 0, 0, chunk};
+}
+DecodeCall decode_paged(int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, int kv_bytes, bool chunk = false) {
+  return DecodeCall{B, H, Hkv, Nq, D, flags, kv_bytes, true, 0, num_pages, page_size, max_pages, chunk};
 }
 // block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere)
 int decode_run(const DecodeCall& c, const void* Q, const void* K, const void* V, void* O, const int* kv_len, const int* block_table, const float* k_scale,
@@ -346,6 +349,48 @@ size_t lc_attn_decode_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, i
 
 int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
   return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1), buf, buflen);
+}
+
+// The chunk entries: the decode entries' DecodeCall with chunk = true (R <= 64: the decode call's plan, name and bits)
+int lc_attn_chunk_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len, int B, int H, int Hkv, int Nq, int Ncap, int D,
+                      int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_flat(B, H, Hkv, Nq, Ncap, D, flags, true), Q, K, V, O, kv_len, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+size_t lc_attn_chunk_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D) { return decode_bytes(decode_flat(B, H, Hkv, Nq, Ncap, D, 0, true)); }
+
+int lc_attn_chunk_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags, char* buf, int buflen) {
+  return decode_name(decode_flat(B, H, Hkv, Nq, Ncap, D, flags, true), buf, buflen);
+}
+
+int lc_attn_chunk_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* block_table, const int* kv_len, int B, int H,
+                            int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  return decode_run(decode_paged(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, 2, true), Q, Kpool, Vpool, O, kv_len, block_table, nullptr,
+                    nullptr, workspace, workspace_bytes, stream);
+}
+
+size_t lc_attn_chunk_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D) {
+  return decode_bytes(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, 2, true));
+}
+
+int lc_attn_chunk_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
+  return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 2, true), buf, buflen);
+}
+
+int lc_attn_chunk_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* block_table, const int* kv_len,
+                            const float* k_scale, const float* v_scale, int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages,
+                            int D, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_paged(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, 1, true), Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale,
+                    v_scale, workspace, workspace_bytes, stream);
+}
+
+size_t lc_attn_chunk_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D) {
+  return decode_bytes(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, 0, 1, true));
+}
+
+int lc_attn_chunk_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
+  return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1, true), buf, buflen);
 }
 
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,

@@ -156,6 +156,7 @@ struct DecodeCall {
   bool paged;                            // false: a contiguous [B,Hkv,Ncap,D] cache; true: pools [num_pages,Hkv,page_size,D] + a block table
   int Ncap;                              // contiguous only
   int num_pages, page_size, max_pages;   // paged only (the query calls state num_pages = 1: it decides nothing)
+  bool chunk = false;                    // a chunk entry (lc_attn_chunk_*): R = (H / Hkv) x Nq is not bounded by 64
 };
 enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
 // ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
@@ -166,10 +167,14 @@ enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family read
 // smallest S that gives every CU a workgroup, with at least 4 tiles of Ncap per range, at most 64; the knob forces 1 .. 64 (ranges may then be
 // empty).  The cache kind decides the kernel and nothing else: RT, S and the workspace bytes of a paged call are those of the contiguous call of
 // Ncap = max_pages x page_size.
+// A chunk call (DecodeCall::chunk) may have R > 64: RB = ceil(R / 64) row blocks per (batch, K / V head).  RB = 1 is the plan of
+// the decode call, whichever entry stated it; RB > 1: RT = 4, attn_chunk_kernel<D> / attn_chunk_paged_kernel<D> / attn_chunk_paged_kv8_kernel<D>
+// on B x Hkv x RB x S workgroups, S by the same rule with B x Hkv x RB groups.
 struct DecodePlan {
   DecodeCall call;     // what was planned
   DecodeCache cache;
   int Ncap, RT, S;     // Ncap: the call's, or max_pages x page_size
+  int RB;              // row blocks of 64 query rows per (batch, K / V head); > 1: the chunk kernels
 };
 struct DecodePtrs {
   const half_t* Q;
@@ -184,7 +189,7 @@ struct DecodePtrs {
 // pointers (nullptr: a query call, which has none)
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p);
 int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p);   // checked arguments; nothing writes into a plan afterwards
-void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel)
+void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel); RB > 1: "attn_chunk_kernel<128> x8"
 // bytes of fp32 partials a plan with S > 1 needs: S x B H Nq rows x (D + 1) floats; 0 for S = 1
 inline size_t decode_workspace_bytes(const DecodePlan& p) {
   return p.S > 1 ? (size_t)p.S * ((size_t)p.call.B * p.call.H * p.call.Nq) * (size_t)(p.call.D + 1) * sizeof(float) : 0;
@@ -193,6 +198,9 @@ int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace
 // the S range workgroups of a plan of cache kind C: tu_attn_decode_impl.h, instantiated once per kind in the unit that compiles that kind's kernels
 template <DecodeCache C>
 int launch_attn_decode_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+// ... and of a plan with RB > 1: tu_attn_chunk.hip, the three kinds in one unit
+template <DecodeCache C>
+int launch_attn_chunk_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on

@@ -720,14 +720,15 @@ int plan_attn(const Knobs& k, const AttnCall& c, AttnPlan* p) {
 // fast as its longest range once every CU has a workgroup — the smallest S with B Hkv S >= CUs — and a range shorter than 4 tiles (one per wave) leaves
 // waves without work while the combine still reads S partials.
 int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
-  const int R = (c.H / c.Hkv) * c.Nq;
+  const long R = (long)(c.H / c.Hkv) * c.Nq;   // (> 64: a chunk call)
   p->call = c;
   p->cache = !c.paged ? DecodeCache::FLAT : c.kv_bytes == 1 ? DecodeCache::PAGED_KV8 : DecodeCache::PAGED;
   p->Ncap = c.paged ? c.max_pages * c.page_size : c.Ncap;
   p->RT = R <= 16 ? 1 : R <= 32 ? 2 : 4;
+  p->RB = (int)((R + 63) / 64);   // row blocks: each is a workgroup per KV range, and counts as a group of the rule
   p->S = k.attn_decode_split;
   if (p->S > 0) return LC_OK;
-  const long groups = (long)c.B * c.Hkv, tiles = ((long)p->Ncap + 63) / 64;
+  const long groups = (long)c.B * c.Hkv * p->RB, tiles = ((long)p->Ncap + 63) / 64;
   long S = (rule_cus(k) + groups - 1) / groups;
   S = std::min(S, tiles / 4);
   p->S = (int)std::max(1L, std::min(S, 64L));
@@ -745,10 +746,12 @@ int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
     ncap = (long)c.max_pages * c.page_size;
     if (ncap > 0x7fffffffL) return LC_ERR_SHAPE;
   } else if (ncap <= 0) return LC_ERR_SHAPE;
-  if ((long)(c.H / c.Hkv) * c.Nq > 64) return LC_ERR_SHAPE;   // R = G x Nq query rows per K / V head: four row tiles of 16 (no chunked prefill against a cache)
+  // R = G x Nq query rows per K / V head: four row tiles of 16 — a chunk entry has ceil(R / 64) row blocks of them instead
+  const long R = (long)(c.H / c.Hkv) * c.Nq;
+  if (!c.chunk && R > 64) return LC_ERR_SHAPE;
   // one head's Ncap rows (an upper bound of one page run) stay below 2 GiB: the kernel's 32-bit offsets (attn_span_fits at kv_bytes an element)
   if ((size_t)ncap * (size_t)c.D * (size_t)c.kv_bytes >= 0x80000000ull) return LC_ERR_SHAPE;
-  if ((size_t)c.B * c.Hkv * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x Hkv x S workgroups, S <= 64
+  if ((size_t)c.B * c.Hkv * (size_t)((R + 63) / 64) * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x Hkv x RB x S workgroups, S <= 64
   if (a && (!aligned16(a->Q) || !aligned16(a->K) || !aligned16(a->V) || !aligned16(a->O))) return LC_ERR_SHAPE;
   if (c.D != 64 && c.D != 128) return LC_ERR_HEADDIM;
   return plan_attn_decode(read_knobs(), c, p);
@@ -756,6 +759,12 @@ int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   static const char* const kKernels[] = {"attn_decode_kernel", "attn_decode_paged_kernel", "attn_decode_paged_kv8_kernel"};   // by DecodeCache
   const char* kern = kKernels[(int)p.cache];
+  if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
+    static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
+    if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", kChunk[(int)p.cache], p.call.D, p.S);
+    else snprintf(buf, buflen, "%s<%d>", kChunk[(int)p.cache], p.call.D);
+    return;
+  }
   if (p.S > 1) snprintf(buf, buflen, "%s<%d,%d> x%d", kern, p.call.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)
   else snprintf(buf, buflen, "%s<%d,%d>", kern, p.call.D, p.RT);
 }

@@ -53,6 +53,8 @@ OWNED_AGPRS = [
     (re.compile(r"hgemm_w4b_kernel|hgemm_w4x_kernel|hgemm_w4y_kernel|gemm_fp8_w4_kernel|gemm_fp8_w4k_kernel"), [(0, 255)]),
     # the decode kernels are plain HIP (builtins only): they own no AGPR, but are listed so that R2 (no scratch) covers them
     (re.compile(r"attn_decode_kernel|attn_decode_combine_kernel|attn_decode_paged_kernel|attn_decode_paged_kv8_kernel"), []),
+    # ... and the chunked-prefill kernels (attn_chunk.hip: the decode body on row blocks)
+    (re.compile(r"attn_chunk_kernel|attn_chunk_paged_kernel|attn_chunk_paged_kv8_kernel"), []),
     # ... and so are the append-to-cache kernels (kv_append_paged.hip)
     (re.compile(r"kv_append_paged_kernel|kv_append_paged_kv8_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),

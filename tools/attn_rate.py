@@ -17,6 +17,8 @@ usage: attn_rate.py [--seconds S] [--rounds R] spec...
           lc_attn_decode_paged_f16 and a block table (combinable with q, len, dsplit, causal; N % P == 0)
           kv8 (with page): that pool quantised to e4m3 with one scale per K / V head (amax / 448), through lc_attn_decode_paged_kv8; its
           K / V GB/s count one byte per element
+          q = Nq with (H / K) x Nq > 64 rows per K / V head: the CHUNK calls (lc_attn_chunk_f16 / _paged_f16 / _paged_kv8) — same options; their sdpa
+          arm takes causal too, as a boolean bottom-right mask built once outside the timing
           append (with page): instead of the decode call, the APPEND of the q = Nq newest tokens of every sequence (positions L - Nq .. L - 1)
           to that pool through lc_kv_append_paged_f16 (kv8: lc_kv_append_paged_kv8); append:torch: the same job in torch ops — an index_put_
           of the rows into the pool viewed as rows (indices computed outside the timing), preceded for kv8 by
@@ -150,6 +152,7 @@ def run_decode(spec, shape, opts):
     split = opt_int(opts, "dsplit", 0)
     page = opt_int(opts, "page", 0)
     kv8 = "kv8" in opts
+    chunk = (H // kvh) * nq > 64
     if kv8 and not page:
         raise SystemExit(f"{spec}: kv8 needs page=P")
     if page:
@@ -179,23 +182,28 @@ def run_decode(spec, shape, opts):
     capi.tune("attn_decode_split", split)
     try:
         if "sdpa" in opts:
-            if causal:
+            if causal and not chunk:
                 raise SystemExit(f"{spec}: the sdpa arm of a decode spec is non-causal")
             ks, vs = k[:, :, :L], v[:, :, :L]
+            mask = None                                 # a chunk spec: query i sees keys j <= L - Nq + i (torch's is_causal is top-left aligned)
+            if causal:
+                mask = torch.arange(L, device="cuda").view(1, L) <= (L - nq + torch.arange(nq, device="cuda")).view(nq, 1)
             try:
-                torch.nn.functional.scaled_dot_product_attention(q, ks, vs, enable_gqa=True)
-                name = "torch sdpa enable_gqa"
-                step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ks, vs, enable_gqa=True)  # noqa: E731
+                torch.nn.functional.scaled_dot_product_attention(q, ks, vs, attn_mask=mask, enable_gqa=True)
+                name = "torch sdpa enable_gqa" + (" + mask" if causal else "")
+                step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ks, vs, attn_mask=mask, enable_gqa=True)  # noqa: E731
             except TypeError:
                 ke, ve = ks.repeat_interleave(H // kvh, dim=1), vs.repeat_interleave(H // kvh, dim=1)
-                name = "torch sdpa (K / V expanded)"
-                step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ke, ve)  # noqa: E731
+                name = "torch sdpa (K / V expanded)" + (" + mask" if causal else "")
+                step = lambda: torch.nn.functional.scaled_dot_product_attention(q, ke, ve, attn_mask=mask)  # noqa: E731
         else:                                           # the cache kind of the spec -> (name function, its shape arguments, step)
             paged = (B, H, kvh, nq, page, N // max(page, 1), D)
+            fam = "attn_chunk" if chunk else "attn_decode"      # more than 64 query rows per K / V head: the chunk entries
+            call = lambda suffix: getattr(capi, fam + suffix)  # noqa: E731
             name_of, shape_args, step = {
-                "kv8": (capi.attn_decode_paged_kv8_kernel_name, paged, lambda: capi.attn_decode_paged_kv8(q, k_pool, v_pool, o, table, lens, k_scale, v_scale, causal=causal)),
-                "paged": (capi.attn_decode_paged_kernel_name, paged, lambda: capi.attn_decode_paged(q, k_pool, v_pool, o, table, lens, causal=causal)),
-                "flat": (capi.attn_decode_kernel_name, (B, H, kvh, nq, N, D), lambda: capi.attn_decode(q, k, v, o, lens, causal=causal)),
+                "kv8": (call("_paged_kv8_kernel_name"), paged, lambda: call("_paged_kv8")(q, k_pool, v_pool, o, table, lens, k_scale, v_scale, causal=causal)),
+                "paged": (call("_paged_kernel_name"), paged, lambda: call("_paged")(q, k_pool, v_pool, o, table, lens, causal=causal)),
+                "flat": (call("_kernel_name"), (B, H, kvh, nq, N, D), lambda: call("")(q, k, v, o, lens, causal=causal)),
             }["kv8" if kv8 else "paged" if page else "flat"]
             name = name_of(*shape_args, causal=causal)
         ms = timed(step)
