@@ -442,8 +442,8 @@ int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page
  * LC_ERR_HEADDIM.  Nq is NOT bounded by the decode kernels' 64 rows: a prefill writes whole prompts.  No workspace.
  * Kernels: kv_append_paged_kernel<D>, kv_append_paged_kv8_kernel<D>.  The name calls never launch, take no num_pages (it decides nothing) and
  * return the status the run call gives that shape; a NULL buffer or buflen < 8: LC_ERR_ARG.
- * Not here: per-token or per-page scales, pools laid out [P,page_size,Hkv,D], a [B,Nq,Hkv,D] source, rotary embedding, an append to a
- * contiguous cache, ragged Nq per sequence other than by left padding. */
+ * Not here: per-token or per-page scales, pools laid out [P,page_size,Hkv,D], an append to a contiguous cache, ragged Nq per sequence other
+ * than by left padding.  (A token-major [B,Nq,Hkv,D] source and rotary embedding: lc_rope_append_paged_* below.) */
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
                            const int* block_table, const int* kv_len,
                            int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
@@ -456,6 +456,53 @@ int lc_kv_append_paged_kernel_name(int B, int Hkv, int Nq, int page_size, int ma
                                    int flags, char* buf, int buflen);
 int lc_kv_append_paged_kv8_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D,
                                        int flags, char* buf, int buflen);
+
+/* EXTENSION: rotary embedding (RoPE) fused with the append (rope_append_paged.hip): the link between the QKV projection
+ * GEMM and lc_kv_append_paged_* / the attention calls.  ONE launch rotates Q and K by position, writes Q in the layout lc_attn_decode_* /
+ * lc_attn_chunk_* read, and writes the rotated (fp8: quantised) K and the unrotated V into the pools — through the same block_table / kv_len
+ * pair, so prefill -> append -> decode is a sequence of this library's calls only, capturable as one graph.
+ * Positions are the append call's: L = kv_len[b] clamped to [0, max_pages x page_size] is the length AFTER the append, token i has position
+ * p = L - Nq + i.  K and V of token i land where lc_kv_append_paged_* puts them (p < 0: no pool write; a page id outside [0, num_pages) drops the
+ * token's K and V rows).  V is not rotated: the V pool is byte for byte what lc_kv_append_paged_f16 / _kv8 writes.
+ * cos_sin: DEVICE float[max_pos, rot_dim]; row t holds cos(theta_{t,j}), j = 0 .. rot_dim/2 - 1, then sin(theta_{t,j}) for the same j (vLLM's
+ * cos_sin_cache layout, in fp32).  The caller owns the angles (base, scaling, NTK, YaRN): the kernel does no trigonometry.  The row read for
+ * position p is min(p, max_pos - 1): clamped in the kernel, nothing is read outside the table.
+ * Rotation of a row x (a Q row of any of the H heads, a K row of any of the Hkv heads) at position p: pair j is elements (j, j + rot_dim/2)
+ * (default: NeoX / Llama "rotate half") or (2j, 2j + 1) (LC_ROPE_INTERLEAVED: GPT-J); x1' = x1 c - x2 s, x2' = x2 c + x1 s.  Inputs go from fp16
+ * to fp32, all arithmetic is fp32, ONE rounding to fp16 (nearest even) at the end; fp16 denormals are kept on input and output.  Elements
+ * rot_dim .. D - 1 (partial rotary) are copied bit for bit.  A pair with a non-finite input has unspecified outputs; nothing outside it is
+ * affected.
+ * Qout: [B,H,Nq,D] fp16 dense, row (b, h, i) rotated at position p; rows with p < 0 are ZEROS; a dropped page id does not affect Qout.
+ * fp16 pools get the rotated fp16 K row; fp8 pools get lc_kv_append_paged_kv8's code of the rotated row ROUNDED TO fp16 FIRST, so the fp8 entry
+ * equals, byte for byte, lc_kv_append_paged_kv8 fed with what the fp16 entry wrote.
+ * Sources.  Default: Q [B,H,Nq,D], Knew and Vnew [B,Hkv,Nq,D], dense, src_row_stride = 0; Qout == Q (the same pointer) rotates in place.
+ * LC_ROPE_PACKED_SRC: Q, Knew and Vnew point into ONE token-major projection output: element (b, i, h, d) of a source is at
+ * ptr[(b Nq + i) src_row_stride + h D + d]; src_row_stride is in elements, a multiple of 8 and >= (H + 2 Hkv) D; a caller passes qkv,
+ * qkv + H D and qkv + (H + Hkv) D.  Qout is still dense [B,H,Nq,D] (the call transposes too) and must not overlap the sources.
+ * Checks, all before any device work: a flag bit other than the two defined, then a NULL Q / Knew / Vnew / Qout / pool / cos_sin / block_table /
+ * kv_len: LC_ERR_ARG; then LC_ERR_SHAPE for non-positive B / H / Hkv / Nq / num_pages / max_pages / D / max_pos, H % Hkv != 0, the append call's
+ * page and span bounds, rot_dim not a multiple of 16 in [16, D], src_row_stride != 0 without LC_ROPE_PACKED_SRC or (with it) not a multiple of 8
+ * or < (H + 2 Hkv) D, a grid of (B Hkv + B H) x ceil(Nq D / 2048) workgroups that does not fit an int, Q / Knew / Vnew / Qout / pools not
+ * 16-byte aligned; then D not in {64, 128}: LC_ERR_HEADDIM.  Nq is unbounded, there is no workspace.
+ * Kernels: rope_append_paged_kernel<D,INTERLEAVED>, rope_append_paged_kv8_kernel<D,INTERLEAVED>.  The name calls never launch, take no
+ * num_pages and return the status the run call gives that shape; a NULL buffer or buflen < 8: LC_ERR_ARG.
+ * Not here: explicit per-token position ids (tree speculation, M-RoPE), an fp16 / bf16 table or angles computed in the kernel, bf16 sources,
+ * RoPE for the contiguous cache, D outside {64, 128}. */
+#define LC_ROPE_INTERLEAVED 1
+#define LC_ROPE_PACKED_SRC 2
+int lc_rope_append_paged_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                             const float* cos_sin, const int* block_table, const int* kv_len,
+                             int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
+                             int rot_dim, int max_pos, long long src_row_stride, int flags, void* stream);
+int lc_rope_append_paged_kv8(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8,
+                             const float* cos_sin, const int* block_table, const int* kv_len,
+                             const float* k_scale, const float* v_scale,
+                             int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
+                             int rot_dim, int max_pos, long long src_row_stride, int flags, void* stream);
+int lc_rope_append_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                     int rot_dim, int max_pos, long long src_row_stride, int flags, char* buf, int buflen);
+int lc_rope_append_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
+                                         int rot_dim, int max_pos, long long src_row_stride, int flags, char* buf, int buflen);
 
 /* EXTENSION: chunked-prefill attention over the three KV caches (attn_chunk.hip): lc_attn_decode_f16,
  * lc_attn_decode_paged_f16 and lc_attn_decode_paged_kv8 with the bound R = (H / Hkv) x Nq <= 64 REMOVED — what attends over a chunk of a prompt

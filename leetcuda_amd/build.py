@@ -30,7 +30,8 @@ ORACLE_NAME = "liblc_oracle.so"
 # isa_audit.json is read by name patterns and entry counts: "attn_decode" is counted as the eight kernels of tu_attn_decode.hip, and the
 # paged kernels' names (attn_decode_paged_kernel<D, RT>) contain that string.
 AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_attn_decode_paged_kv8": "isa_audit_decode_paged_kv8.json",
-                    "tu_kv_append": "isa_audit_kv_append.json", "tu_attn_chunk": "isa_audit_chunk.json"}
+                    "tu_kv_append": "isa_audit_kv_append.json", "tu_attn_chunk": "isa_audit_chunk.json",
+                    "tu_rope_append": "isa_audit_rope_append.json"}
 
 
 def _newer(target: Path, sources) -> bool:

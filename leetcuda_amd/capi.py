@@ -22,6 +22,7 @@ HGEMM_RAGGED = 16  # ragged M / N, K % 32 == 0, N % 8 == 0: the tiled kernels, c
 HGEMM_KPAD = 17    # K % 32 != 0 on a large problem: zero-padded operand copies in the workspace + the tuned kernels
 ATTN_SPLIT_Q, ATTN_SHARED_QKV, ATTN_SHARED_KV, ATTN_TILING_QK, ATTN_TILING_QKV, ATTN_SPLIT_KV = range(6)
 ATTN_CAUSAL, ATTN_V_TRANSPOSED = 1, 2   # lc_attn_fwd_f16_ex / lc_attn_kernel_name_ex flags
+ROPE_INTERLEAVED, ROPE_PACKED_SRC = 1, 2   # lc_rope_append_paged_* flags
 
 # every symbol include/lc_abi.h declares: name -> (restype, argtypes)
 _vp, _i, _cp, _fp, _ip = C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_int)
@@ -74,6 +75,10 @@ SYMBOLS = {
     "lc_kv_append_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
     "lc_kv_append_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_rope_append_paged_f16": (_i, [_vp] * 9 + [_i] * 10 + [C.c_longlong, _i, _vp]),
+    "lc_rope_append_paged_kv8": (_i, [_vp] * 11 + [_i] * 10 + [C.c_longlong, _i, _vp]),
+    "lc_rope_append_paged_kernel_name": (_i, [_i] * 9 + [C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_paged_kv8_kernel_name": (_i, [_i] * 9 + [C.c_longlong, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -611,16 +616,22 @@ def _kv_append_args(k_new, v_new, k_pool, v_pool, block_table, kv_len, k_scale=N
     [num_pages,Hkv,page_size,D] of fp16 (kv8: float8_e4m3fn or uint8); int32 block_table [B,max_pages] and kv_len [B]; kv8: float32 [Hkv] scales
     or None.  Returns B, Hkv, Nq, num_pages, page_size, max_pages, D."""
     import torch
-    pool_types = (torch.float8_e4m3fn, torch.uint8) if kv8 else (torch.half,)
     if k_new.dtype != torch.half or v_new.dtype != torch.half:
         raise TypeError(f"k_new / v_new must be float16, got {k_new.dtype} / {v_new.dtype}")
+    return _kv_append_shapes(tuple(k_new.shape), tuple(v_new.shape), k_pool, v_pool, block_table, kv_len, k_scale, v_scale, kv8)
+
+
+def _kv_append_shapes(k_shape, v_shape, k_pool, v_pool, block_table, kv_len, k_scale=None, v_scale=None, kv8=False):
+    """_kv_append_args behind the dtype of k_new / v_new, on their SHAPES: a packed qkv (rope_append_paged_qkv) has the rows but no tensors of them"""
+    import torch
+    pool_types = (torch.float8_e4m3fn, torch.uint8) if kv8 else (torch.half,)
     if k_pool.dtype not in pool_types or v_pool.dtype not in pool_types:
         raise TypeError(f"k_pool / v_pool must be {' or '.join(str(t) for t in pool_types)}, got {k_pool.dtype} / {v_pool.dtype}")
-    if k_new.dim() != 4 or k_pool.dim() != 4:
+    if len(k_shape) != 4 or k_pool.dim() != 4:
         _shape_err("4-D [B,Hkv,Nq,D] / [num_pages,Hkv,page_size,D] tensors expected")
-    B, Hkv, Nq, D = k_new.shape
-    if tuple(v_new.shape) != (B, Hkv, Nq, D) or k_pool.shape[1] != Hkv or k_pool.shape[3] != D or tuple(v_pool.shape) != tuple(k_pool.shape):
-        _shape_err(f"k_new {tuple(k_new.shape)} v_new {tuple(v_new.shape)} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)}")
+    B, Hkv, Nq, D = k_shape
+    if v_shape != (B, Hkv, Nq, D) or k_pool.shape[1] != Hkv or k_pool.shape[3] != D or tuple(v_pool.shape) != tuple(k_pool.shape):
+        _shape_err(f"k_new {k_shape} v_new {v_shape} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)}")
     if block_table is None or block_table.dim() != 2 or block_table.shape[0] != B:
         _shape_err(f"block_table {None if block_table is None else tuple(block_table.shape)} for batch {B}")
     if kv_len is None or tuple(kv_len.shape) != (B,):
@@ -666,6 +677,131 @@ def kv_append_paged_kernel_name(B, Hkv, Nq, page_size, max_pages, D, kv8=False) 
     symbol = "lc_kv_append_paged_kv8_kernel_name" if kv8 else "lc_kv_append_paged_kernel_name"
     buf = C.create_string_buffer(128)
     check(getattr(load(), symbol)(B, Hkv, Nq, page_size, max_pages, D, 0, buf, 128), symbol)
+    return buf.value.decode()
+
+
+def rope_table(max_pos, rot_dim, base=10000.0):
+    """The cos_sin table of plain RoPE for rope_append_paged*: float32 [max_pos, rot_dim] on the CPU, row t = cos(t w_j), j = 0 .. rot_dim/2 - 1,
+    then sin(t w_j), with w_j = base^(-2j / rot_dim); the angles are computed in float64.  Scaled variants (NTK, YaRN, ...) are the caller's: any
+    table of this layout is accepted."""
+    import torch
+    if max_pos <= 0 or rot_dim < 2 or rot_dim % 2:
+        _shape_err(f"rope_table({max_pos}, {rot_dim})")
+    j = torch.arange(rot_dim // 2, dtype=torch.float64)
+    ang = torch.arange(max_pos, dtype=torch.float64)[:, None] * torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * j / rot_dim)[None, :]
+    return torch.cat([ang.cos(), ang.sin()], dim=1).to(torch.float32).contiguous()
+
+
+def _rope_append_args(q, k_new, v_new, k_pool, v_pool, cos_sin, block_table, kv_len, q_out, k_scale=None, v_scale=None, kv8=False):
+    """The dtype and shape checks of rope_append_paged / rope_append_paged_kv8 (no GPU needed): _kv_append_args' on what the append call shares,
+    then fp16 q [B,H,Nq,D] with H a multiple of Hkv, float32 cos_sin [max_pos, rot_dim], q_out (if given) fp16 of q's shape.  Returns B, H, Hkv,
+    Nq, num_pages, page_size, max_pages, D, rot_dim, max_pos."""
+    import torch
+    if k_new.dtype != torch.half or v_new.dtype != torch.half:
+        raise TypeError(f"k_new / v_new must be float16, got {k_new.dtype} / {v_new.dtype}")
+    if q.dtype != torch.half:
+        raise TypeError(f"q must be float16, got {q.dtype}")
+    return _rope_shapes(tuple(q.shape), tuple(k_new.shape), tuple(v_new.shape), k_pool, v_pool, cos_sin, block_table, kv_len, q_out, k_scale, v_scale, kv8)
+
+
+def _rope_shapes(q_shape, k_shape, v_shape, k_pool, v_pool, cos_sin, block_table, kv_len, q_out, k_scale, v_scale, kv8):
+    """_rope_append_args behind the dtypes of q, k_new and v_new, on their shapes (the dense and the packed call share it)"""
+    import torch
+    B, Hkv, Nq, P, ps, mp, D = _kv_append_shapes(k_shape, v_shape, k_pool, v_pool, block_table, kv_len, k_scale, v_scale, kv8)
+    if q_out is not None and q_out.dtype != torch.half:
+        raise TypeError(f"q_out must be float16, got {q_out.dtype}")
+    if cos_sin.dtype != torch.float32:
+        raise TypeError(f"cos_sin must be float32, got {cos_sin.dtype}")
+    if len(q_shape) != 4 or q_shape[0] != B or q_shape[2] != Nq or q_shape[3] != D or q_shape[1] % Hkv != 0:
+        _shape_err(f"q {q_shape} for k_new {k_shape}")
+    if q_out is not None and tuple(q_out.shape) != q_shape:
+        _shape_err(f"q_out {tuple(q_out.shape)} vs q {q_shape}")
+    if cos_sin.dim() != 2 or cos_sin.shape[0] < 1 or cos_sin.shape[1] % 16 != 0 or not 16 <= cos_sin.shape[1] <= D:
+        _shape_err(f"cos_sin {tuple(cos_sin.shape)}: [max_pos, rot_dim], rot_dim a multiple of 16 in [16, {D}]")
+    return B, q_shape[1], Hkv, Nq, P, ps, mp, D, cos_sin.shape[1], cos_sin.shape[0]
+
+
+def _rope_launch(src_ptrs, q_out, k_pool, v_pool, cos_sin, block_table, kv_len, k_scale, v_scale, dims, stride, flags, kv8):
+    """src_ptrs: the addresses of Q, Knew and Vnew (three tensors, or three places in one packed qkv)"""
+    _need_gpu(q_out, k_pool, v_pool, cos_sin, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    scale_ptrs = [_ptr(s) if s is not None else None for s in (k_scale, v_scale)] if kv8 else []
+    symbol = "lc_rope_append_paged_kv8" if kv8 else "lc_rope_append_paged_f16"
+    check(getattr(load(), symbol)(*src_ptrs, _ptr(q_out), _ptr(k_pool), _ptr(v_pool), _ptr(cos_sin), _ptr(block_table), _ptr(kv_len), *scale_ptrs,
+                                  *dims, stride, flags, _stream()), symbol)
+    return q_out
+
+
+def rope_append_paged(q, k_new, v_new, k_pool, v_pool, cos_sin, block_table, kv_len, q_out=None, interleaved=False):
+    """Rotary embedding fused with kv_append_paged (lc_rope_append_paged_f16), ONE launch: q [B,H,Nq,D] and k_new [B,Hkv,Nq,D] are rotated at
+    position kv_len[b] - Nq + i with row min(position, max_pos - 1) of cos_sin (DEVICE float32 [max_pos, rot_dim], rope_table's layout; pairs
+    (j, j + rot_dim/2), or (2j, 2j + 1) with interleaved=True; elements behind rot_dim are copied); the rotated K and the unrotated v_new go into
+    the pools exactly where kv_append_paged puts them.  Returns q_out [B,H,Nq,D] (None: allocated; `q_out is q`: in place), rows of negative
+    position zeroed."""
+    import torch
+    dims = _rope_append_args(q, k_new, v_new, k_pool, v_pool, cos_sin, block_table, kv_len, q_out)
+    _need_gpu(q, k_new, v_new)
+    return _rope_launch((_ptr(q), _ptr(k_new), _ptr(v_new)), torch.empty_like(q) if q_out is None else q_out, k_pool, v_pool, cos_sin, block_table, kv_len,
+                        None, None, dims, 0, ROPE_INTERLEAVED if interleaved else 0, False)
+
+
+def rope_append_paged_kv8(q, k_new, v_new, k_pool8, v_pool8, cos_sin, block_table, kv_len, q_out=None, interleaved=False, k_scale=None, v_scale=None):
+    """rope_append_paged into fp8 pools (lc_rope_append_paged_kv8): the K code is kv_append_paged_kv8's code of the rotated row rounded to fp16,
+    so the pools equal kv_append_paged_kv8 fed with what rope_append_paged wrote.  k_scale, v_scale: DEVICE float32 [Hkv] or None = 1.0."""
+    import torch
+    dims = _rope_append_args(q, k_new, v_new, k_pool8, v_pool8, cos_sin, block_table, kv_len, q_out, k_scale, v_scale, kv8=True)
+    _need_gpu(q, k_new, v_new)
+    return _rope_launch((_ptr(q), _ptr(k_new), _ptr(v_new)), torch.empty_like(q) if q_out is None else q_out, k_pool8, v_pool8, cos_sin, block_table,
+                        kv_len, k_scale, v_scale, dims, 0, ROPE_INTERLEAVED if interleaved else 0, True)
+
+
+def _rope_qkv_args(qkv, H, Hkv, k_pool, v_pool, cos_sin, block_table, kv_len, q_out, k_scale, v_scale):
+    """The checks of rope_append_paged_qkv (no GPU needed): fp16 qkv [B,Nq,(H + 2 Hkv) D] whose last dim is dense and whose two outer strides
+    describe ONE row stride (a row-strided view of a wider projection output is accepted); the pool dtype picks the entry.  Returns
+    (dims as _rope_append_args, row stride in elements, kv8)."""
+    import torch
+    if qkv.dtype != torch.half:
+        raise TypeError(f"qkv must be float16, got {qkv.dtype}")
+    if k_pool.dtype not in (torch.half, torch.float8_e4m3fn, torch.uint8):
+        raise TypeError(f"k_pool / v_pool must be float16, float8_e4m3fn or uint8, got {k_pool.dtype} / {v_pool.dtype}")
+    kv8 = k_pool.dtype != torch.half
+    if not kv8 and (k_scale is not None or v_scale is not None):
+        raise TypeError("k_scale / v_scale belong to fp8 pools")
+    if qkv.dim() != 3 or k_pool.dim() != 4 or H <= 0 or Hkv <= 0 or H % Hkv != 0:
+        _shape_err(f"qkv {tuple(qkv.shape)} [B,Nq,(H + 2 Hkv) D] with H = {H}, Hkv = {Hkv}; k_pool {tuple(k_pool.shape)}")
+    B, Nq, W = qkv.shape
+    D = k_pool.shape[3]
+    if W != (H + 2 * Hkv) * D:
+        _shape_err(f"qkv {tuple(qkv.shape)}: last dim is not (H + 2 Hkv) D = {(H + 2 * Hkv) * D}")
+    stride = qkv.stride(1) if Nq > 1 else (qkv.stride(0) if B > 1 else W)
+    if qkv.stride(2) != 1 or stride < W or stride % 8 != 0 or (B > 1 and qkv.stride(0) != Nq * stride):
+        _shape_err(f"qkv strides {tuple(qkv.stride())}: one row stride >= {W}, a multiple of 8, is expected")
+    dims = _rope_shapes((B, H, Nq, D), (B, Hkv, Nq, D), (B, Hkv, Nq, D), k_pool, v_pool, cos_sin, block_table, kv_len, q_out, k_scale, v_scale, kv8)
+    return dims, stride, kv8
+
+
+def rope_append_paged_qkv(qkv, H, Hkv, k_pool, v_pool, cos_sin, block_table, kv_len, q_out=None, interleaved=False, k_scale=None, v_scale=None):
+    """rope_append_paged / rope_append_paged_kv8 (the pool dtype picks the entry) straight from the QKV projection's token-major output
+    (LC_ROPE_PACKED_SRC): qkv [B,Nq,(H + 2 Hkv) D] fp16 — or a row-strided view of it — holds each token's H query heads, then its Hkv key
+    heads, then its Hkv value heads.  Returns q_out [B,H,Nq,D] dense (the call transposes too); q_out must not overlap qkv."""
+    import torch
+    dims, stride, kv8 = _rope_qkv_args(qkv, H, Hkv, k_pool, v_pool, cos_sin, block_table, kv_len, q_out, k_scale, v_scale)
+    B, _, _, Nq, _, _, _, D = dims[:8]
+    if not qkv.is_cuda:
+        raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    if q_out is None:
+        q_out = torch.empty((B, H, Nq, D), dtype=torch.half, device=qkv.device)
+    base, esz = _ptr(qkv), qkv.element_size()      # three places in one buffer: the kernel strides by `stride`, so qkv need not be contiguous
+    return _rope_launch((base, base + H * D * esz, base + (H + Hkv) * D * esz), q_out, k_pool, v_pool, cos_sin, block_table, kv_len, k_scale, v_scale,
+                        dims, stride, ROPE_PACKED_SRC | (ROPE_INTERLEAVED if interleaved else 0), kv8)
+
+
+def rope_append_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, rot_dim, max_pos, interleaved=False, kv8=False, src_row_stride=0) -> str:
+    """The kernel rope_append_paged (kv8: rope_append_paged_kv8; src_row_stride != 0: the packed layout of rope_append_paged_qkv) runs for this
+    shape: "rope_append_paged_kernel<D,INTERLEAVED>" / "rope_append_paged_kv8_kernel<D,INTERLEAVED>"."""
+    symbol = "lc_rope_append_paged_kv8_kernel_name" if kv8 else "lc_rope_append_paged_kernel_name"
+    flags = (ROPE_INTERLEAVED if interleaved else 0) | (ROPE_PACKED_SRC if src_row_stride else 0)
+    buf = C.create_string_buffer(128)
+    check(getattr(load(), symbol)(B, H, Hkv, Nq, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, buf, 128), symbol)
     return buf.value.decode()
 
 

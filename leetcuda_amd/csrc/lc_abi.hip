@@ -118,6 +118,28 @@ int append_name(const AppendCall& c, char* buf, int buflen) {
   return LC_OK;
 }
 
+// The two rotary-embedding + append entries each state a RopeAppendCall (an AppendCall with flags 0 + H, rot_dim, max_pos, src_row_stride, flags);
+// check_rope_append (tu_plan.hip) checks it; rope_run and rope_name run and name it.
+RopeAppendCall rope_call(int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                         long long src_row_stride, int flags, int kv_bytes) {
+  return RopeAppendCall{AppendCall{B, Hkv, Nq, D, 0, kv_bytes, num_pages, page_size, max_pages}, H, rot_dim, max_pos, src_row_stride, flags};
+}
+int rope_run(const RopeAppendCall& c, const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool, const float* cos_sin,
+             const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, void* stream) {
+  const RopeAppendPtrs p{AppendPtrs{static_cast<const half_t*>(Knew), static_cast<const half_t*>(Vnew), Kpool, Vpool, block_table, kv_len, k_scale, v_scale,
+                                    static_cast<hipStream_t>(stream)},
+                         static_cast<const half_t*>(Q), static_cast<half_t*>(Qout), cos_sin};
+  if (int rc = check_rope_append(c, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_rope_append(c, p);
+}
+int rope_name(const RopeAppendCall& c, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  if (int rc = check_rope_append(c, nullptr)) return rc;
+  format_rope_append(c, buf, buflen);
+  return LC_OK;
+}
+
 // The two fp8 GEMM entries each state a GemmFp8Call (M, N, K, swizzle_stride, mx); check_gemm_fp8 (tu_plan.hip) checks and plans it.  PA / PB: the block-scaled call
 int gemm_fp8_run(const GemmFp8Call& c, const void* A, const void* PA, const void* B, const void* PB, void* C, float alpha, void* stream) {
   const GemmFp8Ptrs a{static_cast<const uint8_t*>(A), static_cast<const uint8_t*>(B), static_cast<half_t*>(C), static_cast<const uint32_t*>(PA),
@@ -413,6 +435,32 @@ int lc_kv_append_paged_kernel_name(int B, int Hkv, int Nq, int page_size, int ma
 
 int lc_kv_append_paged_kv8_kernel_name(int B, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
   return append_name(AppendCall{B, Hkv, Nq, D, flags, 1, 1, page_size, max_pages}, buf, buflen);
+}
+
+int lc_rope_append_paged_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool, const float* cos_sin,
+                             const int* block_table, const int* kv_len, int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
+                             int rot_dim, int max_pos, long long src_row_stride, int flags, void* stream) {
+  return rope_run(rope_call(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, 2), Q, Knew, Vnew, Qout, Kpool,
+                  Vpool, cos_sin, block_table, kv_len, nullptr, nullptr, stream);
+}
+
+int lc_rope_append_paged_kv8(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8, const float* cos_sin,
+                             const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int Nq,
+                             int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos, long long src_row_stride, int flags,
+                             void* stream) {
+  return rope_run(rope_call(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, 1), Q, Knew, Vnew, Qout, Kpool8,
+                  Vpool8, cos_sin, block_table, kv_len, k_scale, v_scale, stream);
+}
+
+// (the name calls take no num_pages: it decides nothing)
+int lc_rope_append_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                     long long src_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_call(B, H, Hkv, Nq, 1, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, 2), buf, buflen);
+}
+
+int lc_rope_append_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                         long long src_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_call(B, H, Hkv, Nq, 1, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, 1), buf, buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -224,4 +224,25 @@ int check_kv_append(const AppendCall& c, const AppendPtrs* a);
 void format_kv_append(const AppendCall& c, char* buf, int buflen);   // "kv_append_paged_kernel<128>" / "kv_append_paged_kv8_kernel<128>"
 int launch_kv_append(const AppendCall& c, const AppendPtrs& a);      // tu_kv_append.hip; checked arguments
 
+// What a caller of a rotary-embedding + append entry states (lc_rope_append_paged_f16 / _kv8 and their name calls): the append
+// call (its flags are 0) plus what the rotation and the Q side need.  Nothing to plan either: one kernel, rope_append_paged_kernel<D, INTERLEAVED>
+// or rope_append_paged_kv8_kernel<D, INTERLEAVED>, on (B x Hkv + B x H) x ceil(Nq / (2048 / D)) workgroups, no workspace.
+struct RopeAppendCall {
+  AppendCall a;
+  int H, rot_dim, max_pos;
+  long long src_row_stride;              // elements; 0 unless LC_ROPE_PACKED_SRC
+  int flags;                             // LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC
+};
+struct RopeAppendPtrs {
+  AppendPtrs a;
+  const half_t* Q;                       // dense [B,H,Nq,D], or (packed) a token-major projection output, as a.Knew and a.Vnew
+  half_t* Qout;                          // dense [B,H,Nq,D]; may be Q itself for a dense source
+  const float* cos_sin;                  // device float[max_pos, rot_dim]
+};
+// The checks of the two entry points in the order that decides the status of a doubly-bad call; everything the append call shares is
+// check_kv_append's, so a pool geometry that append accepts is accepted here.  p: the run call's pointers (nullptr: a name call)
+int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p);
+void format_rope_append(const RopeAppendCall& c, char* buf, int buflen);   // "rope_append_paged_kernel<128,false>" / "rope_append_paged_kv8_kernel<64,true>"
+int launch_rope_append(const RopeAppendCall& c, const RopeAppendPtrs& p);  // tu_rope_append.hip; checked arguments
+
 }  // namespace lc

@@ -791,6 +791,30 @@ void format_kv_append(const AppendCall& c, char* buf, int buflen) {
   snprintf(buf, buflen, c.kv_bytes == 1 ? "kv_append_paged_kv8_kernel<%d>" : "kv_append_paged_kernel<%d>", c.D);
 }
 
+// Rotary embedding + append (lc_plan.h RopeAppendCall).  Its own ARG checks first, then check_kv_append for everything the two calls share; a
+// head dim append refuses is reported only after every SHAPE check of this call has passed (ARG, SHAPE, HEADDIM: the order of every entry).
+int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p) {
+  if (c.flags & ~(LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC)) return LC_ERR_ARG;
+  if (p && (!p->Q || !p->Qout || !p->cos_sin)) return LC_ERR_ARG;
+  const int rc = check_kv_append(c.a, p ? &p->a : nullptr);
+  if (rc != LC_OK && rc != LC_ERR_HEADDIM) return rc;
+  const int D = c.a.D;
+  if (c.H <= 0 || c.max_pos <= 0 || c.H % c.a.Hkv != 0) return LC_ERR_SHAPE;
+  if (c.rot_dim < 16 || c.rot_dim > D || c.rot_dim % 16 != 0) return LC_ERR_SHAPE;   // a NeoX partner is a whole 16-byte chunk away
+  if (c.flags & LC_ROPE_PACKED_SRC) {
+    if (c.src_row_stride % 8 != 0 || c.src_row_stride < ((long long)c.H + 2LL * c.a.Hkv) * D) return LC_ERR_SHAPE;
+  } else if (c.src_row_stride != 0) return LC_ERR_SHAPE;
+  // 1-D grid of (B x Hkv + B x H) x ceil(Nq / tokens per workgroup) workgroups
+  const size_t bh = (size_t)c.a.B * ((size_t)c.a.Hkv + (size_t)c.H);
+  if (bh > 0x7fffffffull || bh * (((size_t)c.a.Nq - 1) / kv_append_tokens_per_block(D) + 1) > 0x7fffffffull) return LC_ERR_SHAPE;
+  if (p && (!aligned16(p->Q) || !aligned16(p->Qout))) return LC_ERR_SHAPE;
+  return rc;
+}
+void format_rope_append(const RopeAppendCall& c, char* buf, int buflen) {
+  snprintf(buf, buflen, c.a.kv_bytes == 1 ? "rope_append_paged_kv8_kernel<%d,%s>" : "rope_append_paged_kernel<%d,%s>", c.a.D,
+           c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
+}
+
 // The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).
 void format_attn(const AttnPlan& p, char* buf, int buflen) {
   const int D = p.call.D;

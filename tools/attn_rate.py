@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sustained rate of the attention forward at arbitrary shapes, interleaved A/B over tuning knobs.
 usage: attn_rate.py [--seconds S] [--rounds R] spec...
-   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P[:kv8][:append[:torch]]] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
+   spec = B,H,N,D[:q=Nq][:len=L][:dsplit=S][:page=P[:kv8][:append[:torch] | :rope[:torch]]] | B,H,N,D[:bf16][:zero][:vt][:causal][:sdpa][:kvh=K][:expand][:expanded][:nw=K][:walk=K][:split=K][:d512=K][:sched=K][:order=K]   (vt = V handed over as [B,H,D,N];
           causal = the causal mask (lc_attn_fwd_f16_ex); sdpa = torch.nn.functional.scaled_dot_product_attention on the same inputs
           instead of this library (context only); kvh = K: grouped-query attention, K / V tensors with K heads through lc_attn_fwd_f16_gqa
           (FLOPs counted as for the H query heads); kvh = K with expand: what a caller without that entry does — repeat_interleave K and V
@@ -23,6 +23,11 @@ usage: attn_rate.py [--seconds S] [--rounds R] spec...
           to that pool through lc_kv_append_paged_f16 (kv8: lc_kv_append_paged_kv8); append:torch: the same job in torch ops — an index_put_
           of the rows into the pool viewed as rows (indices computed outside the timing), preceded for kv8 by
           (x.float() / s).clamp(-448, 448).to(torch.float8_e4m3fn).  Their GB/s count the bytes read + written
+          rope (with page): rotary embedding + append in ONE call — the q = Nq newest tokens of every sequence as a token-major projection
+          output [B,Nq,(H + 2 K) D] through lc_rope_append_paged_f16 / _kv8 (LC_ROPE_PACKED_SRC, NeoX pairs, rot_dim = D, a base-10000 table
+          of N rows): rotated Q [B,H,Nq,D] out, rotated K and V into the pool.  rope:torch: the same job in torch ops — split, transpose,
+          positions from kv_len, gather the table rows, rotate Q and K in fp32 — followed by kv_append_paged(_kv8).  Their GB/s count the
+          bytes read + written: (H + 2 K) D fp16 in, H D fp16 + 2 K D pool elements out per token
 Every spec runs >= S seconds of back-to-back launches per round; R rounds interleave the specs (within-probe A/B,
 cdna_hip_programming.md rule 24); prints the kernel name the dispatcher reports, median and best TFLOP/s (matmul FLOPs: 4 B H N^2 D;
 causal: half of that, the flash-attn convention) and the median time per call."""
@@ -137,6 +142,43 @@ def run_append(spec, shape, use_torch, kv8, pool, lens):
     return name, 2.0 * B * kvh * nq * D * (2 + (1 if kv8 else 2)) / ms * 1e-6, ms
 
 
+def run_rope(spec, shape, use_torch, kv8, pool, lens):
+    """(name, bytes read + written in GB/s, ms per call) of rotating Q and K of the q = Nq newest tokens and appending K and V to the spec's
+    pools: the fused call on a packed projection output, or (torch) the same job in torch ops followed by kv_append_paged(_kv8)"""
+    B, H, kvh, nq, N, D, L, page = shape
+    k_pool, v_pool, table, k_scale, v_scale = pool
+    rkey = ("rope", B, H, kvh, nq, N, D)
+    if rkey not in cache:
+        for old_key in [x for x in cache if x[0] == "rope"]:
+            del cache[old_key]
+        g = torch.Generator(device="cuda").manual_seed(nq + 1)
+        cache[rkey] = (torch.randn(B, nq, (H + 2 * kvh) * D, device="cuda", generator=g).half(), capi.rope_table(N, D).cuda(),
+                       torch.empty(B, H, nq, D, device="cuda", dtype=torch.half))
+    qkv, cs, q_out = cache[rkey]
+    if use_torch:
+        half = D // 2
+        append = (lambda k, v: capi.kv_append_paged_kv8(k, v, k_pool, v_pool, table, lens, k_scale, v_scale)) if kv8 else \
+                 (lambda k, v: capi.kv_append_paged(k, v, k_pool, v_pool, table, lens))
+
+        def rotate(x, c, s):                                                         # x [B,heads,nq,D] fp16; c, s [B,1,nq,D/2] fp32
+            x1, x2 = x[..., :half].float(), x[..., half:].float()
+            return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).half()
+
+        def step():
+            parts = qkv.view(B, nq, H + 2 * kvh, D).transpose(1, 2)
+            pos = (lens.long().view(B, 1) - nq + torch.arange(nq, device="cuda").view(1, nq)).clamp(0, N - 1)
+            rows = cs[pos].view(B, 1, nq, D)
+            c, s = rows[..., :half], rows[..., half:]
+            q_out.copy_(rotate(parts[:, :H], c, s))
+            append(rotate(parts[:, H:H + kvh], c, s), parts[:, H + kvh:].contiguous())
+        name = "torch rope + " + capi.kv_append_paged_kernel_name(B, kvh, nq, page, N // page, D, kv8=kv8)
+    else:
+        name = capi.rope_append_paged_kernel_name(B, H, kvh, nq, page, N // page, D, D, N, kv8=kv8, src_row_stride=(H + 2 * kvh) * D)
+        step = lambda: capi.rope_append_paged_qkv(qkv, H, kvh, k_pool, v_pool, cs, table, lens, q_out=q_out, k_scale=k_scale, v_scale=v_scale)  # noqa: E731
+    ms = timed(step)
+    return name, 1.0 * B * nq * D * ((H + 2 * kvh) * 2 + H * 2 + 2 * kvh * (1 if kv8 else 2)) / ms * 1e-6, ms
+
+
 def run_decode(spec, shape, opts):
     """(name, K / V GB/s, ms per call) of one decode call"""
     B, H, N, D = shape
@@ -175,10 +217,16 @@ def run_decode(spec, shape, opts):
                 pools = [(pool.float() / s.view(1, kvh, 1, 1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn) for pool, s in zip(pools, sc)]
             cache[pkey] = (pools[0], pools[1], perm.view(B, mp).to(torch.int32).contiguous(), sc[0], sc[1])
         k_pool, v_pool, table, k_scale, v_scale = cache[pkey]
+    if "append" in opts and "rope" in opts:
+        raise SystemExit(f"{spec}: append and rope are two arms, not one spec")
     if "append" in opts:
         if not page or L < nq or causal or "sdpa" in opts:
             raise SystemExit(f"{spec}: append needs page=P and len >= q, and takes neither causal nor sdpa")
         return run_append(spec, (B, kvh, nq, N, D, L, page), "torch" in opts, kv8, cache[pkey], lens)
+    if "rope" in opts:
+        if not page or L < nq or causal or "sdpa" in opts:
+            raise SystemExit(f"{spec}: rope needs page=P and len >= q, and takes neither causal nor sdpa")
+        return run_rope(spec, (B, H, kvh, nq, N, D, L, page), "torch" in opts, kv8, cache[pkey], lens)
     capi.tune("attn_decode_split", split)
     try:
         if "sdpa" in opts:
@@ -268,6 +316,6 @@ for s in args:
     v, t = sorted(res[s]), sorted(times[s])
     if any(o.startswith("q=") for o in s.split(":")):     # decode: res holds K / V GB/s
         print(f"RATE {s:40s} {names[s]:38s} median {t[len(t) // 2] * 1e3:8.1f} us  best {t[0] * 1e3:8.1f}  worst {t[-1] * 1e3:8.1f}  "
-              f"{'R+W' if 'append' in s.split(':') else 'K/V'} {v[len(v) // 2]:7.0f} GB/s", flush=True)
+              f"{'R+W' if {'append', 'rope'} & set(s.split(':')) else 'K/V'} {v[len(v) // 2]:7.0f} GB/s", flush=True)
         continue
     print(f"RATE {s:34s} {names[s]:44s} median {v[len(v) // 2]:7.1f}  best {v[-1]:7.1f}  worst {v[0]:7.1f} TFLOP/s  {t[len(t) // 2] * 1e3:9.1f} us", flush=True)
