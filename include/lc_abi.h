@@ -548,6 +548,53 @@ size_t lc_attn_chunk_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, in
 int lc_attn_chunk_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D,
                                         int flags, char* buf, int buflen);
 
+/* EXTENSION: sliding-window and attention-sink attention over the three KV caches (attn_local.hip): the chunk entries
+ * above with two more arguments in front of `flags`, for models whose layers attend to the last W keys only (Mistral-class, Gemma 2 / 3,
+ * gpt-oss) and whose heads carry a learned sink logit (gpt-oss).  Neither can be had from outside: the low edge of a window moves per query
+ * row, and a sink changes the softmax denominator inside the kernel.
+ *   window  W > 0: query i of batch entry b, at position p = L_b - Nq + i, sees keys j with p - W < j <= p: W keys including its own (the
+ *           Hugging Face `sliding_window` convention; FlashAttention's window_size = (W - 1, 0)), the low edge clipped at key 0.  0: no low
+ *           edge.  W < 0, and W > 0 without LC_ATTN_CAUSAL: LC_ERR_ARG.
+ *   sinks   device float[H] or NULL, read by the kernel only (never by the host: the call stays graph-capturable, and a replay sees the
+ *           values of its time).  sinks[h] is a logit in natural units — it is NOT multiplied by 1 / sqrt(D) — of every row of query head h:
+ *           exp(sinks[h] - max) is added to the softmax denominator, nothing to the numerator.  -inf is no sink; +inf and NaN are not
+ *           supported.  Allowed with or without a window, causal or not.  A row with a sink and no visible key gets O = 0, as without one.
+ * Everything else is the chunk entries', word for word: Q, O [B,H,Nq,D] fp16, the kv_len clamp, the page-id clamp, the scales, alignment, the
+ * 2 GiB span bounds, D in {64, 128}, R = (H / Hkv) x Nq unbounded, the workspace rules and the capture / failed-lease fallback to S = 1.  The
+ * checks are the chunk entries' in their order, the two new LC_ERR_ARG cases right behind the unknown-flag check, all before any device work.
+ * window == 0 && sinks == NULL IS the chunk call: same plan, same kernel name, same bits.
+ * Otherwise: attn_local_kernel<D,RT> / attn_local_paged_kernel<D,RT> / attn_local_paged_kv8_kernel<D,RT> (R <= 64) or attn_local_chunk_kernel<D> /
+ * attn_local_chunk_paged_kernel<D> / attn_local_chunk_paged_kv8_kernel<D> (R > 64) on the grid of the decode / chunk kernel of that shape.  With
+ * a window a workgroup starts at the 64-key tile of the lowest key one of its rows sees, tile_lo = max(0, L_b - Nq + i_min + 1 - W) / 64
+ * (i_min: its lowest token; 0 for R <= 64 and for a row block that straddles a head boundary), and it is the tiles [tile_lo, T) that are cut
+ * into the S ranges: cache rows below tile_lo x 64 and block-table entries below that position are never read, and the time follows W, not L_b.
+ * A call with Nq = 1 whose L_b - W is a multiple of 64 computes, bit for bit, what the decode call computes on cache rows [L_b - W, L_b) with
+ * kv_len = W at equal S.  S never depends on kv_len: it follows the decode rule with the tiles of min(Ncap, W + Nq - 1 + 63) keys in place of
+ * those of Ncap when W > 0; "attn_decode_split" forces it; the workspace is S x B H Nq x (D + 1) floats as before.
+ * The two query calls take `window` and no sinks: S and the bytes do not depend on sinks; the name call reports the kernel of a call WITHOUT
+ * sinks (window = 0: the chunk call's name) — with sinks the kernel is the attn_local_* one of the same template arguments and S. */
+int lc_attn_local_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len,
+                      int B, int H, int Hkv, int Nq, int Ncap, int D, int window, const float* sinks, int flags,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_local_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D, int window);
+int lc_attn_local_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int window, int flags, char* buf, int buflen);
+int lc_attn_local_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                            const int* block_table, const int* kv_len,
+                            int B, int H, int Hkv, int Nq,
+                            int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_local_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window);
+int lc_attn_local_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window,
+                                    int flags, char* buf, int buflen);
+int lc_attn_local_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O,
+                            const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                            int B, int H, int Hkv, int Nq,
+                            int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_local_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window);
+int lc_attn_local_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window,
+                                        int flags, char* buf, int buflen);
+
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

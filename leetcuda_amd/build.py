@@ -31,7 +31,8 @@ ORACLE_NAME = "liblc_oracle.so"
 # paged kernels' names (attn_decode_paged_kernel<D, RT>) contain that string.
 AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_attn_decode_paged_kv8": "isa_audit_decode_paged_kv8.json",
                     "tu_kv_append": "isa_audit_kv_append.json", "tu_attn_chunk": "isa_audit_chunk.json",
-                    "tu_rope_append": "isa_audit_rope_append.json"}
+                    "tu_rope_append": "isa_audit_rope_append.json", "tu_attn_local": "isa_audit_local.json",
+                    "tu_attn_local_paged": "isa_audit_local_paged.json", "tu_attn_local_paged_kv8": "isa_audit_local_paged_kv8.json"}
 
 
 def _newer(target: Path, sources) -> bool:

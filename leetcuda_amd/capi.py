@@ -71,6 +71,15 @@ SYMBOLS = {
     "lc_attn_chunk_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_chunk_paged_kv8_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "lc_attn_chunk_paged_kv8_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _cp, _i]),
+    "lc_attn_local_f16": (_i, [_vp] * 5 + [_i] * 7 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_local_workspace_bytes": (C.c_size_t, [_i] * 7),
+    "lc_attn_local_kernel_name": (_i, [_i] * 8 + [_cp, _i]),
+    "lc_attn_local_paged_f16": (_i, [_vp] * 6 + [_i] * 9 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_local_paged_workspace_bytes": (C.c_size_t, [_i] * 8),
+    "lc_attn_local_paged_kernel_name": (_i, [_i] * 9 + [_cp, _i]),
+    "lc_attn_local_paged_kv8": (_i, [_vp] * 8 + [_i] * 9 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_local_paged_kv8_workspace_bytes": (C.c_size_t, [_i] * 8),
+    "lc_attn_local_paged_kv8_kernel_name": (_i, [_i] * 9 + [_cp, _i]),
     "lc_kv_append_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
@@ -465,7 +474,7 @@ def _decode_kernel_name(symbol, *shape, causal) -> str:
     return buf.value.decode()
 
 
-def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None, *, _entry="lc_attn_decode_f16"):
+def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None, *, _entry="lc_attn_decode_f16", _local=()):
     """Decode attention over a KV cache (lc_attn_decode_f16): q, o [B,H,Nq,D] fp16; k, v [B,Hkv,Ncap,D] fp16; kv_len None (= Ncap) or a
     DEVICE int32 [B] tensor of valid cache lengths, read by the kernel; causal: query i sees keys j <= kv_len[b] - Nq + i.  workspace: None or
     a device tensor of at least attn_decode_workspace_bytes(...) bytes (makes the split-KV form legal under graph capture)."""
@@ -476,7 +485,7 @@ def attn_decode(q, k, v, o, kv_len=None, causal=False, workspace=None, *, _entry
     if kv_len is not None:
         _need_gpu(kv_len)
         assert kv_len.dtype == torch.int32
-    check(getattr(load(), _entry)(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, *dims,
+    check(getattr(load(), _entry)(_ptr(q), _ptr(k), _ptr(v), _ptr(o), _ptr(kv_len) if kv_len is not None else None, *dims, *_local,
                                   ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
     return o
 
@@ -491,7 +500,7 @@ def attn_decode_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False) -> str:
     return _decode_kernel_name("lc_attn_decode_kernel_name", B, H, Hkv, Nq, Ncap, D, causal=causal)
 
 
-def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None, *, _entry="lc_attn_decode_paged_f16"):
+def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, workspace=None, *, _entry="lc_attn_decode_paged_f16", _local=()):
     """Decode attention over a paged KV cache (lc_attn_decode_paged_f16): q, o [B,H,Nq,D] fp16; k_pool, v_pool [num_pages,Hkv,page_size,D]
     fp16, page_size a power of two >= 16; block_table a DEVICE int32 [B,max_pages] tensor of pool page ids; kv_len a DEVICE int32 [B] tensor;
     both are read by the kernel only (page ids are clamped to the pool there).  causal, workspace: as attn_decode."""
@@ -501,7 +510,7 @@ def attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, w
     dims = _attn_dims_decode_paged(q, k_pool, v_pool, o, block_table, kv_len)
     _need_gpu(block_table, kv_len)
     assert block_table.dtype == torch.int32 and kv_len.dtype == torch.int32
-    check(getattr(load(), _entry)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), *dims,
+    check(getattr(load(), _entry)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(block_table), _ptr(kv_len), *dims, *_local,
                                   ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
     return o
 
@@ -539,7 +548,7 @@ def _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale):
 
 
 def attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=None, v_scale=None, causal=False, workspace=None, *,
-                          _entry="lc_attn_decode_paged_kv8"):
+                          _entry="lc_attn_decode_paged_kv8", _local=()):
     """Decode attention over a paged KV cache kept in fp8 (lc_attn_decode_paged_kv8): attn_decode_paged with k_pool8, v_pool8
     [num_pages,Hkv,page_size,D] of torch.float8_e4m3fn (or its bytes as uint8) and k_scale, v_scale DEVICE float32 [Hkv] tensors (None = 1.0):
     K = k_scale[g] K8, V = v_scale[g] V8.  The scales are read by the kernel only, like block_table and kv_len."""
@@ -547,7 +556,7 @@ def attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=N
     _need_gpu(q, k_pool8, v_pool8, o, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
     check(getattr(load(), _entry)(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(block_table), _ptr(kv_len),
                                   _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
-                                  *dims, ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
+                                  *dims, *_local, ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), _entry)
     return o
 
 
@@ -609,6 +618,90 @@ def attn_chunk_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D)
 def attn_chunk_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False) -> str:
     """R > 64: "attn_chunk_paged_kv8_kernel<D>", + " xS" with S > 1; R <= 64: attn_decode_paged_kv8_kernel_name's."""
     return _decode_kernel_name("lc_attn_chunk_paged_kv8_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, causal=causal)
+
+
+# Sliding-window and attention-sink attention (lc_attn_local_*; DESIGN.md section 4.3k): the chunk calls with a window of W keys and a sink
+# logit per query head.  window = 0 and sinks = None is the chunk call itself (same plan, name and bits).
+
+def _local_args(q, window, sinks):
+    """The checks of the two extra arguments of attn_local* (no GPU needed): window an int >= 0, sinks None or a float32 [H] tensor.  Returns
+    what goes between the dims and the flags of the C call; the caller asks for the sinks' device."""
+    import torch
+    if not isinstance(window, int) or window < 0:
+        raise ValueError(f"window must be an int >= 0, got {window!r}")
+    if sinks is None:
+        return window, None
+    if sinks.dtype != torch.float32:
+        raise TypeError(f"sinks must be float32, got {sinks.dtype}")
+    if q.dim() != 4 or tuple(sinks.shape) != (q.shape[1],):
+        _shape_err(f"sinks {tuple(sinks.shape)} for q {tuple(q.shape)}")
+    return window, sinks
+
+
+def _local_ptrs(local):
+    window, sinks = local
+    if sinks is not None:
+        _need_gpu(sinks)
+    return window, _ptr(sinks) if sinks is not None else None
+
+
+def attn_local(q, k, v, o, kv_len=None, causal=False, window=0, sinks=None, workspace=None):
+    """attn_chunk with a sliding window and attention sinks (lc_attn_local_f16).  window = W > 0 (causal only): the query at position
+    p = kv_len[b] - Nq + i sees keys p - W < j <= p, W keys with its own (the Hugging Face `sliding_window`); 0: no low edge.  sinks: None or
+    a DEVICE float32 [H] tensor of one logit per query head, in natural units (not scaled by 1 / sqrt(D)), that joins the softmax denominator
+    of every row of its head and contributes no value; read by the kernel only."""
+    local = _local_args(q, window, sinks)
+    _need_gpu(q)
+    return attn_decode(q, k, v, o, kv_len, causal=causal, workspace=workspace, _entry="lc_attn_local_f16", _local=_local_ptrs(local))
+
+
+def attn_local_workspace_bytes(B, H, Hkv, Nq, Ncap, D, window=0) -> int:
+    """Bytes of split-KV partials the current plan of this shape and window needs (0: one launch, no workspace); sinks do not change it."""
+    return int(load().lc_attn_local_workspace_bytes(B, H, Hkv, Nq, Ncap, D, window))
+
+
+def attn_local_kernel_name(B, H, Hkv, Nq, Ncap, D, causal=False, window=0) -> str:
+    """The kernel attn_local runs WITHOUT sinks: window > 0: "attn_local_kernel<D,RT>" (R <= 64) / "attn_local_chunk_kernel<D>", + " xS" with
+    S > 1 KV ranges; window = 0: attn_chunk_kernel_name's (with sinks: the attn_local_* kernel of the same arguments)."""
+    return _decode_kernel_name("lc_attn_local_kernel_name", B, H, Hkv, Nq, Ncap, D, window, causal=causal)
+
+
+def attn_local_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=False, window=0, sinks=None, workspace=None):
+    """attn_chunk_paged with attn_local's window and sinks (lc_attn_local_paged_f16)."""
+    local = _local_args(q, window, sinks)
+    _need_gpu(q)
+    return attn_decode_paged(q, k_pool, v_pool, o, block_table, kv_len, causal=causal, workspace=workspace, _entry="lc_attn_local_paged_f16",
+                             _local=_local_ptrs(local))
+
+
+def attn_local_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D, window=0) -> int:
+    """Bytes of split-KV partials the current plan of this shape and window needs: those of attn_local at Ncap = max_pages x page_size."""
+    return int(load().lc_attn_local_paged_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D, window))
+
+
+def attn_local_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False, window=0) -> str:
+    """window > 0: "attn_local_paged_kernel<D,RT>" / "attn_local_chunk_paged_kernel<D>", + " xS"; window = 0: attn_chunk_paged_kernel_name's."""
+    return _decode_kernel_name("lc_attn_local_paged_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, window, causal=causal)
+
+
+def attn_local_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale=None, v_scale=None, causal=False, window=0, sinks=None,
+                         workspace=None):
+    """attn_chunk_paged_kv8 with attn_local's window and sinks (lc_attn_local_paged_kv8); the sinks are not multiplied by k_scale."""
+    local = _local_args(q, window, sinks)
+    _kv8_args(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale)
+    _need_gpu(q)
+    return attn_decode_paged_kv8(q, k_pool8, v_pool8, o, block_table, kv_len, k_scale, v_scale, causal=causal, workspace=workspace,
+                                 _entry="lc_attn_local_paged_kv8", _local=_local_ptrs(local))
+
+
+def attn_local_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D, window=0) -> int:
+    """Bytes of split-KV partials the current plan of this shape and window needs: those of attn_local_paged for the same shape."""
+    return int(load().lc_attn_local_paged_kv8_workspace_bytes(B, H, Hkv, Nq, page_size, max_pages, D, window))
+
+
+def attn_local_paged_kv8_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, causal=False, window=0) -> str:
+    """window > 0: "attn_local_paged_kv8_kernel<D,RT>" / "attn_local_chunk_paged_kv8_kernel<D>", + " xS"; window = 0: the chunk call's name."""
+    return _decode_kernel_name("lc_attn_local_paged_kv8_kernel_name", B, H, Hkv, Nq, page_size, max_pages, D, window, causal=causal)
 
 
 def _kv_append_args(k_new, v_new, k_pool, v_pool, block_table, kv_len, k_scale=None, v_scale=None, kv8=False):

@@ -23,6 +23,8 @@ __global__ __launch_bounds__(256) void attn_chunk_kernel(const half_t* __restric
                                                          float sl2, long total_rows) {
   constexpr int RT = 4;
   constexpr bool CHUNK = true;
+  constexpr bool LOCAL = false;
+  const DecodeLocal lc{};
   constexpr bool PAGED = false;
   const DecodePaging pg{};
   constexpr bool KV8 = false;
@@ -39,6 +41,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kernel(const half_t* __r
                                                                int max_pages) {
   constexpr int RT = 4;
   constexpr bool CHUNK = true;
+  constexpr bool LOCAL = false;
+  const DecodeLocal lc{};
   constexpr bool PAGED = true;
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
@@ -58,6 +62,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kv8_kernel(const half_t*
                                                                    int num_pages, int lps, int max_pages) {
   constexpr int RT = 4;
   constexpr bool CHUNK = true;
+  constexpr bool LOCAL = false;
+  const DecodeLocal lc{};
   constexpr bool PAGED = true;
   constexpr bool KV8 = true;
   const DecodePaging pg{block_table, num_pages, lps, max_pages};

@@ -65,6 +65,12 @@ struct DecodeKv8 {
   const float *k_scale, *v_scale;   // device float[Hkv] or nullptr (= 1.0)
 };
 
+// A sliding window and attention sinks (attn_local.hip).  Every other kernel leaves both fields unused.
+struct DecodeLocal {
+  int window;           // W > 0: a row whose last visible key is p sees keys p - W + 1 .. p; 0: no lower edge
+  const float* sinks;   // device float[H], one logit per query head in natural units (not scaled by 1 / sqrt(D)), or nullptr
+};
+
 // eight e4m3 bytes (a: bytes 0 .. 3, b: bytes 4 .. 7, memory order) as eight fp16 values, element i = byte i: one v_cvt_scalef32_pk_f16_fp8 per two
 // elements, scale 1.0 — every e4m3 value is an fp16 value (the smallest, 2^-9, a normal one), so the conversion is exact; 0x7f / 0xff give NaN
 LC_DEVINL u32x4_t kv8_half8(uint32_t a, uint32_t b) {
@@ -80,6 +86,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
                                                           float* __restrict__ part_lse, int H, int Hkv, int Nq, int Ncap, int causal, int S,
                                                           float sl2, long total_rows) {
   constexpr bool CHUNK = false;
+  constexpr bool LOCAL = false;
+  const DecodeLocal lc{};
   constexpr bool PAGED = false;
   const DecodePaging pg{};
   constexpr bool KV8 = false;

@@ -9,6 +9,11 @@
 // head), ((b Hkv + kvh) RB + rb) S + s, and this workgroup owns rows 64 rb ... of the [R, D] matrix; causal, it walks only the keys below L_blk,
 // the largest limit of its rows.  With CHUNK = false the block offset `rbase` is the constant 0 and the walked length `Lw` is L_b: the nine
 // decode kernels' code does not depend on the parameter (DESIGN.md §4.3i compares their assembly).
+// A `constexpr bool LOCAL` with a `const DecodeLocal lc` (LOCAL = false: unused) is in scope as well.  LOCAL = true (the attn_local_*_kernel of
+// attn_local.hip; DESIGN.md §4.3k): a sliding window of lc.window keys (0: none) — a lower limit next to the upper one lim[rt], and a first tile
+// `tile_lo` next to the last one T: the workgroup walks tiles [tile_lo, T) and THOSE are cut into the S ranges — and an attention sink per query
+// head (lc.sinks, nullptr: none): a logit that joins the row's softmax denominator and carries no value, the start of (m, l) in range 0, wave 0.
+// With LOCAL = false tile_lo is the constant 0: the twelve decode and chunk kernels' code does not depend on the parameter (§4.3k compares it).
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -56,9 +61,26 @@
     }
   }
   const int T = (Lw + DEC_KVB - 1) / DEC_KVB;
+  // LOCAL: the tile of the lowest key a row of this workgroup can see, Llo = max(0, L_b - Nq + i_min + 1 - W) with i_min the workgroup's lowest
+  // token (0 unless a row block lies inside one head: then its first row's); nothing below tile_lo 64 is loaded, no table entry below it is read.
+  // (Llo > 0 implies Llo < Lw: tile_lo < T)
+  int tile_lo = 0;
+  if constexpr (LOCAL) {
+    if (lc.window > 0) {
+      int imin = 0;
+      if constexpr (CHUNK) {
+        const int span = (R - rbase < 64 ? R - rbase : 64) - 1;
+        const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nq);
+        imin = i0 + span >= Nq ? 0 : i0;
+      }
+      const long v = (long)Lb - Nq + imin + 1 - lc.window;
+      tile_lo = v > 0 ? (int)(v / DEC_KVB) : 0;
+    }
+  }
+  const int Tw = T - tile_lo;   // tiles this workgroup walks (LOCAL = false: T)
   // (T < 2^24 tiles — one head's cache is below 2 GiB — and S <= 64: the products fit 32 bits)
-  const int t0 = __builtin_amdgcn_readfirstlane((int)((unsigned)(s_idx * T) / (unsigned)S));
-  const int t1 = __builtin_amdgcn_readfirstlane((int)((unsigned)((s_idx + 1) * T) / (unsigned)S));
+  const int t0 = tile_lo + __builtin_amdgcn_readfirstlane((int)((unsigned)(s_idx * Tw) / (unsigned)S));
+  const int t1 = tile_lo + __builtin_amdgcn_readfirstlane((int)((unsigned)((s_idx + 1) * Tw) / (unsigned)S));
 
   const long row0 = ((long)b * H + (long)kvh * G) * Nq;   // the R rows of this (batch, K / V head): one contiguous [R, D] matrix
   const half_t* Qg = Q + row0 * D;
@@ -83,6 +105,9 @@
     int v = causal ? Lb - Nq + (r % Nq) + 1 : Lb;
     lim[rt] = v < 0 ? 0 : v;
   }
+  // LOCAL: key j is visible to a row iff lim - W <= j < lim, one unsigned compare of j - lim + W against W; no window is the widest one
+  // (j - lim >= -(2^31 - 1): the sum does not wrap below 0)
+  const unsigned wlo = LOCAL && lc.window > 0 ? (unsigned)lc.window : 0x7fffffffu;
 
   float m[RT], l[RT];
   f32x4_t o[RT][DB];
@@ -92,6 +117,21 @@
     l[rt] = 0.f;
 #pragma unroll
     for (int db = 0; db < DB; ++db) o[rt][db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  // LOCAL: the sink of the row's query head is one more score of the row, without a value: the running maximum starts at it (natural units,
+  // not scaled by 1 / sqrt(D): x log2 e only) and the running sum at exp2(0) = 1, in ONE lane group of ONE wave of ONE range; the wave merge,
+  // the partial's log-sum-exp and the combine kernel then see a wave that has met one key.  (-inf: l = 1 meets exp2(-inf) = 0 wherever it is
+  // used.)  Padding rows take row R - 1's head, as they take its Q.
+  if constexpr (LOCAL) {
+    if (lc.sinks && s_idx == 0 && w == 0) {
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        int r = rbase + 16 * rt + i16;
+        r = r < R ? r : R - 1;
+        m[rt] = lc.sinks[kvh * G + r / Nq] * 1.4426950408889634f;
+        l[rt] = h == 0 ? 1.f : 0.f;
+      }
+    }
   }
 
   char* vimg = lds + L::kVOff + w * L::kVBytes;
@@ -223,7 +263,10 @@
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float x = (k0 + 16 * kb + r < lim[rt]) ? st[kb][r] * sc2 : DEC_NEG_INF;   // select on the INDEX: the score may be anything
+          bool vis;   // select on the INDEX: the score may be anything
+          if constexpr (LOCAL) vis = (unsigned)(k0 + 16 * kb + r - lim[rt]) + wlo < wlo;
+          else vis = k0 + 16 * kb + r < lim[rt];
+          const float x = vis ? st[kb][r] * sc2 : DEC_NEG_INF;
           st[kb][r] = x;
           mx = fmaxf(mx, x);
         }

@@ -28,6 +28,8 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kv8_kernel(const half_t
                                                                     int Nq, int Ncap, int causal, int S, float sl2, long total_rows,
                                                                     int num_pages, int lps, int max_pages) {
   constexpr bool CHUNK = false;
+  constexpr bool LOCAL = false;
+  const DecodeLocal lc{};
   constexpr bool PAGED = true;
   constexpr bool KV8 = true;
   const DecodePaging pg{block_table, num_pages, lps, max_pages};

@@ -79,10 +79,16 @@ DecodeCall decode_flat(int B, int H, int Hkv, int Nq, int Ncap, int D, int flags
 DecodeCall decode_paged(int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int flags, int kv_bytes, bool chunk = false) {
   return DecodeCall{B, H, Hkv, Nq, D, flags, kv_bytes, true, 0, num_pages, page_size, max_pages, chunk};
 }
-// block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere)
+// the lc_attn_local_* entries: the chunk call c with a window and, a run call, its sinks (window = 0, no sinks: c itself)
+DecodeCall decode_local(DecodeCall c, int window, const float* sinks = nullptr) {
+  c.window = window;
+  c.sinks = sinks != nullptr;
+  return c;
+}
+// block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local call, or nullptr
 int decode_run(const DecodeCall& c, const void* Q, const void* K, const void* V, void* O, const int* kv_len, const int* block_table, const float* k_scale,
-               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream) {
-  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale};
+               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr) {
+  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks};
   DecodePlan p;
   if (int rc = check_attn_decode(c, &a, &p)) return rc;
   if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
@@ -413,6 +419,52 @@ size_t lc_attn_chunk_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, in
 
 int lc_attn_chunk_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int flags, char* buf, int buflen) {
   return decode_name(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1, true), buf, buflen);
+}
+
+// The local entries: the chunk entries' DecodeCall with a window and sinks (neither: the chunk call's plan, name and bits)
+int lc_attn_local_f16(const void* Q, const void* K, const void* V, void* O, const int* kv_len, int B, int H, int Hkv, int Nq, int Ncap, int D,
+                      int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_local(decode_flat(B, H, Hkv, Nq, Ncap, D, flags, true), window, sinks), Q, K, V, O, kv_len, nullptr, nullptr, nullptr, workspace,
+                    workspace_bytes, stream, sinks);
+}
+
+size_t lc_attn_local_workspace_bytes(int B, int H, int Hkv, int Nq, int Ncap, int D, int window) {
+  return decode_bytes(decode_local(decode_flat(B, H, Hkv, Nq, Ncap, D, window > 0 ? LC_ATTN_CAUSAL : 0, true), window));
+}
+
+int lc_attn_local_kernel_name(int B, int H, int Hkv, int Nq, int Ncap, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_local(decode_flat(B, H, Hkv, Nq, Ncap, D, flags, true), window), buf, buflen);
+}
+
+int lc_attn_local_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* block_table, const int* kv_len, int B, int H,
+                            int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_local(decode_paged(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), Q, Kpool, Vpool, O, kv_len,
+                    block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks);
+}
+
+size_t lc_attn_local_paged_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window) {
+  return decode_bytes(decode_local(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, window > 0 ? LC_ATTN_CAUSAL : 0, 2, true), window));
+}
+
+int lc_attn_local_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_local(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 2, true), window), buf, buflen);
+}
+
+int lc_attn_local_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* block_table, const int* kv_len,
+                            const float* k_scale, const float* v_scale, int B, int H, int Hkv, int Nq, int num_pages, int page_size, int max_pages,
+                            int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_local(decode_paged(B, H, Hkv, Nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), Q, Kpool8, Vpool8, O,
+                    kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks);
+}
+
+size_t lc_attn_local_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window) {
+  return decode_bytes(decode_local(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, window > 0 ? LC_ATTN_CAUSAL : 0, 1, true), window));
+}
+
+int lc_attn_local_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window, int flags, char* buf,
+                                        int buflen) {
+  return decode_name(decode_local(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1, true), window), buf, buflen);
 }
 
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,

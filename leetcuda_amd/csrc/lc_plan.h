@@ -157,6 +157,8 @@ struct DecodeCall {
   int Ncap;                              // contiguous only
   int num_pages, page_size, max_pages;   // paged only (the query calls state num_pages = 1: it decides nothing)
   bool chunk = false;                    // a chunk entry (lc_attn_chunk_*): R = (H / Hkv) x Nq is not bounded by 64
+  int window = 0;                        // lc_attn_local_*: W > 0: a sliding window of W keys (causal calls only); 0: none
+  bool sinks = false;                    // lc_attn_local_*: the call has a sink logit per query head (the query calls: never)
 };
 enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
 // ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
@@ -170,11 +172,15 @@ enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family read
 // A chunk call (DecodeCall::chunk) may have R > 64: RB = ceil(R / 64) row blocks per (batch, K / V head).  RB = 1 is the plan of
 // the decode call, whichever entry stated it; RB > 1: RT = 4, attn_chunk_kernel<D> / attn_chunk_paged_kernel<D> / attn_chunk_paged_kv8_kernel<D>
 // on B x Hkv x RB x S workgroups, S by the same rule with B x Hkv x RB groups.
+// A local call (lc_attn_local_*) with window = 0 and no sinks IS the chunk call: same plan.  With either, `local`: the
+// attn_local_*_kernel<D, RT> (RB = 1) / attn_local_chunk_*_kernel<D> (RB > 1) of its cache kind on the same grid; window > 0 puts the tiles of
+// min(Ncap, window + Nq - 1 + 63) keys — what one workgroup walks at most, tile misalignment included — in place of those of Ncap in the rule of S.
 struct DecodePlan {
   DecodeCall call;     // what was planned
   DecodeCache cache;
   int Ncap, RT, S;     // Ncap: the call's, or max_pages x page_size
   int RB;              // row blocks of 64 query rows per (batch, K / V head); > 1: the chunk kernels
+  bool local;          // window > 0 or sinks: the kernels of attn_local.hip
 };
 struct DecodePtrs {
   const half_t* Q;
@@ -184,12 +190,13 @@ struct DecodePtrs {
   hipStream_t st;
   const int* block_table;           // paged: device int32[B, max_pages]; else nullptr
   const float *k_scale, *v_scale;   // PAGED_KV8: device float[Hkv] or nullptr = 1.0; else nullptr
+  const float* sinks;               // a local call: device float[H] or nullptr = no sinks; else nullptr
 };
 // The checks of the three decode entry points, in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's
 // pointers (nullptr: a query call, which has none)
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p);
 int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p);   // checked arguments; nothing writes into a plan afterwards
-void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel); RB > 1: "attn_chunk_kernel<128> x8"
+void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel); RB > 1: "attn_chunk_kernel<128> x8"; local: "attn_local_kernel<128,1>", "attn_local_chunk_kernel<128>"
 // bytes of fp32 partials a plan with S > 1 needs: S x B H Nq rows x (D + 1) floats; 0 for S = 1
 inline size_t decode_workspace_bytes(const DecodePlan& p) {
   return p.S > 1 ? (size_t)p.S * ((size_t)p.call.B * p.call.H * p.call.Nq) * (size_t)(p.call.D + 1) * sizeof(float) : 0;
@@ -201,6 +208,9 @@ int launch_attn_decode_ranges(const DecodePlan& p, int S, const DecodePtrs& a, f
 // ... and of a plan with RB > 1: tu_attn_chunk.hip, the three kinds in one unit
 template <DecodeCache C>
 int launch_attn_chunk_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+// ... and of a local plan, RB = 1 or more: tu_attn_local_impl.h, instantiated in tu_attn_local.hip / _paged.hip / _paged_kv8.hip
+template <DecodeCache C>
+int launch_attn_local_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on

@@ -28,6 +28,9 @@ constexpr DecodeRanges kDecodeRanges[] = {launch_attn_decode_ranges<DecodeCache:
 // ... and of a plan with RB > 1 row blocks (tu_attn_chunk.hip)
 constexpr DecodeRanges kChunkRanges[] = {launch_attn_chunk_ranges<DecodeCache::FLAT>, launch_attn_chunk_ranges<DecodeCache::PAGED>,
                                          launch_attn_chunk_ranges<DecodeCache::PAGED_KV8>};
+// ... and of a local plan, whatever its RB (tu_attn_local*.hip)
+constexpr DecodeRanges kLocalRanges[] = {launch_attn_local_ranges<DecodeCache::FLAT>, launch_attn_local_ranges<DecodeCache::PAGED>,
+                                         launch_attn_local_ranges<DecodeCache::PAGED_KV8>};
 
 template <int D>
 int launch_decode_combine(long rows, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
@@ -54,7 +57,7 @@ int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace
   const long rows = (long)p.call.B * p.call.H * p.call.Nq;
   float* part_o = S > 1 ? part : nullptr;
   float* part_lse = S > 1 ? part + (size_t)S * rows * p.call.D : nullptr;
-  const int rc = (p.RB > 1 ? kChunkRanges : kDecodeRanges)[(int)p.cache](p, S, a, part_o, part_lse);
+  const int rc = (p.local ? kLocalRanges : p.RB > 1 ? kChunkRanges : kDecodeRanges)[(int)p.cache](p, S, a, part_o, part_lse);
   if (rc != LC_OK || S == 1) return rc;
   return p.call.D == 128 ? launch_decode_combine<128>(rows, S, a, part_o, part_lse) : launch_decode_combine<64>(rows, S, a, part_o, part_lse);
 }

@@ -726,9 +726,12 @@ int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
   p->Ncap = c.paged ? c.max_pages * c.page_size : c.Ncap;
   p->RT = R <= 16 ? 1 : R <= 32 ? 2 : 4;
   p->RB = (int)((R + 63) / 64);   // row blocks: each is a workgroup per KV range, and counts as a group of the rule
+  p->local = c.window > 0 || c.sinks;
   p->S = k.attn_decode_split;
   if (p->S > 0) return LC_OK;
-  const long groups = (long)c.B * c.Hkv * p->RB, tiles = ((long)p->Ncap + 63) / 64;
+  // (a window: a workgroup walks at most window + Nq - 1 keys and the rest of the tile its lowest one lies in — not kv_len's business either)
+  const long walked = c.window > 0 ? std::min((long)p->Ncap, (long)c.window + c.Nq - 1 + 63) : (long)p->Ncap;
+  const long groups = (long)c.B * c.Hkv * p->RB, tiles = (walked + 63) / 64;
   long S = (rule_cus(k) + groups - 1) / groups;
   S = std::min(S, tiles / 4);
   p->S = (int)std::max(1L, std::min(S, 64L));
@@ -736,6 +739,7 @@ int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
 }
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
   if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
+  if (c.window < 0 || (c.window > 0 && !(c.flags & LC_ATTN_CAUSAL))) return LC_ERR_ARG;   // a window is a lower edge of the causal mask
   if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
   if (c.H <= 0 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return LC_ERR_SHAPE;
   if (c.B <= 0 || c.Nq <= 0 || c.D <= 0) return LC_ERR_SHAPE;
@@ -758,11 +762,14 @@ int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
 }
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   static const char* const kKernels[] = {"attn_decode_kernel", "attn_decode_paged_kernel", "attn_decode_paged_kv8_kernel"};   // by DecodeCache
-  const char* kern = kKernels[(int)p.cache];
+  static const char* const kLocal[] = {"attn_local_kernel", "attn_local_paged_kernel", "attn_local_paged_kv8_kernel"};
+  const char* kern = (p.local ? kLocal : kKernels)[(int)p.cache];
   if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
     static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
-    if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", kChunk[(int)p.cache], p.call.D, p.S);
-    else snprintf(buf, buflen, "%s<%d>", kChunk[(int)p.cache], p.call.D);
+    static const char* const kLocalChunk[] = {"attn_local_chunk_kernel", "attn_local_chunk_paged_kernel", "attn_local_chunk_paged_kv8_kernel"};
+    const char* chunk = (p.local ? kLocalChunk : kChunk)[(int)p.cache];
+    if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", chunk, p.call.D, p.S);
+    else snprintf(buf, buflen, "%s<%d>", chunk, p.call.D);
     return;
   }
   if (p.S > 1) snprintf(buf, buflen, "%s<%d,%d> x%d", kern, p.call.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)

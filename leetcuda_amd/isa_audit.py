@@ -55,6 +55,8 @@ OWNED_AGPRS = [
     (re.compile(r"attn_decode_kernel|attn_decode_combine_kernel|attn_decode_paged_kernel|attn_decode_paged_kv8_kernel"), []),
     # ... and the chunked-prefill kernels (attn_chunk.hip: the decode body on row blocks)
     (re.compile(r"attn_chunk_kernel|attn_chunk_paged_kernel|attn_chunk_paged_kv8_kernel"), []),
+    # ... and the sliding-window / sink kernels (attn_local.hip: the decode body with LOCAL = true, R <= 64 and row blocks)
+    (re.compile(r"attn_local_(chunk_)?(paged_)?(kv8_)?kernel"), []),
     # ... and so are the append-to-cache kernels (kv_append_paged.hip)
     (re.compile(r"kv_append_paged_kernel|kv_append_paged_kv8_kernel"), []),
     # ... and the rotary-embedding + append kernels (rope_append_paged.hip)
