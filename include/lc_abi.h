@@ -443,7 +443,8 @@ int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page
  * Kernels: kv_append_paged_kernel<D>, kv_append_paged_kv8_kernel<D>.  The name calls never launch, take no num_pages (it decides nothing) and
  * return the status the run call gives that shape; a NULL buffer or buflen < 8: LC_ERR_ARG.
  * Not here: per-token or per-page scales, pools laid out [P,page_size,Hkv,D], an append to a contiguous cache, ragged Nq per sequence other
- * than by left padding.  (A token-major [B,Nq,Hkv,D] source and rotary embedding: lc_rope_append_paged_* below.) */
+ * than by left padding (a ragged batch: lc_rope_append_varlen_* below, which a table of cos = 1, sin = 0 makes a plain append).  (A
+ * token-major [B,Nq,Hkv,D] source and rotary embedding: lc_rope_append_paged_* below.) */
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
                            const int* block_table, const int* kv_len,
                            int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
@@ -594,6 +595,79 @@ int lc_attn_local_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool
 size_t lc_attn_local_paged_kv8_workspace_bytes(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window);
 int lc_attn_local_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int window,
                                         int flags, char* buf, int buflen);
+
+/* EXTENSION: ragged-batch (varlen) attention over the paged caches (attn_varlen.hip): the paged local entries above for a
+ * continuous-batching step, whose sequences bring different numbers of new tokens — a few prompts or one prefill chunk next to many sequences
+ * that decode one token.  The step is stated once: its tokens are packed token-major, one sequence behind the other, and cu_q holds the offsets
+ * (FlashAttention's flash_attn_varlen_func with a block table).  There is no contiguous-cache form: a ragged batch only exists on a paged cache.
+ *   Q, O    token-major [T, H, D] fp16: row t, head h at (t H + h) D — what lc_rope_append_varlen_* below writes.
+ *   cu_q    device int32[B + 1], read by the kernel only (never by the host, like kv_len: the call stays graph-capturable and a replay sees
+ *           the offsets of its time).  Sequence b owns rows q0 = clamp(cu_q[b], 0, T) ... q0 + Nq_b - 1 with
+ *           Nq_b = clamp(cu_q[b + 1] - q0, 0, min(max_nq, T - q0)).  The clamps are the memory-safety contract, like the page-id clamp: NO value
+ *           in cu_q makes a kernel read or write outside the T rows.  Nq_b = 0 is legal and does no work.  Rows at or past cu_q[B] (below T)
+ *           and rows below cu_q[0] are NOT written, whether the plan has one KV range or several.  (A row between the two that the clamps
+ *           leave to no sequence — cu_q not monotone, a sequence longer than max_nq — is not written with one KV range and holds an
+ *           unspecified value with several.)
+ *   T       host upper bound: the rows of Q and O.   max_nq   host upper bound: the largest Nq_b the caller will ever put in cu_q.
+ * kv_len[b] is the length AFTER the step's append: query i of sequence b sits at position p = L_b - Nq_b + i.  LC_ATTN_CAUSAL, window, sinks,
+ * the scales, the kv_len and page-id clamps, D in {64, 128}, the alignment and the span rules are lc_attn_local_paged_*'s, word for word.
+ * The checks are that entry's in its order; a NULL cu_q joins the NULL-pointer check (LC_ERR_ARG); T < 1, max_nq < 1 and max_nq > T join the
+ * shape check (LC_ERR_SHAPE).
+ * Plan: G = H / Hkv, RB = ceil(G max_nq / 64); B x Hkv x RB x S workgroups, of which one whose row block starts at or past G Nq_b returns at
+ * once.  RB = 1: attn_varlen_paged_kernel<D,RT> / attn_varlen_paged_kv8_kernel<D,RT> with the RT of the decode plan of R = G max_nq; RB > 1:
+ * attn_varlen_chunk_paged_kernel<D> / attn_varlen_chunk_paged_kv8_kernel<D>; window = 0 and sinks = NULL run the same kernels.  Inside a
+ * (sequence, K / V head) the rows are ordered as in the rectangular call: a ragged call whose Nq_b all equal max_nq computes, bit for bit,
+ * what lc_attn_local_paged_* computes at equal S on the same tokens as [B,H,Nq,D].  S never depends on device data: the decode rule with
+ * Hkv x min(B RB, ceil(G T / 64) + B) groups, and with W > 0 the tiles of min(Ncap, W + max_nq - 1 + 63) keys; "attn_decode_split" forces it.
+ * S > 1 is followed by attn_varlen_combine_kernel<D>.  The workspace is S x T H x (D + 1) floats, the workspace rules and the capture /
+ * failed-lease fallback to S = 1 are the other decode entries'.  The query calls take no sinks and no pointers. */
+int lc_attn_varlen_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                             const int* cu_q, const int* block_table, const int* kv_len,
+                             int B, int H, int Hkv, int T, int max_nq,
+                             int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_varlen_paged_workspace_bytes(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window);
+int lc_attn_varlen_paged_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                     int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O,
+                             const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                             int B, int H, int Hkv, int T, int max_nq,
+                             int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_varlen_paged_kv8_workspace_bytes(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window);
+int lc_attn_varlen_paged_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                         int flags, char* buf, int buflen);
+
+/* EXTENSION: rotary embedding + append for a ragged batch (rope_append_varlen.hip): lc_rope_append_paged_* for the
+ * step that lc_attn_varlen_paged_* reads, with the same cu_q, T and max_nq and the same clamps.
+ *   Q, Knew, Vnew   token-major fp16 with a row stride each, in elements: element (t, h, d) of Q at Q[t q_row_stride + h D + d], of Knew / Vnew
+ *           at ptr[t kv_row_stride + h D + d].  Both strides are multiples of 8, q_row_stride >= H D, kv_row_stride >= Hkv D.  Three pointers
+ *           into one projection output [T, (H + 2 Hkv) D] are the usual case, dense [T,H,D] and [T,Hkv,D] the other.  LC_ROPE_PACKED_SRC is
+ *           NOT accepted (LC_ERR_ARG): the strides say it all.
+ *   Qout    dense [T,H,D] fp16; may be Q itself when q_row_stride == H D (else LC_ERR_SHAPE).
+ * Token t belongs to the sequence b with cu_q[b] <= t < cu_q[b + 1] under the clamps above; its position is p = L_b - Nq_b + (t - q0).
+ * Everything else is lc_rope_append_paged_*'s rule, by the same device functions: p < 0 (no pool write, a zero row in Qout), a bad page id,
+ * the table-row clamp, NeoX and GPT-J pairs, partial rotary, fp32 arithmetic with one rounding, the fp8 code of the row rounded to fp16.  A
+ * token at or past cu_q[B], or one that the clamps leave to no sequence, writes NOTHING, in the pools or in Qout.
+ * The grid is over global token blocks, ceil(T / (2048 / D)) x (Hkv + H) workgroups: it does not grow with B x max_nq; every row finds its
+ * sequence by a binary search of cu_q.  Checks: lc_rope_append_paged_*'s in their order; a NULL cu_q is LC_ERR_ARG; T < 1, max_nq < 1,
+ * max_nq > T and a bad stride are LC_ERR_SHAPE.  rope_append_varlen_kernel<D,INTERLEAVED> / rope_append_varlen_kv8_kernel<D,INTERLEAVED>.
+ * There is no ragged plain append yet: a table of cos = 1, sin = 0 makes this call one. */
+int lc_rope_append_varlen_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                              const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len,
+                              int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                              int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_kv8(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8,
+                              const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len,
+                              const float* k_scale, const float* v_scale,
+                              int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                              int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                      int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                      char* buf, int buflen);
+int lc_rope_append_varlen_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                          int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                          char* buf, int buflen);
 
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */

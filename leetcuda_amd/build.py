@@ -32,7 +32,9 @@ ORACLE_NAME = "liblc_oracle.so"
 AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_attn_decode_paged_kv8": "isa_audit_decode_paged_kv8.json",
                     "tu_kv_append": "isa_audit_kv_append.json", "tu_attn_chunk": "isa_audit_chunk.json",
                     "tu_rope_append": "isa_audit_rope_append.json", "tu_attn_local": "isa_audit_local.json",
-                    "tu_attn_local_paged": "isa_audit_local_paged.json", "tu_attn_local_paged_kv8": "isa_audit_local_paged_kv8.json"}
+                    "tu_attn_local_paged": "isa_audit_local_paged.json", "tu_attn_local_paged_kv8": "isa_audit_local_paged_kv8.json",
+                    "tu_attn_varlen_paged": "isa_audit_varlen_paged.json", "tu_attn_varlen_paged_kv8": "isa_audit_varlen_paged_kv8.json",
+                    "tu_rope_append_varlen": "isa_audit_rope_append_varlen.json"}
 
 
 def _newer(target: Path, sources) -> bool:

@@ -80,6 +80,12 @@ SYMBOLS = {
     "lc_attn_local_paged_kv8": (_i, [_vp] * 8 + [_i] * 9 + [_vp, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_local_paged_kv8_workspace_bytes": (C.c_size_t, [_i] * 8),
     "lc_attn_local_paged_kv8_kernel_name": (_i, [_i] * 9 + [_cp, _i]),
+    "lc_attn_varlen_paged_f16": (_i, [_vp] * 7 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_workspace_bytes": (C.c_size_t, [_i] * 9),
+    "lc_attn_varlen_paged_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_kv8": (_i, [_vp] * 9 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_kv8_workspace_bytes": (C.c_size_t, [_i] * 9),
+    "lc_attn_varlen_paged_kv8_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
     "lc_kv_append_paged_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "lc_kv_append_paged_kernel_name": (_i, [_i, _i, _i, _i, _i, _i, _i, _cp, _i]),
@@ -88,6 +94,10 @@ SYMBOLS = {
     "lc_rope_append_paged_kv8": (_i, [_vp] * 11 + [_i] * 10 + [C.c_longlong, _i, _vp]),
     "lc_rope_append_paged_kernel_name": (_i, [_i] * 9 + [C.c_longlong, _i, _cp, _i]),
     "lc_rope_append_paged_kv8_kernel_name": (_i, [_i] * 9 + [C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_varlen_f16": (_i, [_vp] * 10 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_kv8": (_i, [_vp] * 12 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_varlen_kv8_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -895,6 +905,211 @@ def rope_append_paged_kernel_name(B, H, Hkv, Nq, page_size, max_pages, D, rot_di
     flags = (ROPE_INTERLEAVED if interleaved else 0) | (ROPE_PACKED_SRC if src_row_stride else 0)
     buf = C.create_string_buffer(128)
     check(getattr(load(), symbol)(B, H, Hkv, Nq, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, buf, 128), symbol)
+    return buf.value.decode()
+
+
+# Ragged-batch (varlen) attention and rotary embedding + append over the paged caches (lc_attn_varlen_paged_*, lc_rope_append_varlen_*; DESIGN.md
+# section 4.3l): one continuous-batching step — sequences with different numbers of new tokens — stated once.  The tokens are packed token-major,
+# q / o [T,H,D], and cu_q (DEVICE int32 [B + 1]) holds each sequence's first row; max_nq bounds every cu_q[b + 1] - cu_q[b].
+
+def _varlen_dims(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq):
+    """The shape checks of attn_varlen_paged* (no GPU needed): q, o [T,H,D]; pools [num_pages,Hkv,page_size,D]; cu_q int32 [B + 1] with B taken
+    from block_table [B,max_pages]; kv_len int32 [B]; 1 <= max_nq <= T.  Returns B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D."""
+    import torch
+    if q.dim() != 3 or k_pool.dim() != 4:
+        _shape_err("3-D [T,H,D] / 4-D [num_pages,Hkv,page_size,D] tensors expected")
+    T, H, D = q.shape
+    Hkv = k_pool.shape[1]
+    if k_pool.shape[3] != D or tuple(v_pool.shape) != tuple(k_pool.shape) or tuple(o.shape) != (T, H, D):
+        _shape_err(f"q {tuple(q.shape)} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)} o {tuple(o.shape)}")
+    if Hkv < 1 or Hkv > H or H % Hkv != 0:
+        _shape_err(f"{H} query heads on {Hkv} K/V heads")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    return B, H, Hkv, T, max_nq, k_pool.shape[0], k_pool.shape[2], block_table.shape[1], D
+
+
+def _varlen_batch(cu_q, block_table, kv_len) -> int:
+    """B from block_table [B,max_pages]; cu_q int32 [B + 1], kv_len int32 [B]"""
+    import torch
+    if block_table is None or block_table.dim() != 2:
+        _shape_err(f"block_table {None if block_table is None else tuple(block_table.shape)}: [B,max_pages] expected")
+    B = block_table.shape[0]
+    if kv_len is None or tuple(kv_len.shape) != (B,):
+        _shape_err(f"kv_len {None if kv_len is None else tuple(kv_len.shape)} for batch {B}")
+    if cu_q is None or tuple(cu_q.shape) != (B + 1,):
+        _shape_err(f"cu_q {None if cu_q is None else tuple(cu_q.shape)} for batch {B}: [B + 1] expected")
+    if block_table.dtype != torch.int32 or kv_len.dtype != torch.int32 or cu_q.dtype != torch.int32:
+        raise TypeError(f"block_table / kv_len / cu_q must be int32, got {block_table.dtype} / {kv_len.dtype} / {cu_q.dtype}")
+    return B
+
+
+def _varlen_local(q, window, sinks):
+    """_local_args for a token-major q [T,H,D]"""
+    import torch
+    if not isinstance(window, int) or window < 0:
+        raise ValueError(f"window must be an int >= 0, got {window!r}")
+    if sinks is None:
+        return window, None
+    if sinks.dtype != torch.float32:
+        raise TypeError(f"sinks must be float32, got {sinks.dtype}")
+    if q.dim() != 3 or tuple(sinks.shape) != (q.shape[1],):
+        _shape_err(f"sinks {tuple(sinks.shape)} for q {tuple(q.shape)}")
+    return window, sinks
+
+
+def attn_varlen_paged(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, causal=False, window=0, sinks=None, workspace=None):
+    """Attention of a ragged batch over a paged KV cache (lc_attn_varlen_paged_f16): q, o [T,H,D] fp16, token-major; sequence b owns rows
+    cu_q[b] .. cu_q[b + 1] - 1 (cu_q a DEVICE int32 [B + 1] tensor, read by the kernel only and clamped there into the T rows and to max_nq
+    rows a sequence); kv_len[b] is the length after the step's append, query i of sequence b sits at kv_len[b] - Nq_b + i.  Pools, block_table,
+    causal, window, sinks and workspace: attn_local_paged's.  Rows at or past cu_q[B] are not written."""
+    import torch
+    if q.dtype != torch.half or o.dtype != torch.half or k_pool.dtype != torch.half or v_pool.dtype != torch.half:
+        raise TypeError(f"q / o / k_pool / v_pool must be float16, got {q.dtype} / {o.dtype} / {k_pool.dtype} / {v_pool.dtype}")
+    dims = _varlen_dims(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq)
+    local = _varlen_local(q, window, sinks)
+    _need_gpu(q, k_pool, v_pool, o, cu_q, block_table, kv_len)
+    check(load().lc_attn_varlen_paged_f16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *dims,
+                                          *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
+          "lc_attn_varlen_paged_f16")
+    return o
+
+
+def attn_varlen_paged_kv8(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, k_scale=None, v_scale=None, causal=False, window=0,
+                          sinks=None, workspace=None):
+    """attn_varlen_paged over fp8 pools (lc_attn_varlen_paged_kv8): k_pool8, v_pool8 of torch.float8_e4m3fn (or its bytes as uint8), k_scale,
+    v_scale DEVICE float32 [Hkv] or None = 1.0, as attn_local_paged_kv8."""
+    import torch
+    fp8 = (torch.float8_e4m3fn, torch.uint8)
+    if q.dtype != torch.half or o.dtype != torch.half:
+        raise TypeError(f"q / o must be float16, got {q.dtype} / {o.dtype}")
+    if k_pool8.dtype not in fp8 or v_pool8.dtype not in fp8:
+        raise TypeError(f"k_pool8 / v_pool8 must be float8_e4m3fn or uint8, got {k_pool8.dtype} / {v_pool8.dtype}")
+    dims = _varlen_dims(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq)
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            continue
+        if s.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {s.dtype}")
+        if tuple(s.shape) != (dims[2],):
+            _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
+    local = _varlen_local(q, window, sinks)
+    _need_gpu(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    check(load().lc_attn_varlen_paged_kv8(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len),
+                                          _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None, *dims,
+                                          *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
+          "lc_attn_varlen_paged_kv8")
+    return o
+
+
+def attn_varlen_paged_workspace_bytes(B, H, Hkv, T, max_nq, page_size, max_pages, D, window=0, kv8=False) -> int:
+    """Bytes of split-KV partials the current plan of this ragged shape needs: S x T H x (D + 1) floats, 0 for one KV range."""
+    symbol = "lc_attn_varlen_paged_kv8_workspace_bytes" if kv8 else "lc_attn_varlen_paged_workspace_bytes"
+    return int(getattr(load(), symbol)(B, H, Hkv, T, max_nq, page_size, max_pages, D, window))
+
+
+def attn_varlen_paged_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=False, window=0, kv8=False) -> str:
+    """"attn_varlen_paged_kernel<D,RT>" (G max_nq <= 64) / "attn_varlen_chunk_paged_kernel<D>" (kv8: the _kv8 kernels), + " xS" with S > 1."""
+    symbol = "lc_attn_varlen_paged_kv8_kernel_name" if kv8 else "lc_attn_varlen_paged_kernel_name"
+    return _decode_kernel_name(symbol, B, H, Hkv, T, max_nq, page_size, max_pages, D, window, causal=causal)
+
+
+def _row_stride(t, what):
+    """the row stride, in elements, of a token-major [T,heads,D] tensor whose rows are dense: a view into a wider projection output is accepted"""
+    T, heads, D = t.shape
+    if t.stride(2) != 1 or (heads > 1 and t.stride(1) != D):
+        _shape_err(f"{what} strides {tuple(t.stride())}: rows of heads x D dense elements are expected")
+    stride = t.stride(0) if T > 1 else heads * D
+    if stride < heads * D or stride % 8 != 0:
+        _shape_err(f"{what} strides {tuple(t.stride())}: a row stride >= {heads * D}, a multiple of 8, is expected")
+    return stride
+
+
+def _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale=None, v_scale=None, kv8=False):
+    """The dtype and shape checks of rope_append_varlen / _kv8 (no GPU needed): fp16 q [T,H,D], k_new, v_new [T,Hkv,D] — dense, or views with one
+    row stride each (k_new and v_new share theirs) —, pools [num_pages,Hkv,page_size,D], float32 cos_sin [max_pos, rot_dim], q_out (if given)
+    fp16 [T,H,D].  Returns (B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride)."""
+    import torch
+    if q.dtype != torch.half or k_new.dtype != torch.half or v_new.dtype != torch.half:
+        raise TypeError(f"q / k_new / v_new must be float16, got {q.dtype} / {k_new.dtype} / {v_new.dtype}")
+    pool_types = (torch.float8_e4m3fn, torch.uint8) if kv8 else (torch.half,)
+    if k_pool.dtype not in pool_types or v_pool.dtype not in pool_types:
+        raise TypeError(f"k_pool / v_pool must be {' or '.join(str(t) for t in pool_types)}, got {k_pool.dtype} / {v_pool.dtype}")
+    if q_out is not None and q_out.dtype != torch.half:
+        raise TypeError(f"q_out must be float16, got {q_out.dtype}")
+    if cos_sin.dtype != torch.float32:
+        raise TypeError(f"cos_sin must be float32, got {cos_sin.dtype}")
+    if q.dim() != 3 or k_new.dim() != 3 or k_pool.dim() != 4:
+        _shape_err("3-D [T,H,D] / [T,Hkv,D] and 4-D [num_pages,Hkv,page_size,D] tensors expected")
+    T, H, D = q.shape
+    Hkv = k_pool.shape[1]
+    if tuple(k_new.shape) != (T, Hkv, D) or tuple(v_new.shape) != (T, Hkv, D) or k_pool.shape[3] != D or tuple(v_pool.shape) != tuple(k_pool.shape):
+        _shape_err(f"q {tuple(q.shape)} k_new {tuple(k_new.shape)} v_new {tuple(v_new.shape)} k_pool {tuple(k_pool.shape)} v_pool {tuple(v_pool.shape)}")
+    if Hkv < 1 or H % Hkv != 0:
+        _shape_err(f"{H} query heads on {Hkv} K/V heads")
+    if q_out is not None and tuple(q_out.shape) != (T, H, D):
+        _shape_err(f"q_out {tuple(q_out.shape)} vs q {tuple(q.shape)}")
+    if cos_sin.dim() != 2 or cos_sin.shape[0] < 1 or cos_sin.shape[1] % 16 != 0 or not 16 <= cos_sin.shape[1] <= D:
+        _shape_err(f"cos_sin {tuple(cos_sin.shape)}: [max_pos, rot_dim], rot_dim a multiple of 16 in [16, {D}]")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            continue
+        if not kv8:
+            raise TypeError("k_scale / v_scale belong to fp8 pools")
+        if s.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {s.dtype}")
+        if tuple(s.shape) != (Hkv,):
+            _shape_err(f"{name} {tuple(s.shape)} for {Hkv} K/V heads")
+    qs, ks = _row_stride(q, "q"), _row_stride(k_new, "k_new")
+    if _row_stride(v_new, "v_new") != ks:
+        _shape_err(f"k_new / v_new row strides {ks} / {_row_stride(v_new, 'v_new')}: one stride for both is expected")
+    if q_out is q and qs != H * D:
+        _shape_err("in place (q_out is q) needs a dense q")
+    return B, H, Hkv, T, max_nq, k_pool.shape[0], k_pool.shape[2], block_table.shape[1], D, cos_sin.shape[1], cos_sin.shape[0], qs, ks
+
+
+def _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, kv8):
+    import torch
+    args = _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale, v_scale, kv8)
+    for t in (q, k_new, v_new):      # (views into a projection output are not contiguous: the kernel strides)
+        if not t.is_cuda:
+            raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    if q_out is None:
+        q_out = torch.empty((args[3], args[1], args[8]), dtype=torch.half, device=q.device)
+    _need_gpu(q_out, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    scale_ptrs = [_ptr(s) if s is not None else None for s in (k_scale, v_scale)] if kv8 else []
+    symbol = "lc_rope_append_varlen_kv8" if kv8 else "lc_rope_append_varlen_f16"
+    check(getattr(load(), symbol)(_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(q_out), _ptr(k_pool), _ptr(v_pool), _ptr(cos_sin), _ptr(cu_q),
+                                  _ptr(block_table), _ptr(kv_len), *scale_ptrs, *args, ROPE_INTERLEAVED if interleaved else 0, _stream()), symbol)
+    return q_out
+
+
+def rope_append_varlen(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out=None, interleaved=False):
+    """rope_append_paged for a ragged batch (lc_rope_append_varlen_f16), ONE launch: q [T,H,D], k_new, v_new [T,Hkv,D] fp16, token-major — dense
+    tensors or views into the QKV projection's output [T,(H + 2 Hkv) D], e.g. qkv[:, :H * D].view(T, H, D).  Token t of the sequence b with
+    cu_q[b] <= t < cu_q[b + 1] is rotated at position kv_len[b] - Nq_b + (t - cu_q[b]) and its K and V rows go where kv_append_paged puts
+    them; cu_q, max_nq and the clamps are attn_varlen_paged's.  Returns q_out [T,H,D] dense (None: allocated; `q_out is q`: in place, dense q
+    only), what attn_varlen_paged reads.  A token at or past cu_q[B] writes nothing."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, None, None, False)
+
+
+def rope_append_varlen_kv8(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, block_table, kv_len, max_nq, q_out=None, interleaved=False,
+                           k_scale=None, v_scale=None):
+    """rope_append_varlen into fp8 pools (lc_rope_append_varlen_kv8): rope_append_paged_kv8's codes and scales."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, True)
+
+
+def rope_append_varlen_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, interleaved=False, kv8=False, q_row_stride=None,
+                                   kv_row_stride=None) -> str:
+    """"rope_append_varlen_kernel<D,INTERLEAVED>" / "rope_append_varlen_kv8_kernel<D,INTERLEAVED>" (strides None: dense)."""
+    symbol = "lc_rope_append_varlen_kv8_kernel_name" if kv8 else "lc_rope_append_varlen_kernel_name"
+    buf = C.create_string_buffer(128)
+    check(getattr(load(), symbol)(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, H * D if q_row_stride is None else q_row_stride,
+                                  Hkv * D if kv_row_stride is None else kv_row_stride, ROPE_INTERLEAVED if interleaved else 0, buf, 128), symbol)
     return buf.value.decode()
 
 

@@ -29,6 +29,8 @@ __global__ __launch_bounds__(256) void attn_chunk_kernel(const half_t* __restric
   const DecodePaging pg{};
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -49,6 +51,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kernel(const half_t* __r
   const DecodePaging pg{block_table, num_pages, lps, max_pages};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -71,6 +75,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kv8_kernel(const half_t*
   // (the body takes the pools as byte bases only: page_base)
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 

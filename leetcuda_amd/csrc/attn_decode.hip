@@ -71,6 +71,13 @@ struct DecodeLocal {
   const float* sinks;   // device float[H], one logit per query head in natural units (not scaled by 1 / sqrt(D)), or nullptr
 };
 
+// A ragged batch (attn_varlen.hip): Q and O are token-major [T, H, D] and cu_q holds the row offsets of the sequences.  Every
+// other kernel leaves both fields unused.
+struct DecodeVarlen {
+  const int* cu_q;   // device int32[B + 1]; read by the kernel only, every value clamped into [0, T]
+  int T;             // rows of Q and O
+};
+
 // eight e4m3 bytes (a: bytes 0 .. 3, b: bytes 4 .. 7, memory order) as eight fp16 values, element i = byte i: one v_cvt_scalef32_pk_f16_fp8 per two
 // elements, scale 1.0 — every e4m3 value is an fp16 value (the smallest, 2^-9, a normal one), so the conversion is exact; 0x7f / 0xff give NaN
 LC_DEVINL u32x4_t kv8_half8(uint32_t a, uint32_t b) {
@@ -92,6 +99,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
   const DecodePaging pg{};
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 

@@ -14,6 +14,12 @@
 // `tile_lo` next to the last one T: the workgroup walks tiles [tile_lo, T) and THOSE are cut into the S ranges — and an attention sink per query
 // head (lc.sinks, nullptr: none): a logit that joins the row's softmax denominator and carries no value, the start of (m, l) in range 0, wave 0.
 // With LOCAL = false tile_lo is the constant 0: the twelve decode and chunk kernels' code does not depend on the parameter (§4.3k compares it).
+// A `constexpr bool VARLEN` with a `const DecodeVarlen vl` (VARLEN = false: unused) is the last one.  VARLEN = true (the attn_varlen_*_kernel of
+// attn_varlen.hip; DESIGN.md §4.3l): Q and O are token-major [T, H, D] and sequence b owns the tokens q0 = clamp(cu_q[b], 0, T) ... q0 + Nq_b - 1,
+// Nq_b = clamp(cu_q[b + 1] - q0, 0, min(Nq, T - q0)).  The argument Nq is then max_nq, the host's bound, and sizes the grid's RB only; every
+// other use is the workgroup-uniform `Nqb` = Nq_b.  The row order inside a (sequence, K / V head) stays r = g Nq_b + i: only the ADDRESS of a row
+// changes, global row (q0 + r % Nq_b) H + kvh G + r / Nq_b in place of row0 + r.  A workgroup whose row block starts at or past R_b returns in
+// front of the first LDS access and barrier.  With VARLEN = false Nqb IS Nq: the 36 other kernels' code does not depend on the parameter.
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -44,7 +50,16 @@
     rbase = 64 * (bks - bk * RB);
   }
   const int b = __builtin_amdgcn_readfirstlane(bk / Hkv), kvh = bk - b * Hkv;
-  const int G = __builtin_amdgcn_readfirstlane(H / Hkv), R = G * Nq;
+  const int G = __builtin_amdgcn_readfirstlane(H / Hkv);
+  int Nqb = Nq, q0 = 0;   // VARLEN: this sequence's tokens, clamped into the T rows whatever cu_q holds
+  if constexpr (VARLEN) {
+    const int c0 = __builtin_amdgcn_readfirstlane(vl.cu_q[b]), c1 = __builtin_amdgcn_readfirstlane(vl.cu_q[b + 1]);
+    q0 = c0 < 0 ? 0 : (c0 > vl.T ? vl.T : c0);
+    const int cap = Nq < vl.T - q0 ? Nq : vl.T - q0;
+    Nqb = c1 <= q0 ? 0 : (c1 - q0 > cap ? cap : c1 - q0);   // (c1 > q0 >= 0: the difference does not wrap)
+    if (rbase >= G * Nqb) return;   // no row of this sequence in the block (Nq_b = 0 included): nothing touched
+  }
+  const int R = G * Nqb;
   int Lb = kv_len ? kv_len[b] : Ncap;
   Lb = __builtin_amdgcn_readfirstlane(Lb);   // (a vector load of a uniform address: tell hipcc that the tile loop is wave-uniform)
   Lb = Lb < 0 ? 0 : (Lb > Ncap ? Ncap : Lb);
@@ -54,9 +69,9 @@
   if constexpr (CHUNK) {
     if (causal) {
       const int span = (R - rbase < 64 ? R - rbase : 64) - 1;   // last row of the block - first
-      const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nq);
-      const int imax = i0 + span >= Nq ? Nq - 1 : i0 + span;
-      const int v = Lb - Nq + imax + 1;
+      const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nqb);
+      const int imax = i0 + span >= Nqb ? Nqb - 1 : i0 + span;
+      const int v = Lb - Nqb + imax + 1;
       Lw = v < 0 ? 0 : (v > Lb ? Lb : v);
     }
   }
@@ -70,10 +85,10 @@
       int imin = 0;
       if constexpr (CHUNK) {
         const int span = (R - rbase < 64 ? R - rbase : 64) - 1;
-        const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nq);
-        imin = i0 + span >= Nq ? 0 : i0;
+        const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nqb);
+        imin = i0 + span >= Nqb ? 0 : i0;
       }
-      const long v = (long)Lb - Nq + imin + 1 - lc.window;
+      const long v = (long)Lb - Nqb + imin + 1 - lc.window;
       tile_lo = v > 0 ? (int)(v / DEC_KVB) : 0;
     }
   }
@@ -84,6 +99,11 @@
 
   const long row0 = ((long)b * H + (long)kvh * G) * Nq;   // the R rows of this (batch, K / V head): one contiguous [R, D] matrix
   const half_t* Qg = Q + row0 * D;
+  // VARLEN: the global row of row r of this (sequence, K / V head) in the token-major [T, H, D] buffers (q0 + i < T: the clamps above)
+  auto vrow = [&](int r) {
+    const int g = r / Nqb;
+    return (long)(q0 + (r - g * Nqb)) * H + kvh * G + g;
+  };
   // (PAGED: K / V are the pools; the base of a load group is that of its page, below)
   const half_t* Kg = PAGED ? K : K + ((long)b * Hkv + kvh) * (long)Ncap * D;
   const half_t* Vg = PAGED ? V : V + ((long)b * Hkv + kvh) * (long)Ncap * D;
@@ -92,7 +112,10 @@
   for (int c = tid; c < 16 * RT * CH; c += 256) {
     const int r = c / CH, ch = c % CH;
     const int rs = rbase + r < R ? rbase + r : R - 1;
-    *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Qg + (long)rs * D + ch * 8);
+    if constexpr (VARLEN)
+      *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Q + vrow(rs) * D + ch * 8);
+    else
+      *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Qg + (long)rs * D + ch * 8);
   }
   __syncthreads();
 
@@ -102,7 +125,7 @@
   for (int rt = 0; rt < RT; ++rt) {
     int r = rbase + 16 * rt + i16;
     r = r < R ? r : R - 1;
-    int v = causal ? Lb - Nq + (r % Nq) + 1 : Lb;
+    int v = causal ? Lb - Nqb + (r % Nqb) + 1 : Lb;
     lim[rt] = v < 0 ? 0 : v;
   }
   // LOCAL: key j is visible to a row iff lim - W <= j < lim, one unsigned compare of j - lim + W against W; no window is the widest one
@@ -128,7 +151,7 @@
       for (int rt = 0; rt < RT; ++rt) {
         int r = rbase + 16 * rt + i16;
         r = r < R ? r : R - 1;
-        m[rt] = lc.sinks[kvh * G + r / Nq] * 1.4426950408889634f;
+        m[rt] = lc.sinks[kvh * G + r / Nqb] * 1.4426950408889634f;
         l[rt] = h == 0 ? 1.f : 0.f;
       }
     }
@@ -381,7 +404,8 @@
     if (r >= R) continue;   // padding rows store nothing
     float inv = lt[rt] > 0.f ? 1.f / lt[rt] : 0.f;
     if constexpr (KV8) inv *= vsc;
-    const long row = row0 + r;
+    long row = row0 + r;
+    if constexpr (VARLEN) row = vrow(r);
     if (S == 1) {
 #pragma unroll
       for (int db = 0; db < DB; ++db) {

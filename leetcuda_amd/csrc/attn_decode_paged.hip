@@ -31,6 +31,8 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const half_t* __
   const DecodePaging pg{block_table, num_pages, lps, max_pages};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 

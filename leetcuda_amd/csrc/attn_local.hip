@@ -29,6 +29,8 @@ __global__ __launch_bounds__(256) void attn_local_kernel(const half_t* __restric
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
   const DecodeLocal lc{window, sinks};
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -46,6 +48,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_kernel(const half_t* __r
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
   const DecodeLocal lc{window, sinks};
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -65,6 +69,8 @@ __global__ __launch_bounds__(256) void attn_local_paged_kernel(const half_t* __r
   const DecodeLocal lc{window, sinks};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -86,6 +92,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kernel(const half_
   const DecodeLocal lc{window, sinks};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -108,6 +116,8 @@ __global__ __launch_bounds__(256) void attn_local_paged_kv8_kernel(const half_t*
   // (the body takes the pools as byte bases only: page_base)
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 
@@ -130,6 +140,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kv8_kernel(const h
   const DecodeLocal lc{window, sinks};
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool VARLEN = false;
+  const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
 

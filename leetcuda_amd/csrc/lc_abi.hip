@@ -85,10 +85,17 @@ DecodeCall decode_local(DecodeCall c, int window, const float* sinks = nullptr) 
   c.sinks = sinks != nullptr;
   return c;
 }
-// block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local call, or nullptr
+// the lc_attn_varlen_paged_* entries: the paged local call of Nq = max_nq on T token-major rows
+DecodeCall decode_varlen(DecodeCall c, int T) {
+  c.varlen = true;
+  c.T = T;
+  c.max_nq = c.Nq;
+  return c;
+}
+// block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local or varlen call, or nullptr; cu_q: a varlen call
 int decode_run(const DecodeCall& c, const void* Q, const void* K, const void* V, void* O, const int* kv_len, const int* block_table, const float* k_scale,
-               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr) {
-  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks};
+               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr, const int* cu_q = nullptr) {
+  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks, cu_q};
   DecodePlan p;
   if (int rc = check_attn_decode(c, &a, &p)) return rc;
   if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
@@ -138,6 +145,26 @@ int rope_run(const RopeAppendCall& c, const void* Q, const void* Knew, const voi
   if (int rc = check_rope_append(c, &p)) return rc;
   if (int rc = launch_guard()) return rc;
   return launch_rope_append(c, p);
+}
+// the lc_rope_append_varlen_* entries: the rope call of Nq = max_nq on T token-major rows with a stride each
+RopeAppendCall rope_varlen_call(int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                long long q_row_stride, long long kv_row_stride, int flags, int kv_bytes) {
+  RopeAppendCall c = rope_call(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, flags, kv_bytes);
+  c.varlen = true;
+  c.T = T;
+  c.max_nq = max_nq;
+  c.kv_row_stride = kv_row_stride;
+  return c;
+}
+int rope_varlen_run(const RopeAppendCall& c, const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                    const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                    void* stream) {
+  const RopeAppendPtrs p{AppendPtrs{static_cast<const half_t*>(Knew), static_cast<const half_t*>(Vnew), Kpool, Vpool, block_table, kv_len, k_scale, v_scale,
+                                    static_cast<hipStream_t>(stream)},
+                         static_cast<const half_t*>(Q), static_cast<half_t*>(Qout), cos_sin, cu_q};
+  if (int rc = check_rope_append(c, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_rope_append_varlen(c, p);
 }
 int rope_name(const RopeAppendCall& c, char* buf, int buflen) {
   if (!buf || buflen < 8) return LC_ERR_ARG;
@@ -467,6 +494,42 @@ int lc_attn_local_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_
   return decode_name(decode_local(decode_paged(B, H, Hkv, Nq, 1, page_size, max_pages, D, flags, 1, true), window), buf, buflen);
 }
 
+// The varlen entries: the paged local entries' DecodeCall of Nq = max_nq, with cu_q and T (no contiguous form: a ragged batch lives on a paged cache)
+int lc_attn_varlen_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* cu_q, const int* block_table, const int* kv_len,
+                             int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+                             const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T), Q,
+                    Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q);
+}
+
+size_t lc_attn_varlen_paged_workspace_bytes(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window) {
+  return decode_bytes(
+      decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, window > 0 ? LC_ATTN_CAUSAL : 0, 2, true), window), T));
+}
+
+int lc_attn_varlen_paged_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf,
+                                     int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T), buf, buflen);
+}
+
+int lc_attn_varlen_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* cu_q, const int* block_table,
+                             const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages,
+                             int page_size, int max_pages, int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T), Q,
+                    Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q);
+}
+
+size_t lc_attn_varlen_paged_kv8_workspace_bytes(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window) {
+  return decode_bytes(
+      decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, window > 0 ? LC_ATTN_CAUSAL : 0, 1, true), window), T));
+}
+
+int lc_attn_varlen_paged_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf,
+                                         int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T), buf, buflen);
+}
+
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,
                            int Nq, int num_pages, int page_size, int max_pages, int D, int flags, void* stream) {
   return append_run(AppendCall{B, Hkv, Nq, D, flags, 2, num_pages, page_size, max_pages}, Knew, Vnew, Kpool, Vpool, block_table, kv_len, nullptr, nullptr,
@@ -513,6 +576,33 @@ int lc_rope_append_paged_kernel_name(int B, int H, int Hkv, int Nq, int page_siz
 int lc_rope_append_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                          long long src_row_stride, int flags, char* buf, int buflen) {
   return rope_name(rope_call(B, H, Hkv, Nq, 1, page_size, max_pages, D, rot_dim, max_pos, src_row_stride, flags, 1), buf, buflen);
+}
+
+int lc_rope_append_varlen_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool, const float* cos_sin,
+                              const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages,
+                              int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                              void* stream) {
+  return rope_varlen_run(rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2),
+                         Q, Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream);
+}
+
+int lc_rope_append_varlen_kv8(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8, const float* cos_sin,
+                              const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H,
+                              int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                              long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
+  return rope_varlen_run(rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1),
+                         Q, Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream);
+}
+
+// (the name calls take no num_pages: it decides nothing)
+int lc_rope_append_varlen_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                      long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2), buf, buflen);
+}
+
+int lc_rope_append_varlen_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                          long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1), buf, buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -159,6 +159,8 @@ struct DecodeCall {
   bool chunk = false;                    // a chunk entry (lc_attn_chunk_*): R = (H / Hkv) x Nq is not bounded by 64
   int window = 0;                        // lc_attn_local_*: W > 0: a sliding window of W keys (causal calls only); 0: none
   bool sinks = false;                    // lc_attn_local_*: the call has a sink logit per query head (the query calls: never)
+  bool varlen = false;                   // lc_attn_varlen_paged_*: a ragged batch — Q, O token-major [T,H,D], cu_q[B + 1]; Nq = max_nq, chunk = true
+  int T = 0, max_nq = 0;                 // varlen only: the rows of Q and O, and the host's bound on every Nq_b
 };
 enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
 // ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
@@ -175,6 +177,10 @@ enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family read
 // A local call (lc_attn_local_*) with window = 0 and no sinks IS the chunk call: same plan.  With either, `local`: the
 // attn_local_*_kernel<D, RT> (RB = 1) / attn_local_chunk_*_kernel<D> (RB > 1) of its cache kind on the same grid; window > 0 puts the tiles of
 // min(Ncap, window + Nq - 1 + 63) keys — what one workgroup walks at most, tile misalignment included — in place of those of Ncap in the rule of S.
+// A varlen call (lc_attn_varlen_paged_*) is planned as the chunk call of Nq = max_nq — RT, RB, the tiles of a window — on the
+// attn_varlen_*_kernel of its cache kind (all LOCAL = true: no second plan for window = 0 and no sinks), with two differences: the groups of the
+// rule of S are Hkv x min(B RB, ceil(G T / 64) + B), an upper bound of the row blocks that can hold work whatever cu_q says, and the partials
+// are S x T H rows, merged by attn_varlen_combine_kernel<D>.
 struct DecodePlan {
   DecodeCall call;     // what was planned
   DecodeCache cache;
@@ -190,16 +196,20 @@ struct DecodePtrs {
   hipStream_t st;
   const int* block_table;           // paged: device int32[B, max_pages]; else nullptr
   const float *k_scale, *v_scale;   // PAGED_KV8: device float[Hkv] or nullptr = 1.0; else nullptr
-  const float* sinks;               // a local call: device float[H] or nullptr = no sinks; else nullptr
+  const float* sinks;               // a local or varlen call: device float[H] or nullptr = no sinks; else nullptr
+  const int* cu_q = nullptr;        // a varlen call: device int32[B + 1]; else nullptr
 };
 // The checks of the three decode entry points, in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's
 // pointers (nullptr: a query call, which has none)
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p);
 int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p);   // checked arguments; nothing writes into a plan afterwards
+// (varlen: "attn_varlen_paged_kernel<128,1> x8", "attn_varlen_chunk_paged_kv8_kernel<64>")
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel); RB > 1: "attn_chunk_kernel<128> x8"; local: "attn_local_kernel<128,1>", "attn_local_chunk_kernel<128>"
-// bytes of fp32 partials a plan with S > 1 needs: S x B H Nq rows x (D + 1) floats; 0 for S = 1
+// rows of Q and O, and of each of the S partials: B H Nq — varlen: T H
+inline size_t decode_rows(const DecodeCall& c) { return c.varlen ? (size_t)c.T * c.H : (size_t)c.B * c.H * c.Nq; }
+// bytes of fp32 partials a plan with S > 1 needs: S x rows x (D + 1) floats; 0 for S = 1
 inline size_t decode_workspace_bytes(const DecodePlan& p) {
-  return p.S > 1 ? (size_t)p.S * ((size_t)p.call.B * p.call.H * p.call.Nq) * (size_t)(p.call.D + 1) * sizeof(float) : 0;
+  return p.S > 1 ? (size_t)p.S * decode_rows(p.call) * (size_t)(p.call.D + 1) * sizeof(float) : 0;
 }
 int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace);   // tu_attn_decode.hip
 // the S range workgroups of a plan of cache kind C: tu_attn_decode_impl.h, instantiated once per kind in the unit that compiles that kind's kernels
@@ -211,6 +221,11 @@ int launch_attn_chunk_ranges(const DecodePlan& p, int S, const DecodePtrs& a, fl
 // ... and of a local plan, RB = 1 or more: tu_attn_local_impl.h, instantiated in tu_attn_local.hip / _paged.hip / _paged_kv8.hip
 template <DecodeCache C>
 int launch_attn_local_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+// ... and of a varlen plan (PAGED and PAGED_KV8 only): tu_attn_varlen_impl.h, instantiated in tu_attn_varlen_paged.hip / _paged_kv8.hip; its
+// combine launch (attn_varlen_combine_kernel<D>, both kinds): tu_attn_varlen_paged.hip
+template <DecodeCache C>
+int launch_attn_varlen_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+int launch_attn_varlen_combine(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
 
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on
@@ -240,19 +255,27 @@ int launch_kv_append(const AppendCall& c, const AppendPtrs& a);      // tu_kv_ap
 struct RopeAppendCall {
   AppendCall a;
   int H, rot_dim, max_pos;
-  long long src_row_stride;              // elements; 0 unless LC_ROPE_PACKED_SRC
-  int flags;                             // LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC
+  long long src_row_stride;              // elements; 0 unless LC_ROPE_PACKED_SRC (varlen: q_row_stride)
+  int flags;                             // LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC (varlen: LC_ROPE_INTERLEAVED only)
+  // lc_rope_append_varlen_* (DESIGN.md §4.3l): a ragged batch — token-major sources with a row stride each, Qout dense [T,H,D], cu_q[B + 1];
+  // a.Nq = max_nq.  One kernel, rope_append_varlen_kernel<D, INTERLEAVED> or rope_append_varlen_kv8_kernel<D, INTERLEAVED>, on
+  // ceil(T / (2048 / D)) x (Hkv + H) workgroups: the grid is over global token blocks and does not grow with B
+  bool varlen = false;
+  int T = 0, max_nq = 0;
+  long long kv_row_stride = 0;           // elements; Knew and Vnew
 };
 struct RopeAppendPtrs {
   AppendPtrs a;
   const half_t* Q;                       // dense [B,H,Nq,D], or (packed) a token-major projection output, as a.Knew and a.Vnew
   half_t* Qout;                          // dense [B,H,Nq,D]; may be Q itself for a dense source
   const float* cos_sin;                  // device float[max_pos, rot_dim]
+  const int* cu_q = nullptr;             // a varlen call: device int32[B + 1]; else nullptr
 };
 // The checks of the two entry points in the order that decides the status of a doubly-bad call; everything the append call shares is
 // check_kv_append's, so a pool geometry that append accepts is accepted here.  p: the run call's pointers (nullptr: a name call)
 int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p);
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen);   // "rope_append_paged_kernel<128,false>" / "rope_append_paged_kv8_kernel<64,true>"
-int launch_rope_append(const RopeAppendCall& c, const RopeAppendPtrs& p);  // tu_rope_append.hip; checked arguments
+int launch_rope_append(const RopeAppendCall& c, const RopeAppendPtrs& p);  // tu_rope_append.hip; checked arguments; a varlen call: ...
+int launch_rope_append_varlen(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen.hip
 
 }  // namespace lc

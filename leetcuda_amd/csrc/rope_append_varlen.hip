@@ -1,0 +1,109 @@
+// rope_append_varlen.hip — rotary embedding + append for a ragged batch (lc_rope_append_varlen_f16 / _kv8): the write side of
+// the step that attn_varlen.hip reads.  The rule of a token is rope_append_paged.hip's, word for word — rope_rotate8 and kv8_quantize8
+// themselves — and what changes is how a row finds its sequence:
+//   - sources are token-major with a row stride each: element (t, h, d) of Q at Q[t q_row_stride + h D + d], of Knew / Vnew at
+//     ptr[t kv_row_stride + h D + d] (three pointers into one projection output [T, (H + 2 Hkv) D], or dense [T,H,D] / [T,Hkv,D]); Qout is dense
+//     [T,H,D], the layout attn_varlen.hip reads, and may be Q itself when q_row_stride = H D (a row lives in one wave: rope_append_paged.hip)
+//   - the grid is over GLOBAL token blocks: ceil(T / (2048 / D)) x (Hkv + H) workgroups, the K/V ones first.  It does not grow with B x max_nq.
+//     A block may straddle sequences, so b, L_b and the page are per ROW: each row finds the sequence b with cu_q[b] <= t < cu_q[b + 1] by a
+//     binary search of cu_q — at most log2(B + 1) + 1 loads of an array that stays in the caches — and then applies attn_varlen.hip's clamps:
+//     q0 = clamp(cu_q[b], 0, T), Nq_b = clamp(cu_q[b + 1] - q0, 0, min(max_nq, T - q0)), i = t - q0, position p = L_b - Nq_b + i
+//   - a token no sequence owns (t >= cu_q[B], or i outside [0, Nq_b) under the clamps) writes nothing, in the pools or in Qout
+// Only t < T is ever used as a row: no value in cu_q takes a load or a store outside the T rows.
+#pragma once
+#include "rope_append_paged.hip"
+
+namespace lc {
+
+template <int D, bool INTERLEAVED, bool KV8>
+LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew, half_t* Qout,
+                                       void* __restrict__ Kpool, void* __restrict__ Vpool, const float* __restrict__ cos_sin,
+                                       const int* __restrict__ cu_q, const int* __restrict__ block_table, const int* __restrict__ kv_len,
+                                       const float* __restrict__ k_scale, const float* __restrict__ v_scale, int B, int H, int Hkv, int T,
+                                       int max_nq, int num_pages, int lps, int max_pages, int nblk, int rot_dim, int max_pos,
+                                       long long q_row_stride, long long kv_row_stride) {
+  constexpr int LPR = D / 8, TPB = 256 / LPR;   // lanes per row, tokens per workgroup
+  // uniform: the role, the head and the token block of this workgroup
+  const unsigned blk0 = __builtin_amdgcn_workgroup_id_x(), tid = __builtin_amdgcn_workitem_id_x();
+  const unsigned nkv = (unsigned)Hkv * (unsigned)nblk;
+  const bool isq = blk0 >= nkv;                 // the Q workgroups follow the Hkv x nblk K/V workgroups
+  const unsigned blk = isq ? blk0 - nkv : blk0;
+  const unsigned h = blk / (unsigned)nblk, tb = blk - h * (unsigned)nblk;
+  const unsigned r = tid / LPR, c = tid % LPR, t = tb * TPB + r;
+  if (t >= (unsigned)T) return;
+  // the sequence of token t: the first b whose end lies behind t (zero-length sequences are stepped over)
+  int lo = 0, hi = B;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cu_q[mid + 1] <= (int)t) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo >= B) return;                          // t >= cu_q[B]: nobody's token
+  const int b = lo;
+  const int q0 = min(max(cu_q[b], 0), T);
+  const int c1 = cu_q[b + 1];
+  const int nqb = c1 <= q0 ? 0 : min(c1 - q0, min(max_nq, T - q0));
+  const int i = (int)t - q0;
+  if (i < 0 || i >= nqb) return;                // outside the sequence under the clamps (a cu_q that is not monotone, Nq_b > max_nq)
+  const int ncap = max_pages << lps;
+  const int L = min(max(kv_len[b], 0), ncap);
+  const int p = L - nqb + i;
+  const size_t rowq = (size_t)t * (size_t)q_row_stride + (size_t)h * D, rowkv = (size_t)t * (size_t)kv_row_stride + (size_t)h * D;
+  const unsigned cp = rope_partner_chunk<INTERLEAVED>(c, rot_dim);   // the partner chunk of the same row
+  const float* cs = cos_sin + (size_t)min(max(p, 0), max_pos - 1) * (unsigned)rot_dim;   // the row read is clamped: nothing outside the table
+  if (isq) {
+    u32x4_t* dst = reinterpret_cast<u32x4_t*>(Qout + ((size_t)t * (unsigned)H + h) * D + c * 8);
+    if (p < 0) {                                                 // more tokens than keys: no visible key, a defined value
+      *dst = u32x4_t{0u, 0u, 0u, 0u};
+      return;
+    }
+    const u32x4_t q = *reinterpret_cast<const u32x4_t*>(Q + rowq + c * 8);
+    const u32x4_t qp = INTERLEAVED ? q : *reinterpret_cast<const u32x4_t*>(Q + rowq + cp * 8);
+    *dst = rope_rotate8<INTERLEAVED>(q, qp, cs, c, rot_dim);
+    return;
+  }
+  if (p < 0) return;
+  const int pid = block_table[(size_t)b * max_pages + (p >> lps)];   // p < L <= ncap: inside the table row
+  if ((unsigned)pid >= (unsigned)num_pages) return;             // a bad page id drops the token
+  const u32x4_t k = *reinterpret_cast<const u32x4_t*>(Knew + rowkv + c * 8);
+  const u32x4_t kp = INTERLEAVED ? k : *reinterpret_cast<const u32x4_t*>(Knew + rowkv + cp * 8);
+  const u32x4_t v = *reinterpret_cast<const u32x4_t*>(Vnew + rowkv + c * 8);
+  const u32x4_t kr = rope_rotate8<INTERLEAVED>(k, kp, cs, c, rot_dim);
+  const size_t run = ((size_t)pid * (unsigned)Hkv + h) << lps;   // first row of the (page, head) run
+  const unsigned off = (unsigned)(p & ((1 << lps) - 1)) * D + c * 8;   // elements inside the run
+  if constexpr (KV8) {
+    const float ks = k_scale ? k_scale[h] : 1.0f, vs = v_scale ? v_scale[h] : 1.0f;
+    *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Kpool) + run * D + off) = kv8_quantize8(kr, ks);   // the codes of the row ROUNDED to fp16
+    *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Vpool) + run * D + off) = kv8_quantize8(v, vs);
+  } else {
+    *reinterpret_cast<u32x4_t*>(static_cast<half_t*>(Kpool) + run * D + off) = kr;
+    *reinterpret_cast<u32x4_t*>(static_cast<half_t*>(Vpool) + run * D + off) = v;
+  }
+}
+
+// grid: nblk x (Hkv + H) workgroups of 256, nblk = ceil(T / (2048 / D)), the first Hkv x nblk of them K/V; lps = log2(page_size)
+template <int D, bool INTERLEAVED>
+__global__ __launch_bounds__(256) void rope_append_varlen_kernel(const half_t* Q, const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew,
+                                                                 half_t* Qout, half_t* __restrict__ Kpool, half_t* __restrict__ Vpool,
+                                                                 const float* __restrict__ cos_sin, const int* __restrict__ cu_q,
+                                                                 const int* __restrict__ block_table, const int* __restrict__ kv_len, int B, int H,
+                                                                 int Hkv, int T, int max_nq, int num_pages, int lps, int max_pages, int nblk,
+                                                                 int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride) {
+  rope_append_varlen_body<D, INTERLEAVED, false>(Q, Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, B, H, Hkv, T,
+                                                 max_nq, num_pages, lps, max_pages, nblk, rot_dim, max_pos, q_row_stride, kv_row_stride);
+}
+
+template <int D, bool INTERLEAVED>
+__global__ __launch_bounds__(256) void rope_append_varlen_kv8_kernel(const half_t* Q, const half_t* __restrict__ Knew,
+                                                                     const half_t* __restrict__ Vnew, half_t* Qout, uint8_t* __restrict__ Kpool8,
+                                                                     uint8_t* __restrict__ Vpool8, const float* __restrict__ cos_sin,
+                                                                     const int* __restrict__ cu_q, const int* __restrict__ block_table,
+                                                                     const int* __restrict__ kv_len, const float* __restrict__ k_scale,
+                                                                     const float* __restrict__ v_scale, int B, int H, int Hkv, int T, int max_nq,
+                                                                     int num_pages, int lps, int max_pages, int nblk, int rot_dim, int max_pos,
+                                                                     long long q_row_stride, long long kv_row_stride) {
+  rope_append_varlen_body<D, INTERLEAVED, true>(Q, Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, B, H, Hkv, T,
+                                                max_nq, num_pages, lps, max_pages, nblk, rot_dim, max_pos, q_row_stride, kv_row_stride);
+}
+
+}  // namespace lc

@@ -731,7 +731,10 @@ int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
   if (p->S > 0) return LC_OK;
   // (a window: a workgroup walks at most window + Nq - 1 keys and the rest of the tile its lowest one lies in — not kv_len's business either)
   const long walked = c.window > 0 ? std::min((long)p->Ncap, (long)c.window + c.Nq - 1 + 63) : (long)p->Ncap;
-  const long groups = (long)c.B * c.Hkv * p->RB, tiles = (walked + 63) / 64;
+  long groups = (long)c.B * c.Hkv * p->RB;
+  // (varlen: no more row blocks hold work than the T tokens can fill — ceil(G T / 64) full ones and a partial one per sequence — whatever cu_q says)
+  if (c.varlen) groups = c.Hkv * std::min((long)c.B * p->RB, ((long)(c.H / c.Hkv) * c.T + 63) / 64 + c.B);
+  const long tiles = (walked + 63) / 64;
   long S = (rule_cus(k) + groups - 1) / groups;
   S = std::min(S, tiles / 4);
   p->S = (int)std::max(1L, std::min(S, 64L));
@@ -740,9 +743,10 @@ int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
   if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
   if (c.window < 0 || (c.window > 0 && !(c.flags & LC_ATTN_CAUSAL))) return LC_ERR_ARG;   // a window is a lower edge of the causal mask
-  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
+  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)) || (c.varlen && !a->cu_q))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
   if (c.H <= 0 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return LC_ERR_SHAPE;
   if (c.B <= 0 || c.Nq <= 0 || c.D <= 0) return LC_ERR_SHAPE;
+  if (c.varlen && (c.T < 1 || c.max_nq > c.T)) return LC_ERR_SHAPE;   // (Nq IS max_nq: < 1 is refused above)
   long ncap = c.Ncap;
   if (c.paged) {
     if (c.num_pages <= 0 || c.max_pages <= 0) return LC_ERR_SHAPE;
@@ -763,11 +767,13 @@ int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   static const char* const kKernels[] = {"attn_decode_kernel", "attn_decode_paged_kernel", "attn_decode_paged_kv8_kernel"};   // by DecodeCache
   static const char* const kLocal[] = {"attn_local_kernel", "attn_local_paged_kernel", "attn_local_paged_kv8_kernel"};
-  const char* kern = (p.local ? kLocal : kKernels)[(int)p.cache];
+  static const char* const kVarlen[] = {"", "attn_varlen_paged_kernel", "attn_varlen_paged_kv8_kernel"};
+  const char* kern = (p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
   if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
     static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
     static const char* const kLocalChunk[] = {"attn_local_chunk_kernel", "attn_local_chunk_paged_kernel", "attn_local_chunk_paged_kv8_kernel"};
-    const char* chunk = (p.local ? kLocalChunk : kChunk)[(int)p.cache];
+    static const char* const kVarlenChunk[] = {"", "attn_varlen_chunk_paged_kernel", "attn_varlen_chunk_paged_kv8_kernel"};
+    const char* chunk = (p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
     if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", chunk, p.call.D, p.S);
     else snprintf(buf, buflen, "%s<%d>", chunk, p.call.D);
     return;
@@ -800,14 +806,26 @@ void format_kv_append(const AppendCall& c, char* buf, int buflen) {
 
 // Rotary embedding + append (lc_plan.h RopeAppendCall).  Its own ARG checks first, then check_kv_append for everything the two calls share; a
 // head dim append refuses is reported only after every SHAPE check of this call has passed (ARG, SHAPE, HEADDIM: the order of every entry).
+// A varlen call (c.varlen): LC_ROPE_PACKED_SRC is an unknown flag (the two strides say it all), cu_q joins the NULL check, T and max_nq the
+// shape check; the strides are those of token-major rows; the grid is ceil(T / tokens per workgroup) x (Hkv + H).  (check_kv_append sees
+// Nq = max_nq: its grid bound is that of the rectangular call the ragged one replaces.)
 int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p) {
-  if (c.flags & ~(LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC)) return LC_ERR_ARG;
-  if (p && (!p->Q || !p->Qout || !p->cos_sin)) return LC_ERR_ARG;
+  if (c.flags & ~(c.varlen ? LC_ROPE_INTERLEAVED : LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC)) return LC_ERR_ARG;
+  if (p && (!p->Q || !p->Qout || !p->cos_sin || (c.varlen && !p->cu_q))) return LC_ERR_ARG;
   const int rc = check_kv_append(c.a, p ? &p->a : nullptr);
   if (rc != LC_OK && rc != LC_ERR_HEADDIM) return rc;
   const int D = c.a.D;
   if (c.H <= 0 || c.max_pos <= 0 || c.H % c.a.Hkv != 0) return LC_ERR_SHAPE;
   if (c.rot_dim < 16 || c.rot_dim > D || c.rot_dim % 16 != 0) return LC_ERR_SHAPE;   // a NeoX partner is a whole 16-byte chunk away
+  if (c.varlen) {
+    if (c.T < 1 || c.max_nq > c.T) return LC_ERR_SHAPE;
+    if (c.src_row_stride % 8 != 0 || c.src_row_stride < (long long)c.H * D) return LC_ERR_SHAPE;
+    if (c.kv_row_stride % 8 != 0 || c.kv_row_stride < (long long)c.a.Hkv * D) return LC_ERR_SHAPE;
+    if (((size_t)c.T - 1) / kv_append_tokens_per_block(D) + 1 > 0x7fffffffull / ((size_t)c.a.Hkv + (size_t)c.H)) return LC_ERR_SHAPE;
+    if (p && (!aligned16(p->Q) || !aligned16(p->Qout))) return LC_ERR_SHAPE;
+    if (p && p->Q == p->Qout && c.src_row_stride != (long long)c.H * D) return LC_ERR_SHAPE;   // in place: the dense layout only
+    return rc;
+  }
   if (c.flags & LC_ROPE_PACKED_SRC) {
     if (c.src_row_stride % 8 != 0 || c.src_row_stride < ((long long)c.H + 2LL * c.a.Hkv) * D) return LC_ERR_SHAPE;
   } else if (c.src_row_stride != 0) return LC_ERR_SHAPE;
@@ -818,8 +836,9 @@ int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p) {
   return rc;
 }
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen) {
-  snprintf(buf, buflen, c.a.kv_bytes == 1 ? "rope_append_paged_kv8_kernel<%d,%s>" : "rope_append_paged_kernel<%d,%s>", c.a.D,
-           c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
+  const char* fmt = c.a.kv_bytes == 1 ? "rope_append_paged_kv8_kernel<%d,%s>" : "rope_append_paged_kernel<%d,%s>";
+  if (c.varlen) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_kernel<%d,%s>" : "rope_append_varlen_kernel<%d,%s>";
+  snprintf(buf, buflen, fmt, c.a.D, c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
 }
 
 // The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).

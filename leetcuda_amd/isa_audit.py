@@ -61,6 +61,9 @@ OWNED_AGPRS = [
     (re.compile(r"kv_append_paged_kernel|kv_append_paged_kv8_kernel"), []),
     # ... and the rotary-embedding + append kernels (rope_append_paged.hip)
     (re.compile(r"rope_append_paged_kernel|rope_append_paged_kv8_kernel"), []),
+    # ... and the ragged-batch kernels (attn_varlen.hip: the decode body with VARLEN = true; rope_append_varlen.hip)
+    (re.compile(r"attn_varlen_(chunk_)?paged_(kv8_)?kernel|attn_varlen_combine_kernel"), []),
+    (re.compile(r"rope_append_varlen_kernel|rope_append_varlen_kv8_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
 ]
 
