@@ -444,7 +444,10 @@ int lc_attn_decode_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page
  * return the status the run call gives that shape; a NULL buffer or buflen < 8: LC_ERR_ARG.
  * Not here: per-token or per-page scales, pools laid out [P,page_size,Hkv,D], an append to a contiguous cache, ragged Nq per sequence other
  * than by left padding (a ragged batch: lc_rope_append_varlen_* below, which a table of cos = 1, sin = 0 makes a plain append).  (A
- * token-major [B,Nq,Hkv,D] source and rotary embedding: lc_rope_append_paged_* below.) */
+ * token-major [B,Nq,Hkv,D] source and rotary embedding: lc_rope_append_paged_* below.)
+ * bfloat16: for 16-bit pools lc_kv_append_paged_f16 is a copy of bits and serves bf16 rows and pools as it stands (the pools that
+ * lc_attn_varlen_paged_bf16 reads); there is no bf16 form of lc_kv_append_paged_kv8 — lc_rope_append_varlen_kv8_bf16 with a table of cos = 1,
+ * sin = 0 quantises bf16 rows. */
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool,
                            const int* block_table, const int* kv_len,
                            int B, int Hkv, int Nq, int num_pages, int page_size, int max_pages, int D,
@@ -487,8 +490,8 @@ int lc_kv_append_paged_kv8_kernel_name(int B, int Hkv, int Nq, int page_size, in
  * 16-byte aligned; then D not in {64, 128}: LC_ERR_HEADDIM.  Nq is unbounded, there is no workspace.
  * Kernels: rope_append_paged_kernel<D,INTERLEAVED>, rope_append_paged_kv8_kernel<D,INTERLEAVED>.  The name calls never launch, take no
  * num_pages and return the status the run call gives that shape; a NULL buffer or buflen < 8: LC_ERR_ARG.
- * Not here: explicit per-token position ids (tree speculation, M-RoPE), an fp16 / bf16 table or angles computed in the kernel, bf16 sources,
- * RoPE for the contiguous cache, D outside {64, 128}. */
+ * Not here: explicit per-token position ids (tree speculation, M-RoPE), an fp16 / bf16 table or angles computed in the kernel, bf16 sources
+ * (the ragged form has them: lc_rope_append_varlen_bf16 / _kv8_bf16 below), RoPE for the contiguous cache, D outside {64, 128}. */
 #define LC_ROPE_INTERLEAVED 1
 #define LC_ROPE_PACKED_SRC 2
 int lc_rope_append_paged_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
@@ -668,6 +671,55 @@ int lc_rope_append_varlen_kernel_name(int B, int H, int Hkv, int T, int max_nq, 
 int lc_rope_append_varlen_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
                                           int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
                                           char* buf, int buflen);
+
+/* EXTENSION: bfloat16 forms of the four ragged entries above (attn_varlen_bf16.hip, rope_append_varlen_bf16.hip) — what a
+ * model that ships in bfloat16 (Llama 3, Mistral, Gemma 2 / 3, gpt-oss) needs for one serving step: [GEMM -> lc_rope_append_varlen_bf16 ->
+ * lc_attn_varlen_paged_bf16], capturable as one graph like its fp16 twin.  Each entry takes the arguments of its fp16 twin, one for one; every
+ * 16-bit element — Q, O, Knew, Vnew, Qout and 16-bit pools — is read and written as bfloat16.  fp8 pools are the SAME OCP e4m3fn bytes under
+ * the same fp32 per-head scales: a cache written by either element type is read by both.  cos_sin, sinks and the scales stay fp32.
+ * The checks, their order and the statuses are the twin's: the same bad argument gets the same code.  So is the plan — RT, RB, S, the grid, the
+ * LDS size and the workspace: lc_attn_varlen_paged_workspace_bytes / lc_attn_varlen_paged_kv8_workspace_bytes serve both element types (there
+ * is no _bf16 workspace query), and "attn_decode_split" forces S as it does there.  The name calls report that plan with the kernels
+ * attn_varlen_paged_bf16_kernel<D,RT> / attn_varlen_chunk_paged_bf16_kernel<D> / attn_varlen_paged_kv8_bf16_kernel<D,RT> /
+ * attn_varlen_chunk_paged_kv8_bf16_kernel<D> (S > 1: + attn_varlen_combine_bf16_kernel<D>) and rope_append_varlen_bf16_kernel<D,INTERLEAVED> /
+ * rope_append_varlen_kv8_bf16_kernel<D,INTERLEAVED>.
+ * Arithmetic.  Attention: Q K^T and P V on v_mfma_f32_16x16x32_bf16 with fp32 accumulation; P is rounded to bf16 (nearest even) while the
+ * row sum keeps the unrounded fp32 value; the softmax state, the partials and their merge are fp32; O is rounded ONCE, fp32 -> bf16 nearest
+ * even.  An fp8 cache is converted e4m3 -> bf16 in registers, exactly.  RoPE: bf16 -> fp32 (exact), the fp32 arithmetic of the fp16 entry,
+ * ONE rounding to bf16 (nearest even, denormals kept); elements at or behind rot_dim and all of V are copied bit for bit; an fp8 pool gets
+ * the code e4m3fn_rne(clamp(fp32(x) / scale, +-448)) of the rotated row ROUNDED TO bf16 FIRST (what a bf16 pool quantised afterwards would
+ * hold), NaN -> a NaN code, +-inf -> +-448.
+ * A ragged call whose Nq_b all equal max_nq is the rectangular call: the rectangular and contiguous-cache entries have no bf16 form.
+ * Not here: bf16 forms of lc_attn_decode_* / lc_attn_chunk_* / lc_attn_local_* / lc_rope_append_paged_*, D outside {64, 128}, a 16-bit table. */
+int lc_attn_varlen_paged_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O,
+                              const int* cu_q, const int* block_table, const int* kv_len,
+                              int B, int H, int Hkv, int T, int max_nq,
+                              int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                          int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O,
+                                  const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                                  int B, int H, int Hkv, int T, int max_nq,
+                                  int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                              int flags, char* buf, int buflen);
+int lc_rope_append_varlen_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                               const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len,
+                               int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                               int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_kv8_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8,
+                                   const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len,
+                                   const float* k_scale, const float* v_scale,
+                                   int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                                   int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                           int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                           char* buf, int buflen);
+int lc_rope_append_varlen_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                               int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                               char* buf, int buflen);
 
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */

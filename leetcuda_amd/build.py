@@ -34,7 +34,9 @@ AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_a
                     "tu_rope_append": "isa_audit_rope_append.json", "tu_attn_local": "isa_audit_local.json",
                     "tu_attn_local_paged": "isa_audit_local_paged.json", "tu_attn_local_paged_kv8": "isa_audit_local_paged_kv8.json",
                     "tu_attn_varlen_paged": "isa_audit_varlen_paged.json", "tu_attn_varlen_paged_kv8": "isa_audit_varlen_paged_kv8.json",
-                    "tu_rope_append_varlen": "isa_audit_rope_append_varlen.json"}
+                    "tu_rope_append_varlen": "isa_audit_rope_append_varlen.json",
+                    "tu_attn_varlen_paged_bf16": "isa_audit_varlen_paged_bf16.json", "tu_attn_varlen_paged_kv8_bf16": "isa_audit_varlen_paged_kv8_bf16.json",
+                    "tu_rope_append_varlen_bf16": "isa_audit_rope_append_varlen_bf16.json"}
 
 
 def _newer(target: Path, sources) -> bool:

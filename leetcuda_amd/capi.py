@@ -98,6 +98,15 @@ SYMBOLS = {
     "lc_rope_append_varlen_kv8": (_i, [_vp] * 12 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
     "lc_rope_append_varlen_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
     "lc_rope_append_varlen_kv8_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    # the bfloat16 ragged entries: argument for argument their fp16 twins (the workspace queries above serve both)
+    "lc_attn_varlen_paged_bf16": (_i, [_vp] * 7 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_kv8_bf16": (_i, [_vp] * 9 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_kv8_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_rope_append_varlen_bf16": (_i, [_vp] * 10 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_kv8_bf16": (_i, [_vp] * 12 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_bf16_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_varlen_kv8_bf16_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -1026,18 +1035,21 @@ def _row_stride(t, what):
     return stride
 
 
-def _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale=None, v_scale=None, kv8=False):
-    """The dtype and shape checks of rope_append_varlen / _kv8 (no GPU needed): fp16 q [T,H,D], k_new, v_new [T,Hkv,D] — dense, or views with one
-    row stride each (k_new and v_new share theirs) —, pools [num_pages,Hkv,page_size,D], float32 cos_sin [max_pos, rot_dim], q_out (if given)
-    fp16 [T,H,D].  Returns (B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride)."""
+def _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale=None, v_scale=None, kv8=False,
+                      bf16=False):
+    """The dtype and shape checks of rope_append_varlen / _kv8 and their _bf16 twins (no GPU needed): fp16 (bf16: bfloat16) q [T,H,D], k_new,
+    v_new [T,Hkv,D] — dense, or views with one row stride each (k_new and v_new share theirs) —, pools [num_pages,Hkv,page_size,D], float32
+    cos_sin [max_pos, rot_dim], q_out (if given) of q's type [T,H,D].  Returns (B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D,
+    rot_dim, max_pos, q_row_stride, kv_row_stride)."""
     import torch
-    if q.dtype != torch.half or k_new.dtype != torch.half or v_new.dtype != torch.half:
-        raise TypeError(f"q / k_new / v_new must be float16, got {q.dtype} / {k_new.dtype} / {v_new.dtype}")
-    pool_types = (torch.float8_e4m3fn, torch.uint8) if kv8 else (torch.half,)
+    elem, ename = (torch.bfloat16, "bfloat16") if bf16 else (torch.half, "float16")
+    if q.dtype != elem or k_new.dtype != elem or v_new.dtype != elem:
+        raise TypeError(f"q / k_new / v_new must be {ename}, got {q.dtype} / {k_new.dtype} / {v_new.dtype}")
+    pool_types = (torch.float8_e4m3fn, torch.uint8) if kv8 else (elem,)
     if k_pool.dtype not in pool_types or v_pool.dtype not in pool_types:
         raise TypeError(f"k_pool / v_pool must be {' or '.join(str(t) for t in pool_types)}, got {k_pool.dtype} / {v_pool.dtype}")
-    if q_out is not None and q_out.dtype != torch.half:
-        raise TypeError(f"q_out must be float16, got {q_out.dtype}")
+    if q_out is not None and q_out.dtype != elem:
+        raise TypeError(f"q_out must be {ename}, got {q_out.dtype}")
     if cos_sin.dtype != torch.float32:
         raise TypeError(f"cos_sin must be float32, got {cos_sin.dtype}")
     if q.dim() != 3 or k_new.dim() != 3 or k_pool.dim() != 4:
@@ -1072,17 +1084,21 @@ def _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_tabl
     return B, H, Hkv, T, max_nq, k_pool.shape[0], k_pool.shape[2], block_table.shape[1], D, cos_sin.shape[1], cos_sin.shape[0], qs, ks
 
 
-def _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, kv8):
+def _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, kv8,
+                        bf16=False):
     import torch
-    args = _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale, v_scale, kv8)
+    args = _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale, v_scale, kv8, bf16)
     for t in (q, k_new, v_new):      # (views into a projection output are not contiguous: the kernel strides)
         if not t.is_cuda:
             raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
     if q_out is None:
-        q_out = torch.empty((args[3], args[1], args[8]), dtype=torch.half, device=q.device)
+        q_out = torch.empty((args[3], args[1], args[8]), dtype=q.dtype, device=q.device)
     _need_gpu(q_out, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
     scale_ptrs = [_ptr(s) if s is not None else None for s in (k_scale, v_scale)] if kv8 else []
-    symbol = "lc_rope_append_varlen_kv8" if kv8 else "lc_rope_append_varlen_f16"
+    if bf16:
+        symbol = "lc_rope_append_varlen_kv8_bf16" if kv8 else "lc_rope_append_varlen_bf16"
+    else:
+        symbol = "lc_rope_append_varlen_kv8" if kv8 else "lc_rope_append_varlen_f16"
     check(getattr(load(), symbol)(_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(q_out), _ptr(k_pool), _ptr(v_pool), _ptr(cos_sin), _ptr(cu_q),
                                   _ptr(block_table), _ptr(kv_len), *scale_ptrs, *args, ROPE_INTERLEAVED if interleaved else 0, _stream()), symbol)
     return q_out
@@ -1107,6 +1123,83 @@ def rope_append_varlen_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D
                                    kv_row_stride=None) -> str:
     """"rope_append_varlen_kernel<D,INTERLEAVED>" / "rope_append_varlen_kv8_kernel<D,INTERLEAVED>" (strides None: dense)."""
     symbol = "lc_rope_append_varlen_kv8_kernel_name" if kv8 else "lc_rope_append_varlen_kernel_name"
+    buf = C.create_string_buffer(128)
+    check(getattr(load(), symbol)(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, H * D if q_row_stride is None else q_row_stride,
+                                  Hkv * D if kv_row_stride is None else kv_row_stride, ROPE_INTERLEAVED if interleaved else 0, buf, 128), symbol)
+    return buf.value.decode()
+
+
+# The bfloat16 twins of the four ragged calls (lc_attn_varlen_paged_bf16 / _kv8_bf16, lc_rope_append_varlen_bf16 / _kv8_bf16; DESIGN.md section
+# 4.3m): the same shape checks through the same helpers, torch.bfloat16 wherever the twin wants torch.half.  The fp8 pools, the float32 scales,
+# sinks and cos_sin table, the workspace and its size (attn_varlen_paged_workspace_bytes) are the twins'.  For bf16 pools the plain append is
+# kv_append_paged on the pools' bits: a 16-bit row is copied, whatever it encodes.
+
+def attn_varlen_paged_bf16(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, causal=False, window=0, sinks=None, workspace=None):
+    """attn_varlen_paged with bfloat16 q, o [T,H,D] and bfloat16 pools (lc_attn_varlen_paged_bf16): every other argument, the clamps and the
+    plan are attn_varlen_paged's."""
+    import torch
+    if q.dtype != torch.bfloat16 or o.dtype != torch.bfloat16 or k_pool.dtype != torch.bfloat16 or v_pool.dtype != torch.bfloat16:
+        raise TypeError(f"q / o / k_pool / v_pool must be bfloat16, got {q.dtype} / {o.dtype} / {k_pool.dtype} / {v_pool.dtype}")
+    dims = _varlen_dims(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq)
+    local = _varlen_local(q, window, sinks)
+    _need_gpu(q, k_pool, v_pool, o, cu_q, block_table, kv_len)
+    check(load().lc_attn_varlen_paged_bf16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *dims,
+                                           *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
+          "lc_attn_varlen_paged_bf16")
+    return o
+
+
+def attn_varlen_paged_kv8_bf16(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, k_scale=None, v_scale=None, causal=False, window=0,
+                               sinks=None, workspace=None):
+    """attn_varlen_paged_kv8 with bfloat16 q, o (lc_attn_varlen_paged_kv8_bf16): the pools are the same e4m3 bytes under the same float32
+    scales — a cache written by either element type is read by both."""
+    import torch
+    fp8 = (torch.float8_e4m3fn, torch.uint8)
+    if q.dtype != torch.bfloat16 or o.dtype != torch.bfloat16:
+        raise TypeError(f"q / o must be bfloat16, got {q.dtype} / {o.dtype}")
+    if k_pool8.dtype not in fp8 or v_pool8.dtype not in fp8:
+        raise TypeError(f"k_pool8 / v_pool8 must be float8_e4m3fn or uint8, got {k_pool8.dtype} / {v_pool8.dtype}")
+    dims = _varlen_dims(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq)
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            continue
+        if s.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {s.dtype}")
+        if tuple(s.shape) != (dims[2],):
+            _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
+    local = _varlen_local(q, window, sinks)
+    _need_gpu(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    check(load().lc_attn_varlen_paged_kv8_bf16(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len),
+                                               _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
+                                               *dims, *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
+          "lc_attn_varlen_paged_kv8_bf16")
+    return o
+
+
+def attn_varlen_paged_bf16_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=False, window=0, kv8=False) -> str:
+    """attn_varlen_paged_kernel_name's plan with the bf16 kernel in it: "attn_varlen_paged_bf16_kernel<D,RT>" / "attn_varlen_chunk_paged_bf16_kernel<D>"
+    (kv8: "..._paged_kv8_bf16_kernel"), + " xS" with S > 1."""
+    symbol = "lc_attn_varlen_paged_kv8_bf16_kernel_name" if kv8 else "lc_attn_varlen_paged_bf16_kernel_name"
+    return _decode_kernel_name(symbol, B, H, Hkv, T, max_nq, page_size, max_pages, D, window, causal=causal)
+
+
+def rope_append_varlen_bf16(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out=None, interleaved=False):
+    """rope_append_varlen with bfloat16 sources, pools and q_out (lc_rope_append_varlen_bf16); cos_sin stays float32.  Returns q_out [T,H,D]
+    bfloat16, what attn_varlen_paged_bf16 reads."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, None, None, False, True)
+
+
+def rope_append_varlen_kv8_bf16(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, block_table, kv_len, max_nq, q_out=None, interleaved=False,
+                                k_scale=None, v_scale=None):
+    """rope_append_varlen_bf16 into fp8 pools (lc_rope_append_varlen_kv8_bf16): the codes of the rotated row rounded to bfloat16 first."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, True,
+                               True)
+
+
+def rope_append_varlen_bf16_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, interleaved=False, kv8=False,
+                                        q_row_stride=None, kv_row_stride=None) -> str:
+    """"rope_append_varlen_bf16_kernel<D,INTERLEAVED>" / "rope_append_varlen_kv8_bf16_kernel<D,INTERLEAVED>" (strides None: dense)."""
+    symbol = "lc_rope_append_varlen_kv8_bf16_kernel_name" if kv8 else "lc_rope_append_varlen_bf16_kernel_name"
     buf = C.create_string_buffer(128)
     check(getattr(load(), symbol)(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, H * D if q_row_stride is None else q_row_stride,
                                   Hkv * D if kv_row_stride is None else kv_row_stride, ROPE_INTERLEAVED if interleaved else 0, buf, 128), symbol)

@@ -30,6 +30,7 @@ __global__ __launch_bounds__(256) void attn_chunk_kernel(const half_t* __restric
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -52,6 +53,7 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kernel(const half_t* __r
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -76,6 +78,7 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kv8_kernel(const half_t*
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }

@@ -87,6 +87,29 @@ LC_DEVINL u32x4_t kv8_half8(uint32_t a, uint32_t b) {
                  __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(b, 1.0f, true))};
 }
 
+// ... and as eight bf16 values (v_cvt_scalef32_pk_bf16_fp8, scale 1.0): exact as well — an e4m3 value has 4 significand bits and an exponent
+// far inside bf16's range
+LC_DEVINL u32x4_t kv8_bf16x8(uint32_t a, uint32_t b) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(a, 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b, 1.0f, true))};
+}
+// The element flavour of the shared body (attn_decode_body.inc, `BF16`): the e4m3 -> 16-bit conversion and the 16 x 16 x 32 MFMA on raw
+// 16-bit fragments, on the model of lc_common.h's mfma32_16 / cvt16.  BF16 = false: kv8_half8 and mfma16 themselves.
+template <bool BF16>
+LC_DEVINL u32x4_t kv8_16x8(uint32_t a, uint32_t b) {
+  if constexpr (BF16) return kv8_bf16x8(a, b);
+  else return kv8_half8(a, b);
+}
+template <bool BF16>
+LC_DEVINL f32x4_t mfma16_16(half8_t a, half8_t b, f32x4_t c) {
+  if constexpr (BF16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+  else
+    return mfma16(a, b, c);
+}
+
 template <int D, int RT>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restrict__ Q, const half_t* __restrict__ K, const half_t* __restrict__ V,
                                                           half_t* __restrict__ O, const int* __restrict__ kv_len, float* __restrict__ part_o,
@@ -100,6 +123,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
   constexpr bool KV8 = false;
   const DecodeKv8 kv8{};
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }

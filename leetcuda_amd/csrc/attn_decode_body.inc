@@ -20,6 +20,11 @@
 // other use is the workgroup-uniform `Nqb` = Nq_b.  The row order inside a (sequence, K / V head) stays r = g Nq_b + i: only the ADDRESS of a row
 // changes, global row (q0 + r % Nq_b) H + kvh G + r / Nq_b in place of row0 + r.  A workgroup whose row block starts at or past R_b returns in
 // front of the first LDS access and barrier.  With VARLEN = false Nqb IS Nq: the 36 other kernels' code does not depend on the parameter.
+// A `constexpr bool BF16` closes the list.  BF16 = true (the attn_varlen_*_bf16_kernel of attn_varlen_bf16.hip; DESIGN.md §4.3m): the 16-bit lanes
+// of Q, O and a 16-bit cache are bfloat16.  Four places read them as numbers and only those change: the two MFMA sites (mfma16_16<BF16>), the
+// rounding of P and of O (cvt16<BF16>, RNE), and the e4m3 -> 16-bit conversion of an fp8 cache (kv8_16x8<BF16>).  Loads, LDS images, transposed
+// reads, masks, (m, l) and the partials do not know the element type.  With BF16 = false the three helpers ARE mfma16, (half_t)x and kv8_half8:
+// every fp16 kernel's code is what it was without the parameter (§4.3m compares it).
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -232,8 +237,8 @@
     for (int n = 0; n < VLR; ++n) {
       const int c = n * 64 + lane;
       if constexpr (KV8) {   // one e4m3 chunk is the two adjacent fp16 chunks 2 (c % CHV), + 1 of its row: the image is the fp16 kernels'
-        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CHV, 2 * (c % CHV))) = kv8_half8(vf[n][0], vf[n][1]);
-        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CHV, 2 * (c % CHV) + 1)) = kv8_half8(vf[n][2], vf[n][3]);
+        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CHV, 2 * (c % CHV))) = kv8_16x8<BF16>(vf[n][0], vf[n][1]);
+        *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CHV, 2 * (c % CHV) + 1)) = kv8_16x8<BF16>(vf[n][2], vf[n][3]);
       } else {
         *reinterpret_cast<u32x4_t*>(vimg + dec_v_off<D>(c / CH, c % CH)) = vf[n];
       }
@@ -241,7 +246,7 @@
   };
   // the A operand of k-step s of 16-key block kb
   auto k_frag = [&](int kb, int s) {
-    if constexpr (KV8) return __builtin_bit_cast(half8_t, kv8_half8(kf[kb][s >> 1][2 * (s & 1)], kf[kb][s >> 1][2 * (s & 1) + 1]));
+    if constexpr (KV8) return __builtin_bit_cast(half8_t, kv8_16x8<BF16>(kf[kb][s >> 1][2 * (s & 1)], kf[kb][s >> 1][2 * (s & 1) + 1]));
     else return __builtin_bit_cast(half8_t, kf[kb][s]);
   };
   // KV8: the scales of this K / V head, fp32 only: k_scale goes once into the score scale, v_scale into the normalisation of O
@@ -262,7 +267,7 @@
   }
   for (int u = 0; u < steps; ++u) {
     // ---- Sᵀ = K Qᵀ for this tile (the K registers are free behind it)
-    // and the online softmax (log2 domain) of each row tile right behind its scores: Sᵀ -> P in fp16, register for register the B operand of
+    // and the online softmax (log2 domain) of each row tile right behind its scores: Sᵀ -> P in fp16 (BF16: bf16), register for register the B operand of
     // Oᵀ += Vᵀ Pᵀ (16 score registers per lane alive at a time, not 16 RT)
     const int k0 = key0(u) + 4 * h;
     half8_t pf[RT][NPS];
@@ -278,7 +283,7 @@
       for (int kb = 0; kb < NKB; ++kb) {
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < KS; ++s) acc = mfma16(k_frag(kb, s), qf[s], acc);
+        for (int s = 0; s < KS; ++s) acc = mfma16_16<BF16>(k_frag(kb, s), qf[s], acc);
         st[kb] = acc;
       }
       float mx = DEC_NEG_INF;
@@ -306,7 +311,7 @@
         for (int r = 0; r < 4; ++r) {
           const float p = __builtin_amdgcn_exp2f(st[kb][r] - mu);
           ps += p;
-          pf[rt][kb >> 1][4 * (kb & 1) + r] = (half_t)p;
+          pf[rt][kb >> 1][4 * (kb & 1) + r] = cvt16<BF16>(p);
         }
       l[rt] = l[rt] * alpha[rt] + ps;   // (this lane's keys of the step: the four lane groups of a row are summed once, behind the loop)
     }
@@ -338,7 +343,7 @@
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int s = 0; s < NPS; ++s) o[rt][db] = mfma16(va[s], pf[rt][s], o[rt][db]);
+        for (int s = 0; s < NPS; ++s) o[rt][db] = mfma16_16<BF16>(va[s], pf[rt][s], o[rt][db]);
     }
     if (more) store_v();   // (LDS operations of one wave execute in order: the transposed reads above are behind us)
   }
@@ -397,7 +402,7 @@
   if (w != 0) return;
   add(0);
 
-  // ---- wave 0 writes: fp16 O (S == 1) or the normalised fp32 partial + the row's log2-domain log-sum-exp
+  // ---- wave 0 writes: fp16 (BF16: bf16) O (S == 1) or the normalised fp32 partial + the row's log2-domain log-sum-exp
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int r = rbase + 16 * rt + i16;
@@ -410,7 +415,7 @@
 #pragma unroll
       for (int db = 0; db < DB; ++db) {
         const f32x4_t x = o[rt][db] * inv;
-        half4_t y = {(half_t)x[0], (half_t)x[1], (half_t)x[2], (half_t)x[3]};
+        half4_t y = {cvt16<BF16>(x[0]), cvt16<BF16>(x[1]), cvt16<BF16>(x[2]), cvt16<BF16>(x[3])};
         *reinterpret_cast<half4_t*>(O + row * D + 16 * db + 4 * h) = y;
       }
     } else {

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const half_t* __
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }

@@ -38,6 +38,7 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kv8_kernel(const half_t
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }

@@ -30,6 +30,7 @@ __global__ __launch_bounds__(256) void attn_local_kernel(const half_t* __restric
   const DecodeKv8 kv8{};
   const DecodeLocal lc{window, sinks};
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(256) void attn_local_chunk_kernel(const half_t* __r
   const DecodeKv8 kv8{};
   const DecodeLocal lc{window, sinks};
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(256) void attn_local_paged_kernel(const half_t* __r
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -93,6 +96,7 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kernel(const half_
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -117,6 +121,7 @@ __global__ __launch_bounds__(256) void attn_local_paged_kv8_kernel(const half_t*
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }
@@ -141,6 +146,7 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kv8_kernel(const h
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool VARLEN = false;
+  constexpr bool BF16 = false;
   const DecodeVarlen vl{};
 #include "attn_decode_body.inc"
 }

@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kernel(const half_t* __
   constexpr bool PAGED = true;
   constexpr bool KV8 = false;
   constexpr bool VARLEN = true;
+  constexpr bool BF16 = false;
   const DecodeKv8 kv8{};
   const DecodePaging pg{block_table, num_pages, lps, max_pages};
   const DecodeLocal lc{window, sinks};
@@ -55,6 +56,7 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kernel(const half
   constexpr bool PAGED = true;
   constexpr bool KV8 = false;
   constexpr bool VARLEN = true;
+  constexpr bool BF16 = false;
   const DecodeKv8 kv8{};
   const DecodePaging pg{block_table, num_pages, lps, max_pages};
   const DecodeLocal lc{window, sinks};
@@ -78,6 +80,7 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_kernel(const half_t
   constexpr bool PAGED = true;
   constexpr bool KV8 = true;
   constexpr bool VARLEN = true;
+  constexpr bool BF16 = false;
   const DecodePaging pg{block_table, num_pages, lps, max_pages};
   const DecodeKv8 kv8{k_scale, v_scale};
   const DecodeLocal lc{window, sinks};
@@ -104,6 +107,7 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_kernel(const 
   constexpr bool PAGED = true;
   constexpr bool KV8 = true;
   constexpr bool VARLEN = true;
+  constexpr bool BF16 = false;
   const DecodePaging pg{block_table, num_pages, lps, max_pages};
   const DecodeKv8 kv8{k_scale, v_scale};
   const DecodeLocal lc{window, sinks};

@@ -52,6 +52,42 @@ LC_DEVINL u32x2_t kv8_quantize8(u32x4_t raw, float s) {
   return out;
 }
 
+// The bfloat16 flavours of the two functions above (rope_append_varlen_bf16.hip): a bf16 element IS the upper half of its fp32
+// value, so the decode is a shift; the quotient, the clamp, the conversion and the NaN rule are the same, the NaN test on the bf16 bits
+LC_DEVINL bool nan_bits_bf16(uint32_t h) { return (h & 0x7fffu) > 0x7f80u; }
+LC_DEVINL float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }           // element 0 of a dword of two bf16
+LC_DEVINL float bf16_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }   // element 1
+// two fp32 -> one dword of two bf16 (RNE), element 0 in the low half
+LC_DEVINL uint32_t bf16_pack2(float lo, float hi) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  const bf16x2_t v = {(__bf16)lo, (__bf16)hi};
+  return __builtin_bit_cast(uint32_t, v);
+}
+
+// kv8_quot2 for the two bf16 of one dword
+LC_DEVINL void kv8_quot2_bf16(uint32_t w, float s, float& lo, float& hi, uint32_t& nan) {
+  const float ql = bf16_lo(w) / s, qh = bf16_hi(w) / s;
+  nan = ((nan_bits_bf16(w) || nan_bits32(ql)) ? 0x7fu : 0u) | ((nan_bits_bf16(w >> 16) || nan_bits32(qh)) ? 0x7f00u : 0u);
+  lo = __builtin_amdgcn_fmed3f(ql, -448.0f, 448.0f);
+  hi = __builtin_amdgcn_fmed3f(qh, -448.0f, 448.0f);
+}
+
+// 8 bf16 (one 16-byte chunk) -> 8 e4m3fn bytes under scale s
+LC_DEVINL u32x2_t kv8_quantize8_bf16(u32x4_t raw, float s) {
+  u32x2_t out;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float a, b, c, d;
+    uint32_t n0, n1;
+    kv8_quot2_bf16(raw[2 * j], s, a, b, n0);
+    kv8_quot2_bf16(raw[2 * j + 1], s, c, d, n1);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);   // bytes 0, 1
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);        // bytes 2, 3
+    out[j] = (uint32_t)w | n0 | (n1 << 16);
+  }
+  return out;
+}
+
 template <int D, bool KV8>
 LC_DEVINL void kv_append_paged_body(const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew, void* __restrict__ Kpool, void* __restrict__ Vpool,
                                     const int* __restrict__ block_table, const int* __restrict__ kv_len, const float* __restrict__ k_scale,

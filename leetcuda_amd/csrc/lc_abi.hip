@@ -86,10 +86,12 @@ DecodeCall decode_local(DecodeCall c, int window, const float* sinks = nullptr) 
   return c;
 }
 // the lc_attn_varlen_paged_* entries: the paged local call of Nq = max_nq on T token-major rows
-DecodeCall decode_varlen(DecodeCall c, int T) {
+// bf16: the lc_attn_varlen_paged_*bf16 entries — the same call on bfloat16 elements
+DecodeCall decode_varlen(DecodeCall c, int T, bool bf16 = false) {
   c.varlen = true;
   c.T = T;
   c.max_nq = c.Nq;
+  c.bf16 = bf16;
   return c;
 }
 // block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local or varlen call, or nullptr; cu_q: a varlen call
@@ -148,12 +150,13 @@ int rope_run(const RopeAppendCall& c, const void* Q, const void* Knew, const voi
 }
 // the lc_rope_append_varlen_* entries: the rope call of Nq = max_nq on T token-major rows with a stride each
 RopeAppendCall rope_varlen_call(int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
-                                long long q_row_stride, long long kv_row_stride, int flags, int kv_bytes) {
+                                long long q_row_stride, long long kv_row_stride, int flags, int kv_bytes, bool bf16 = false) {
   RopeAppendCall c = rope_call(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, flags, kv_bytes);
   c.varlen = true;
   c.T = T;
   c.max_nq = max_nq;
   c.kv_row_stride = kv_row_stride;
+  c.bf16 = bf16;   // the lc_rope_append_varlen_*bf16 entries
   return c;
 }
 int rope_varlen_run(const RopeAppendCall& c, const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
@@ -164,7 +167,7 @@ int rope_varlen_run(const RopeAppendCall& c, const void* Q, const void* Knew, co
                          static_cast<const half_t*>(Q), static_cast<half_t*>(Qout), cos_sin, cu_q};
   if (int rc = check_rope_append(c, &p)) return rc;
   if (int rc = launch_guard()) return rc;
-  return launch_rope_append_varlen(c, p);
+  return c.bf16 ? launch_rope_append_varlen_bf16(c, p) : launch_rope_append_varlen(c, p);
 }
 int rope_name(const RopeAppendCall& c, char* buf, int buflen) {
   if (!buf || buflen < 8) return LC_ERR_ARG;
@@ -530,6 +533,35 @@ int lc_attn_varlen_paged_kv8_kernel_name(int B, int H, int Hkv, int T, int max_n
   return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T), buf, buflen);
 }
 
+// The bfloat16 varlen entries: the two entries above, argument for argument, as a DecodeCall with bf16 = true.  The checks,
+// the plan and the workspace bytes are the fp16 call's (lc_attn_varlen_paged_workspace_bytes / _kv8_workspace_bytes serve both)
+int lc_attn_varlen_paged_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* cu_q, const int* block_table, const int* kv_len,
+                              int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+                              const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, true),
+                    Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q);
+}
+
+int lc_attn_varlen_paged_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags,
+                                          char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* cu_q, const int* block_table,
+                                  const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq,
+                                  int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, true),
+                    Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q);
+}
+
+int lc_attn_varlen_paged_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags,
+                                              char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true), buf,
+                     buflen);
+}
+
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,
                            int Nq, int num_pages, int page_size, int max_pages, int D, int flags, void* stream) {
   return append_run(AppendCall{B, Hkv, Nq, D, flags, 2, num_pages, page_size, max_pages}, Knew, Vnew, Kpool, Vpool, block_table, kv_len, nullptr, nullptr,
@@ -603,6 +635,37 @@ int lc_rope_append_varlen_kernel_name(int B, int H, int Hkv, int T, int max_nq, 
 int lc_rope_append_varlen_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                           long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
   return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1), buf, buflen);
+}
+
+// the bfloat16 twins: the same RopeAppendCall with bf16 = true
+int lc_rope_append_varlen_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool, const float* cos_sin,
+                               const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages,
+                               int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride,
+                               int flags, void* stream) {
+  return rope_varlen_run(
+      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true), Q, Knew,
+      Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream);
+}
+
+int lc_rope_append_varlen_kv8_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8, const float* cos_sin,
+                                   const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B,
+                                   int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                   long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
+  return rope_varlen_run(
+      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true), Q, Knew,
+      Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream);
+}
+
+int lc_rope_append_varlen_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                           long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true), buf,
+                   buflen);
+}
+
+int lc_rope_append_varlen_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                               long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true), buf,
+                   buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

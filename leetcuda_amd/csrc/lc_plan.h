@@ -161,6 +161,8 @@ struct DecodeCall {
   bool sinks = false;                    // lc_attn_local_*: the call has a sink logit per query head (the query calls: never)
   bool varlen = false;                   // lc_attn_varlen_paged_*: a ragged batch — Q, O token-major [T,H,D], cu_q[B + 1]; Nq = max_nq, chunk = true
   int T = 0, max_nq = 0;                 // varlen only: the rows of Q and O, and the host's bound on every Nq_b
+  bool bf16 = false;                     // lc_attn_varlen_paged_*bf16: Q, O and a 16-bit cache are bfloat16 (varlen only).  It picks the
+                                         // kernels (and their names) and nothing else: every check and RT, RB, S, grid, LDS, workspace are the fp16 call's
 };
 enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
 // ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
@@ -189,7 +191,7 @@ struct DecodePlan {
   bool local;          // window > 0 or sinks: the kernels of attn_local.hip
 };
 struct DecodePtrs {
-  const half_t* Q;
+  const half_t* Q;     // (16-bit lanes: a bf16 plan's kernels read and write them as bfloat16 — O, the sources of the rope call and Qout too)
   const void *K, *V;   // the cache or the pools; each unit casts once to the element type of its own kernel
   half_t* O;
   const int* kv_len;   // device int32[B]; FLAT: or nullptr
@@ -203,7 +205,7 @@ struct DecodePtrs {
 // pointers (nullptr: a query call, which has none)
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p);
 int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p);   // checked arguments; nothing writes into a plan afterwards
-// (varlen: "attn_varlen_paged_kernel<128,1> x8", "attn_varlen_chunk_paged_kv8_kernel<64>")
+// (varlen: "attn_varlen_paged_kernel<128,1> x8", "attn_varlen_chunk_paged_kv8_kernel<64>"; bf16: "attn_varlen_paged_bf16_kernel<128,1> x8")
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen);   // "attn_decode_kernel<128,1> x8" (" xS": S > 1, + the combine kernel); RB > 1: "attn_chunk_kernel<128> x8"; local: "attn_local_kernel<128,1>", "attn_local_chunk_kernel<128>"
 // rows of Q and O, and of each of the S partials: B H Nq — varlen: T H
 inline size_t decode_rows(const DecodeCall& c) { return c.varlen ? (size_t)c.T * c.H : (size_t)c.B * c.H * c.Nq; }
@@ -226,6 +228,11 @@ int launch_attn_local_ranges(const DecodePlan& p, int S, const DecodePtrs& a, fl
 template <DecodeCache C>
 int launch_attn_varlen_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 int launch_attn_varlen_combine(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
+// ... and of a varlen plan with bf16 elements (DecodeCall::bf16): the same launcher on the attn_varlen_*_bf16_kernel, instantiated in
+// tu_attn_varlen_paged_bf16.hip / _paged_kv8_bf16.hip; its combine launch (attn_varlen_combine_bf16_kernel<D>): tu_attn_varlen_paged_bf16.hip
+template <DecodeCache C>
+int launch_attn_varlen_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+int launch_attn_varlen_combine_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
 
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on
@@ -263,6 +270,8 @@ struct RopeAppendCall {
   bool varlen = false;
   int T = 0, max_nq = 0;
   long long kv_row_stride = 0;           // elements; Knew and Vnew
+  bool bf16 = false;                     // lc_rope_append_varlen_*bf16: sources, Qout and 16-bit pools are bfloat16 (varlen only); it
+                                         // picks rope_append_varlen_bf16_kernel / _kv8_bf16_kernel and nothing else
 };
 struct RopeAppendPtrs {
   AppendPtrs a;
@@ -276,6 +285,7 @@ struct RopeAppendPtrs {
 int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p);
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen);   // "rope_append_paged_kernel<128,false>" / "rope_append_paged_kv8_kernel<64,true>"
 int launch_rope_append(const RopeAppendCall& c, const RopeAppendPtrs& p);  // tu_rope_append.hip; checked arguments; a varlen call: ...
-int launch_rope_append_varlen(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen.hip
+int launch_rope_append_varlen(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen.hip; with bf16 elements: ...
+int launch_rope_append_varlen_bf16(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen_bf16.hip
 
 }  // namespace lc

@@ -72,6 +72,36 @@ LC_DEVINL u32x4_t rope_rotate8(u32x4_t own, u32x4_t other, const float* __restri
   return rot ? __builtin_bit_cast(u32x4_t, out) : own;
 }
 
+// rope_rotate8 on a chunk of 8 bf16: the same table indices, the same rope_fma, one rounding to bf16
+template <bool INTERLEAVED>
+LC_DEVINL u32x4_t rope_rotate8_bf16(u32x4_t own, u32x4_t other, const float* __restrict__ cs, unsigned c, int rot_dim) {
+  const unsigned rc = (unsigned)rot_dim >> 3, half = (unsigned)rot_dim >> 1;
+  const bool rot = c < rc;
+  u32x4_t out;
+  if constexpr (INTERLEAVED) {
+    const unsigned j = rot ? c * 4 : 0;                 // pairs 4c .. 4c + 3: one dword each
+    const f32x4_t co = rope_table4(cs + j), si = rope_table4(cs + half + j);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x1 = bf16_lo(own[e]), x2 = bf16_hi(own[e]);
+      out[e] = bf16_pack2(rope_fma(x1, co[e], x2, -si[e]), rope_fma(x2, co[e], x1, si[e]));
+    }
+  } else {
+    const unsigned hc = rc >> 1;
+    const bool second = c >= hc;                        // the lane holds x2 of pairs 8 (c - hc) ..: x2' = x2 c + x1 s
+    const unsigned j = rot ? (second ? c - hc : c) * 8 : 0;
+    const f32x4_t c0 = rope_table4(cs + j), c1 = rope_table4(cs + j + 4), s0 = rope_table4(cs + half + j), s1 = rope_table4(cs + half + j + 4);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {                       // dword d: elements 2d, 2d + 1
+      const float cl = d < 2 ? c0[2 * d] : c1[2 * d - 4], ch = d < 2 ? c0[2 * d + 1] : c1[2 * d - 3];
+      const float sl = d < 2 ? s0[2 * d] : s1[2 * d - 4], sh = d < 2 ? s0[2 * d + 1] : s1[2 * d - 3];
+      out[d] = bf16_pack2(rope_fma(bf16_lo(own[d]), cl, bf16_lo(other[d]), second ? sl : -sl),
+                          rope_fma(bf16_hi(own[d]), ch, bf16_hi(other[d]), second ? sh : -sh));
+    }
+  }
+  return rot ? out : own;
+}
+
 // the chunk a NeoX lane needs besides its own: rot_dim / 16 chunks up or down inside the rotated part, itself behind it
 template <bool INTERLEAVED>
 LC_DEVINL unsigned rope_partner_chunk(unsigned c, int rot_dim) {

@@ -15,7 +15,9 @@
 
 namespace lc {
 
-template <int D, bool INTERLEAVED, bool KV8>
+// BF16 (rope_append_varlen_bf16.hip): the 16-bit elements are bfloat16 — rope_rotate8_bf16 and kv8_quantize8_bf16 in place of
+// rope_rotate8 and kv8_quantize8, nothing else
+template <int D, bool INTERLEAVED, bool KV8, bool BF16 = false>
 LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew, half_t* Qout,
                                        void* __restrict__ Kpool, void* __restrict__ Vpool, const float* __restrict__ cos_sin,
                                        const int* __restrict__ cu_q, const int* __restrict__ block_table, const int* __restrict__ kv_len,
@@ -59,7 +61,8 @@ LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict
     }
     const u32x4_t q = *reinterpret_cast<const u32x4_t*>(Q + rowq + c * 8);
     const u32x4_t qp = INTERLEAVED ? q : *reinterpret_cast<const u32x4_t*>(Q + rowq + cp * 8);
-    *dst = rope_rotate8<INTERLEAVED>(q, qp, cs, c, rot_dim);
+    if constexpr (BF16) *dst = rope_rotate8_bf16<INTERLEAVED>(q, qp, cs, c, rot_dim);
+    else *dst = rope_rotate8<INTERLEAVED>(q, qp, cs, c, rot_dim);
     return;
   }
   if (p < 0) return;
@@ -68,13 +71,20 @@ LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict
   const u32x4_t k = *reinterpret_cast<const u32x4_t*>(Knew + rowkv + c * 8);
   const u32x4_t kp = INTERLEAVED ? k : *reinterpret_cast<const u32x4_t*>(Knew + rowkv + cp * 8);
   const u32x4_t v = *reinterpret_cast<const u32x4_t*>(Vnew + rowkv + c * 8);
-  const u32x4_t kr = rope_rotate8<INTERLEAVED>(k, kp, cs, c, rot_dim);
+  u32x4_t kr;
+  if constexpr (BF16) kr = rope_rotate8_bf16<INTERLEAVED>(k, kp, cs, c, rot_dim);
+  else kr = rope_rotate8<INTERLEAVED>(k, kp, cs, c, rot_dim);
   const size_t run = ((size_t)pid * (unsigned)Hkv + h) << lps;   // first row of the (page, head) run
   const unsigned off = (unsigned)(p & ((1 << lps) - 1)) * D + c * 8;   // elements inside the run
   if constexpr (KV8) {
     const float ks = k_scale ? k_scale[h] : 1.0f, vs = v_scale ? v_scale[h] : 1.0f;
-    *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Kpool) + run * D + off) = kv8_quantize8(kr, ks);   // the codes of the row ROUNDED to fp16
-    *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Vpool) + run * D + off) = kv8_quantize8(v, vs);
+    if constexpr (BF16) {   // the codes of the row ROUNDED to bf16
+      *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Kpool) + run * D + off) = kv8_quantize8_bf16(kr, ks);
+      *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Vpool) + run * D + off) = kv8_quantize8_bf16(v, vs);
+    } else {
+      *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Kpool) + run * D + off) = kv8_quantize8(kr, ks);   // the codes of the row ROUNDED to fp16
+      *reinterpret_cast<u32x2_t*>(static_cast<uint8_t*>(Vpool) + run * D + off) = kv8_quantize8(v, vs);
+    }
   } else {
     *reinterpret_cast<u32x4_t*>(static_cast<half_t*>(Kpool) + run * D + off) = kr;
     *reinterpret_cast<u32x4_t*>(static_cast<half_t*>(Vpool) + run * D + off) = v;

@@ -5,7 +5,13 @@
 //   it serves;  VARLEN_KV_T  the element type of those kernels' K / V
 //   varlen_mid(a), varlen_tail(c)   tuples of what its kernels take between kv_len and part_o, and between rows and window
 // and gets launch_attn_varlen_ranges<VARLEN_CACHE> (lc_plan.h): the D / RT dispatch, the grid of B x Hkv x RB x S workgroups, the LDS size.
+// The two bf16 units (tu_attn_varlen_paged_bf16.hip, _paged_kv8_bf16.hip) define VARLEN_RANGES launch_attn_varlen_bf16_ranges and get that one
+// instead: the same arguments, grid and LDS size on their own kernels.
 #include "lc_plan.h"
+
+#ifndef VARLEN_RANGES
+#define VARLEN_RANGES launch_attn_varlen_ranges
+#endif
 
 namespace lc {
 namespace {
@@ -35,7 +41,7 @@ int launch_varlen_d(const DecodePlan& p, int S, const DecodePtrs& a, float* part
 }  // namespace
 
 template <>
-int launch_attn_varlen_ranges<VARLEN_CACHE>(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
+int VARLEN_RANGES<VARLEN_CACHE>(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
   return p.call.D == 128 ? launch_varlen_d<128>(p, S, a, part_o, part_lse) : launch_varlen_d<64>(p, S, a, part_o, part_lse);
 }
 

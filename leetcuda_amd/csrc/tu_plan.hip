@@ -768,12 +768,14 @@ void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   static const char* const kKernels[] = {"attn_decode_kernel", "attn_decode_paged_kernel", "attn_decode_paged_kv8_kernel"};   // by DecodeCache
   static const char* const kLocal[] = {"attn_local_kernel", "attn_local_paged_kernel", "attn_local_paged_kv8_kernel"};
   static const char* const kVarlen[] = {"", "attn_varlen_paged_kernel", "attn_varlen_paged_kv8_kernel"};
-  const char* kern = (p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
+  static const char* const kVarlenBf16[] = {"", "attn_varlen_paged_bf16_kernel", "attn_varlen_paged_kv8_bf16_kernel"};   // (DecodeCall::bf16: varlen only)
+  const char* kern = (p.call.bf16 ? kVarlenBf16 : p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
   if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
     static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
     static const char* const kLocalChunk[] = {"attn_local_chunk_kernel", "attn_local_chunk_paged_kernel", "attn_local_chunk_paged_kv8_kernel"};
     static const char* const kVarlenChunk[] = {"", "attn_varlen_chunk_paged_kernel", "attn_varlen_chunk_paged_kv8_kernel"};
-    const char* chunk = (p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
+    static const char* const kVarlenChunkBf16[] = {"", "attn_varlen_chunk_paged_bf16_kernel", "attn_varlen_chunk_paged_kv8_bf16_kernel"};
+    const char* chunk = (p.call.bf16 ? kVarlenChunkBf16 : p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
     if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", chunk, p.call.D, p.S);
     else snprintf(buf, buflen, "%s<%d>", chunk, p.call.D);
     return;
@@ -838,6 +840,7 @@ int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p) {
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen) {
   const char* fmt = c.a.kv_bytes == 1 ? "rope_append_paged_kv8_kernel<%d,%s>" : "rope_append_paged_kernel<%d,%s>";
   if (c.varlen) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_kernel<%d,%s>" : "rope_append_varlen_kernel<%d,%s>";
+  if (c.bf16) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_bf16_kernel<%d,%s>" : "rope_append_varlen_bf16_kernel<%d,%s>";   // (varlen only)
   snprintf(buf, buflen, fmt, c.a.D, c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
 }
 

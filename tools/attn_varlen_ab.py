@@ -1,7 +1,7 @@
 """Time the ragged-batch calls (attn_varlen_paged, rope_append_varlen) against the rectangular calls they replace, and the
 existing decode / chunk / local / rope calls against another build of the library, in one process and in alternating rounds:
 
-    python tools/attn_varlen_ab.py [--parent-lib PATH] [--rounds 5] [--secs 0.3] [--rows abcdefg]
+    python tools/attn_varlen_ab.py [--parent-lib PATH] [--rounds 5] [--secs 0.3] [--rows abcdefg] [--bf16]
 
 H 32 / Hkv 8 / D 128, a paged fp16 cache with pages of 64 keys, every call the bare C entry on prepared arguments.  The rows:
     a  pure decode: B = 64, every Nq_b = 1, L = 4096 — the ragged call against lc_attn_decode_paged_f16 (same RT, same work: the price of VARLEN)
@@ -13,6 +13,9 @@ H 32 / Hkv 8 / D 128, a paged fp16 cache with pages of 64 keys, every call the b
     f  the existing decode, chunk, local and rope calls of THIS library against the same calls of --parent-lib (the parent commit's build)
     g  d again with max_nq = 496, 512 and 528 (RB = 31, 32, 33): the one live row block of every (sequence, K / V head) is workgroup
        (b Hkv + kvh) RB S of the 1-D grid, and consecutive workgroups go round the 8 XCDs — RB S a multiple of 8 puts all of them on one
+    h  (--bf16, or --rows h) the bfloat16 entries against their fp16 twins on the SAME shapes, for both cache kinds: a's
+       decode step, b's mixed step and c's eight prompts through lc_attn_varlen_paged_f16 / _bf16 and _kv8 / _kv8_bf16, and the mixed step's
+       rope call through lc_rope_append_varlen_f16 / _bf16 and _kv8 / _kv8_bf16.  The yardstick of a bf16 line is the fp16 line of its row
 Each line: the median, best and worst of the rounds' times (device events around >= --secs seconds of back-to-back calls, after a warm-up), the
 kernel name, and the ratio of the medians to the line's reference.  The rounds alternate the variants of a row, each round starting with another
 one, so that a drift of the machine lands on all of them.  Needs an MI355X."""
@@ -95,13 +98,70 @@ def cu_of(nqs):
     return cu
 
 
+def bf16_rows(lib, stream, rounds, secs):
+    """row h: per shape and cache kind, the fp16 and the bf16 entry on the same geometry and the same values (the 16-bit tensors of one are the
+    other's converted; the fp8 pools and the tables are shared): the bytes moved and the number of instructions issued are the same"""
+    BF = torch.bfloat16
+
+    def both(x):
+        return {"f16": x, "bf16": x.to(BF)}
+
+    shapes = (("decode", 64, 4096, [1] * 64, 1), ("mixed step", 64, 4096, [1] * 63 + [512], 512),
+              ("eight prompts", 8, 2048, [100 + (2048 - 100) * i // 7 for i in range(8)], 2048))
+    cs = capi.rope_table(4096, D).cuda()
+    for label, B, L, nqs, max_nq in shapes:
+        T, mp = sum(nqs), L // PS
+        lens = i32([L] * B if label != "eight prompts" else nqs)
+        cu = i32(cu_of(nqs))
+        table = torch.randperm(B * mp, device="cuda").to(torch.int32).view(B, mp).contiguous()
+        q, kp = both(torch.randn(T, H, D, device="cuda").half()), both(torch.randn(B * mp, HKV, PS, D, device="cuda").half())
+        vp = both(torch.randn(B * mp, HKV, PS, D, device="cuda").half())
+        kp8, vp8 = (torch.randint(0, 0x7E, (B * mp, HKV, PS, D), device="cuda", dtype=torch.uint8) for _ in range(2))      # finite e4m3 codes
+        ks, vs = (torch.full((HKV,), 0.25, device="cuda") for _ in range(2))
+        o = {k: torch.empty_like(v) for k, v in q.items()}
+        for kind in ("paged", "kv8"):
+            variants = {}
+            for el in ("f16", "bf16"):
+                if kind == "paged":
+                    fn = lib.lc_attn_varlen_paged_f16 if el == "f16" else lib.lc_attn_varlen_paged_bf16
+                    step = call(fn, q[el].data_ptr(), kp[el].data_ptr(), vp[el].data_ptr(), o[el].data_ptr(), cu.data_ptr(), table.data_ptr(),
+                                lens.data_ptr(), B, H, HKV, T, max_nq, B * mp, PS, mp, D, 0, None, CAUSAL, None, 0, stream)
+                else:
+                    fn = lib.lc_attn_varlen_paged_kv8 if el == "f16" else lib.lc_attn_varlen_paged_kv8_bf16
+                    step = call(fn, q[el].data_ptr(), kp8.data_ptr(), vp8.data_ptr(), o[el].data_ptr(), cu.data_ptr(), table.data_ptr(), lens.data_ptr(),
+                                ks.data_ptr(), vs.data_ptr(), B, H, HKV, T, max_nq, B * mp, PS, mp, D, 0, None, CAUSAL, None, 0, stream)
+                namer = capi.attn_varlen_paged_kernel_name if el == "f16" else capi.attn_varlen_paged_bf16_kernel_name
+                variants[el] = (step, namer(B, H, HKV, T, max_nq, PS, mp, D, causal=True, kv8=kind == "kv8"))
+            run_row(f"h {label} {kind}", variants, "f16", rounds, secs)
+        if label != "mixed step":
+            continue
+        kt, vt = both(torch.randn(T, HKV, D, device="cuda").half()), both(torch.randn(T, HKV, D, device="cuda").half())
+        qo = {k: torch.empty_like(v) for k, v in q.items()}
+        for kind in ("paged", "kv8"):
+            variants = {}
+            for el in ("f16", "bf16"):
+                sym = {("paged", "f16"): "lc_rope_append_varlen_f16", ("paged", "bf16"): "lc_rope_append_varlen_bf16",
+                       ("kv8", "f16"): "lc_rope_append_varlen_kv8", ("kv8", "bf16"): "lc_rope_append_varlen_kv8_bf16"}[kind, el]
+                pk, pv = (kp[el], vp[el]) if kind == "paged" else (kp8, vp8)
+                scale_ptrs = (ks.data_ptr(), vs.data_ptr()) if kind == "kv8" else ()
+                step = call(getattr(lib, sym), q[el].data_ptr(), kt[el].data_ptr(), vt[el].data_ptr(), qo[el].data_ptr(), pk.data_ptr(), pv.data_ptr(),
+                            cs.data_ptr(), cu.data_ptr(), table.data_ptr(), lens.data_ptr(), *scale_ptrs, B, H, HKV, T, max_nq, B * mp, PS, mp, D, D, 4096,
+                            H * D, HKV * D, 0, stream)
+                namer = capi.rope_append_varlen_kernel_name if el == "f16" else capi.rope_append_varlen_bf16_kernel_name
+                variants[el] = (step, namer(B, H, HKV, T, max_nq, PS, mp, D, D, 4096, kv8=kind == "kv8"))
+            run_row(f"h rope {kind}", variants, "f16", rounds, secs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--secs", type=float, default=0.3)
     ap.add_argument("--rows", default="abcdefg")
+    ap.add_argument("--bf16", action="store_true", help="time the bfloat16 entries against their fp16 twins (row h) and nothing else")
     a = ap.parse_args()
+    if a.bf16:
+        a.rows = "h"
     parent = None
     if a.parent_lib:   # its own symbols first (RTLD_DEEPBIND): two builds of one library in a process must not interpose each other
         parent = C.CDLL(a.parent_lib, mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
@@ -202,6 +262,9 @@ def main():
                                                vp_.data_ptr(), cs.data_ptr(), cu_.data_ptr(), tab_.data_ptr(), lens_.data_ptr(), B_, H, HKV, T_, mq, kp_.shape[0],
                                                PS, mp_, D, D, 4096, H * D, HKV * D, 0, stream),
                                           capi.rope_append_varlen_kernel_name(B_, H, HKV, T_, mq, PS, mp_, D, D, 4096))}, "rope_paged padded", a.rounds, a.secs)
+    # ---- h: the bf16 entries against their fp16 twins
+    if "h" in a.rows:
+        bf16_rows(lib, stream, a.rounds, a.secs)
     # ---- f: the existing calls, this build against the parent's
     if "f" in a.rows:
         if parent is None:
