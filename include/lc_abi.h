@@ -721,6 +721,61 @@ int lc_rope_append_varlen_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int
                                                int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
                                                char* buf, int buflen);
 
+/* EXTENSION: the ragged entries with a log-sum-exp output, and the merge of two attention states (attn_varlen_lse.hip, attn_merge.hip, DESIGN.md
+ * section 4.3n) — what shared-prefix (cascade) attention, attention over KV shards and a windowed + global pass are built from.
+ * lc_attn_varlen_paged_lse_f16 / _lse_kv8 / _lse_bf16 / _lse_kv8_bf16 take the arguments of lc_attn_varlen_paged_f16 / _kv8 / _bf16 /
+ * _kv8_bf16 with `lse` right behind O:
+ *   lse   device float32 [T H]: row t, head h at t H + h, the row of O.  lse = ln(sum over the row's visible keys of exp(score)), the sink of
+ *         the head included; score = q.k / sqrt(D), times k_scale[head] for fp8 pools (v_scale does not enter).  A row that sees no key and
+ *         has no sink: -inf (its O is 0).  Rows no sequence owns are written in neither buffer.
+ * The checks, their order and the statuses are the twin's, with lse == NULL among the NULL pointers (LC_ERR_ARG).  So are the plan — RT, RB, S,
+ * grid, LDS — and the workspace: lc_attn_varlen_paged_workspace_bytes / _kv8_workspace_bytes serve these entries too, and the capture / failed
+ * lease fallback to S = 1 is the twin's.  O is the twin's O bit for bit.  The name calls report the twin's plan with "_lse" in the kernel:
+ * attn_varlen_paged_lse_kernel<D,RT>, attn_varlen_chunk_paged_kv8_lse_bf16_kernel<D>, ... (S > 1: + attn_varlen_combine_lse_kernel<D> /
+ * attn_varlen_combine_lse_bf16_kernel<D>).
+ * lc_attn_merge_states_f16 / _bf16: (Oa, lse_a) and (Ob, lse_b) are the states of the SAME rows over two DISJOINT key sets, O [T,H,D] 16-bit,
+ * lse float32 [T H]; the merged state is that of the union.  Per row in fp32: m = max(la, lb), wa = exp(la - m), wb = exp(lb - m),
+ * O = (wa Oa + wb Ob) / (wa + wb) rounded once (nearest even), lse = m + ln(wa + wb).  One side -inf: the other passes through bit for bit.
+ * Both -inf: O = 0, lse = -inf.  Oout may be Oa or Ob and lse_out may be lse_a or lse_b (in place).
+ *   cu_q  NULL: all T H rows.  Else device int32 [B + 1], the offsets of the ragged calls: only the rows of tokens clamp(cu_q[0], 0, T) ..
+ *         clamp(cu_q[B], 0, T) - 1 are read and written, so a captured step whose T is a bound keeps the rows behind its last token.
+ * Status: a NULL pointer other than cu_q LC_ERR_ARG; B, T or H < 1, T H > 2^31 - 1 or an O pointer off 16 bytes LC_ERR_SHAPE; D outside
+ * {64, 128} LC_ERR_HEADDIM.  attn_merge_states_kernel<D> / attn_merge_states_bf16_kernel<D>, no workspace.
+ * Not here: an lse output of lc_attn_fwd_* and of the rectangular cache entries (a ragged call whose Nq_b all equal max_nq is the rectangular
+ * call), an N-way merge in one launch, fp32 O partials between the levels. */
+int lc_attn_varlen_paged_lse_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse,
+                                 const int* cu_q, const int* block_table, const int* kv_len,
+                                 int B, int H, int Hkv, int T, int max_nq,
+                                 int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_lse_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                         int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_lse_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse,
+                                 const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                                 int B, int H, int Hkv, int T, int max_nq,
+                                 int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_lse_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                             int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_lse_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse,
+                                  const int* cu_q, const int* block_table, const int* kv_len,
+                                  int B, int H, int Hkv, int T, int max_nq,
+                                  int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_lse_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                              int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_lse_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse,
+                                      const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                                      int B, int H, int Hkv, int T, int max_nq,
+                                      int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_lse_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                                  int flags, char* buf, int buflen);
+int lc_attn_merge_states_f16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out,
+                             const int* cu_q, int B, int T, int H, int D, void* stream);
+int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out,
+                              const int* cu_q, int B, int T, int H, int D, void* stream);
+
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

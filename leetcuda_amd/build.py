@@ -36,7 +36,10 @@ AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_a
                     "tu_attn_varlen_paged": "isa_audit_varlen_paged.json", "tu_attn_varlen_paged_kv8": "isa_audit_varlen_paged_kv8.json",
                     "tu_rope_append_varlen": "isa_audit_rope_append_varlen.json",
                     "tu_attn_varlen_paged_bf16": "isa_audit_varlen_paged_bf16.json", "tu_attn_varlen_paged_kv8_bf16": "isa_audit_varlen_paged_kv8_bf16.json",
-                    "tu_rope_append_varlen_bf16": "isa_audit_rope_append_varlen_bf16.json"}
+                    "tu_rope_append_varlen_bf16": "isa_audit_rope_append_varlen_bf16.json",
+                    "tu_attn_varlen_paged_lse": "isa_audit_varlen_paged_lse.json", "tu_attn_varlen_paged_kv8_lse": "isa_audit_varlen_paged_kv8_lse.json",
+                    "tu_attn_varlen_paged_lse_bf16": "isa_audit_varlen_paged_lse_bf16.json",
+                    "tu_attn_varlen_paged_kv8_lse_bf16": "isa_audit_varlen_paged_kv8_lse_bf16.json", "tu_attn_merge": "isa_audit_merge.json"}
 
 
 def _newer(target: Path, sources) -> bool:

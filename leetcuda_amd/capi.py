@@ -107,6 +107,18 @@ SYMBOLS = {
     "lc_rope_append_varlen_kv8_bf16": (_i, [_vp] * 12 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
     "lc_rope_append_varlen_bf16_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
     "lc_rope_append_varlen_kv8_bf16_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    # the ragged entries that also write each row's log-sum-exp: their twins with `lse` right behind O (the workspace queries above serve them)
+    "lc_attn_varlen_paged_lse_f16": (_i, [_vp] * 8 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_lse_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_lse_kv8": (_i, [_vp] * 10 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_lse_kv8_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_lse_bf16": (_i, [_vp] * 8 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_lse_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_lse_kv8_bf16": (_i, [_vp] * 10 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_lse_kv8_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    # merge of two (O, lse) states: Oa, lse_a, Ob, lse_b, Oout, lse_out, cu_q (or NULL), B, T, H, D, stream
+    "lc_attn_merge_states_f16": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
+    "lc_attn_merge_states_bf16": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -1204,6 +1216,152 @@ def rope_append_varlen_bf16_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pag
     check(getattr(load(), symbol)(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, H * D if q_row_stride is None else q_row_stride,
                                   Hkv * D if kv_row_stride is None else kv_row_stride, ROPE_INTERLEAVED if interleaved else 0, buf, 128), symbol)
     return buf.value.decode()
+
+
+# The ragged calls that also hand back each row's log-sum-exp, the merge of two such states, and the shared-prefix (cascade) step built from
+# them (lc_attn_varlen_paged_lse_*, lc_attn_merge_states_*).  lse is float32 [T,H]: row t, head h is the natural log of
+# the sum of exp(score) over the keys that row saw, its sink included; -inf for a row that saw none (its O is 0).
+
+def _lse_out(q, lse):
+    """the lse tensor of a call on q [T,H,D]: float32 [T,H], allocated next to q when None"""
+    import torch
+    if lse is None:
+        return torch.empty(tuple(q.shape[:2]), dtype=torch.float32, device=q.device)
+    if lse.dtype != torch.float32:
+        raise TypeError(f"lse must be float32, got {lse.dtype}")
+    if q.dim() != 3 or tuple(lse.shape) != tuple(q.shape[:2]) or not lse.is_contiguous():
+        _shape_err(f"lse {tuple(lse.shape)} for q {tuple(q.shape)}: contiguous [T,H] expected")
+    return lse
+
+
+def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, kv8, bf16):
+    import torch
+    el, el_name = (torch.bfloat16, "bfloat16") if bf16 else (torch.half, "float16")
+    fp8 = (torch.float8_e4m3fn, torch.uint8)
+    if kv8:
+        if q.dtype != el or o.dtype != el:
+            raise TypeError(f"q / o must be {el_name}, got {q.dtype} / {o.dtype}")
+        if k_pool.dtype not in fp8 or v_pool.dtype not in fp8:
+            raise TypeError(f"k_pool8 / v_pool8 must be float8_e4m3fn or uint8, got {k_pool.dtype} / {v_pool.dtype}")
+    elif q.dtype != el or o.dtype != el or k_pool.dtype != el or v_pool.dtype != el:
+        raise TypeError(f"q / o / k_pool / v_pool must be {el_name}, got {q.dtype} / {o.dtype} / {k_pool.dtype} / {v_pool.dtype}")
+    dims = _varlen_dims(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq)
+    scales = ()
+    if kv8:
+        for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if s is None:
+                continue
+            if s.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32, got {s.dtype}")
+            if tuple(s.shape) != (dims[2],):
+                _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
+        scales = (_ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None)
+    local = _varlen_local(q, window, sinks)
+    lse = _lse_out(q, lse)
+    _need_gpu(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if kv8 and s is not None))
+    symbol = "lc_attn_varlen_paged_lse_" + (("kv8_bf16" if bf16 else "kv8") if kv8 else ("bf16" if bf16 else "f16"))
+    check(getattr(load(), symbol)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(lse), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *scales, *dims,
+                                  *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), symbol)
+    return o, lse
+
+
+def attn_varlen_paged_lse(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, lse=None, causal=False, window=0, sinks=None, workspace=None):
+    """attn_varlen_paged that also writes each row's log-sum-exp (lc_attn_varlen_paged_lse_f16): lse float32 [T,H] (None: allocated).  O is
+    attn_varlen_paged's, bit for bit; the workspace is attn_varlen_paged_workspace_bytes'.  Returns (o, lse)."""
+    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, False)
+
+
+def attn_varlen_paged_kv8_lse(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, lse=None, k_scale=None, v_scale=None, causal=False,
+                              window=0, sinks=None, workspace=None):
+    """attn_varlen_paged_kv8 + lse (lc_attn_varlen_paged_lse_kv8): the scores under the log are q.k k_scale / sqrt(D); v_scale does not enter."""
+    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, False)
+
+
+def attn_varlen_paged_lse_bf16(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, lse=None, causal=False, window=0, sinks=None,
+                               workspace=None):
+    """attn_varlen_paged_bf16 + lse (lc_attn_varlen_paged_lse_bf16); lse stays float32."""
+    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, True)
+
+
+def attn_varlen_paged_kv8_lse_bf16(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, lse=None, k_scale=None, v_scale=None, causal=False,
+                                   window=0, sinks=None, workspace=None):
+    """attn_varlen_paged_kv8_bf16 + lse (lc_attn_varlen_paged_lse_kv8_bf16)."""
+    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, True)
+
+
+def attn_varlen_paged_lse_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=False, window=0, kv8=False, bf16=False) -> str:
+    """attn_varlen_paged_kernel_name's (bf16: attn_varlen_paged_bf16_kernel_name's) plan with `_lse` in the kernel's name:
+    "attn_varlen_paged_lse_kernel<D,RT>", "attn_varlen_chunk_paged_kv8_lse_bf16_kernel<D>", + " xS" with S > 1."""
+    symbol = "lc_attn_varlen_paged_lse_" + ("kv8_" if kv8 else "") + ("bf16_" if bf16 else "") + "kernel_name"
+    return _decode_kernel_name(symbol, B, H, Hkv, T, max_nq, page_size, max_pages, D, window, causal=causal)
+
+
+def attn_merge_states(o_a, lse_a, o_b, lse_b, out=None, lse_out=None, cu_q=None):
+    """Merge two attention states over disjoint key sets (lc_attn_merge_states_f16 / _bf16, picked by o_a's dtype; float32 O is refused):
+    o_a, o_b [T,H,D] float16 or bfloat16, lse_a, lse_b float32 [T,H].  out / lse_out: where the merged state goes — None allocates, and either
+    may BE an input (in place).  cu_q: None = every row, or the DEVICE int32 [B + 1] offsets of the ragged calls: only the rows of tokens
+    cu_q[0] .. cu_q[B] - 1 (clamped into the T rows) are read and written.  A side whose lse is -inf contributes nothing and the other passes
+    through bit for bit; both -inf give O = 0, lse = -inf.  Returns (out, lse_out)."""
+    import torch
+    if o_a.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"o_a / o_b must be float16 or bfloat16, got {o_a.dtype}")
+    out = torch.empty_like(o_a) if out is None else out
+    if o_b.dtype != o_a.dtype or out.dtype != o_a.dtype:
+        raise TypeError(f"o_a / o_b / out must share one 16-bit dtype, got {o_a.dtype} / {o_b.dtype} / {out.dtype}")
+    if o_a.dim() != 3 or tuple(o_b.shape) != tuple(o_a.shape) or tuple(out.shape) != tuple(o_a.shape):
+        _shape_err(f"o_a {tuple(o_a.shape)} o_b {tuple(o_b.shape)} out {tuple(out.shape)}: one [T,H,D] expected")
+    if not (o_a.is_contiguous() and o_b.is_contiguous() and out.is_contiguous()):
+        _shape_err("o_a / o_b / out must be contiguous")
+    lse_a, lse_b, lse_out = _lse_out(o_a, lse_a), _lse_out(o_a, lse_b), _lse_out(o_a, lse_out)
+    T, H, D = o_a.shape
+    B = 1
+    if cu_q is not None:
+        if cu_q.dtype != torch.int32:
+            raise TypeError(f"cu_q must be int32, got {cu_q.dtype}")
+        if cu_q.dim() != 1 or cu_q.shape[0] < 2:
+            _shape_err(f"cu_q {tuple(cu_q.shape)}: [B + 1] expected")
+        B = cu_q.shape[0] - 1
+    _need_gpu(o_a, lse_a, o_b, lse_b, out, lse_out, *(() if cu_q is None else (cu_q,)))
+    symbol = "lc_attn_merge_states_bf16" if o_a.dtype == torch.bfloat16 else "lc_attn_merge_states_f16"
+    check(getattr(load(), symbol)(_ptr(o_a), _ptr(lse_a), _ptr(o_b), _ptr(lse_b), _ptr(out), _ptr(lse_out), None if cu_q is None else _ptr(cu_q),
+                                  B, T, H, D, _stream()), symbol)
+    return out, lse_out
+
+
+def attn_cascade_paged(q, k_pool, v_pool, o, cu_groups, prefix_table, prefix_len, cu_q, block_table, kv_len, max_nq_prefix, max_nq, *, sinks=None,
+                       scratch, k_scale=None, v_scale=None, workspaces=(None, None)):
+    """One shared-prefix (cascade) attention step over a paged cache, as three library calls on the current stream and no host sync (the whole
+    step is graph-capturable):
+      1. prefix level — non-causal, window 0, no sinks: prefix group g is ONE ragged "sequence" that owns the tokens cu_groups[g] ..
+         cu_groups[g + 1] - 1 (the new tokens of every sequence behind that prefix, which are therefore contiguous in q) and reads the
+         prefix_len[g] keys of prefix_table[g] once per 64 query rows instead of once per sequence;  -> scratch (o_prefix, lse_prefix)
+      2. suffix level — causal, the ragged call of the step on the PRIVATE keys only: block_table / kv_len hold each sequence's pages and
+         length behind the prefix (new tokens included); `sinks` goes here and only here;  -> (o, lse)
+      3. merge, in place into (o, lse), on the rows of cu_q.
+    q, o [T,H,D] float16 or bfloat16; the pools 16-bit of q's dtype, or fp8 (float8_e4m3fn / uint8) with k_scale / v_scale float32 [Hkv].
+    cu_groups int32 [Gp + 1], prefix_table int32 [Gp, pages], prefix_len int32 [Gp], cu_q int32 [B + 1], block_table int32 [B, pages], kv_len
+    int32 [B]: all DEVICE tensors, read by the kernels only.  max_nq_prefix bounds the tokens of a group, max_nq those of a sequence.
+    scratch = (o_prefix [T,H,D] of q's dtype, lse_prefix float32 [T,H], lse float32 [T,H]): the caller's buffers — nothing is allocated here.
+    workspaces: optional split-KV workspaces of the two levels (attn_varlen_paged_workspace_bytes of each level's shape); under capture a level
+    without one runs one KV range.
+    Caveats.  The prefix must end on a page boundary of the caller's tables (the suffix table starts with a fresh page: a page belongs to one
+    level).  A sliding window does not compose with the cascade (the window's lower edge would cut through the levels): there is none.  A
+    sink is one more score of a row and must join exactly ONE level: here the suffix.  Every token of cu_q must lie in a group — a sequence
+    without a shared prefix is a group of prefix_len 0 (lse -inf: the suffix passes through bit for bit).  Returns (o, lse)."""
+    import torch
+    if not isinstance(scratch, (tuple, list)) or len(scratch) != 3:
+        raise TypeError("scratch must be (o_prefix, lse_prefix, lse)")
+    o_p, lse_p, lse = scratch
+    kv8 = k_pool.dtype in (torch.float8_e4m3fn, torch.uint8)
+    if q.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q must be float16 or bfloat16, got {q.dtype}")
+    if sinks is not None and not torch.is_tensor(sinks):
+        raise TypeError("sinks must be a float32 tensor or None")
+    bf16 = q.dtype == torch.bfloat16
+    ks, vs = (k_scale, v_scale) if kv8 else (None, None)
+    _varlen_lse(q, k_pool, v_pool, o_p, lse_p, cu_groups, prefix_table, prefix_len, max_nq_prefix, ks, vs, False, 0, None, workspaces[0], kv8, bf16)
+    _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, ks, vs, True, 0, sinks, workspaces[1], kv8, bf16)
+    return attn_merge_states(o, lse, o_p, lse_p, out=o, lse_out=lse, cu_q=cu_q)
 
 
 def attn_fwd_bf16(q, k, v, o):

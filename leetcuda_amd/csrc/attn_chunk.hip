@@ -32,6 +32,8 @@ __global__ __launch_bounds__(256) void attn_chunk_kernel(const half_t* __restric
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -55,6 +57,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kernel(const half_t* __r
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -80,6 +84,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kv8_kernel(const half_t*
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

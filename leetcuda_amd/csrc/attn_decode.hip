@@ -78,6 +78,11 @@ struct DecodeVarlen {
   int T;             // rows of Q and O
 };
 
+// The row's log-sum-exp next to O (attn_varlen_lse.hip).  Every other kernel leaves the field unused.
+struct DecodeLse {
+  float* lse;   // device float[rows of O]: ln(sum over the row's visible keys of exp(score), the sink included); -inf: no key, no sink
+};
+
 // eight e4m3 bytes (a: bytes 0 .. 3, b: bytes 4 .. 7, memory order) as eight fp16 values, element i = byte i: one v_cvt_scalef32_pk_f16_fp8 per two
 // elements, scale 1.0 — every e4m3 value is an fp16 value (the smallest, 2^-9, a normal one), so the conversion is exact; 0x7f / 0xff give NaN
 LC_DEVINL u32x4_t kv8_half8(uint32_t a, uint32_t b) {
@@ -125,6 +130,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

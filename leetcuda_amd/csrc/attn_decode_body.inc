@@ -25,6 +25,10 @@
 // rounding of P and of O (cvt16<BF16>, RNE), and the e4m3 -> 16-bit conversion of an fp8 cache (kv8_16x8<BF16>).  Loads, LDS images, transposed
 // reads, masks, (m, l) and the partials do not know the element type.  With BF16 = false the three helpers ARE mfma16, (half_t)x and kv8_half8:
 // every fp16 kernel's code is what it was without the parameter (§4.3m compares it).
+// A `constexpr bool LSE` with a `const DecodeLse ls` (LSE = false: unused) is the newest.  LSE = true (the attn_varlen_*_lse*_kernel of
+// attn_varlen_lse.hip; DESIGN.md §4.3n): where wave 0 stores a row's O (S == 1) its h == 0 lanes also store the row's log-sum-exp in NATURAL
+// units, ls.lse[row] with the global row of O and O's row guard.  The S > 1 path is untouched: part_lse always carried it, and the combine
+// kernel of an LSE plan stores it.  With LSE = false nothing changes: every other kernel's code does not depend on the parameter (§4.3n compares it).
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -417,6 +421,9 @@
         const f32x4_t x = o[rt][db] * inv;
         half4_t y = {cvt16<BF16>(x[0]), cvt16<BF16>(x[1]), cvt16<BF16>(x[2]), cvt16<BF16>(x[3])};
         *reinterpret_cast<half4_t*>(O + row * D + 16 * db + 4 * h) = y;
+      }
+      if constexpr (LSE) {   // (m in the log2 domain -> natural log: what a caller's merge of two results wants)
+        if (h == 0) ls.lse[row] = lt[rt] > 0.f ? (mt[rt] + log2f(lt[rt])) * 0.6931471805599453f : DEC_NEG_INF;
       }
     } else {
       float* po = part_o + ((long)s_idx * total_rows + row) * D;

@@ -34,6 +34,8 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const half_t* __
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

@@ -40,6 +40,8 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kv8_kernel(const half_t
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

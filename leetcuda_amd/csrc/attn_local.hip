@@ -32,6 +32,8 @@ __global__ __launch_bounds__(256) void attn_local_kernel(const half_t* __restric
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -52,6 +54,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_kernel(const half_t* __r
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -74,6 +78,8 @@ __global__ __launch_bounds__(256) void attn_local_paged_kernel(const half_t* __r
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -98,6 +104,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kernel(const half_
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -123,6 +131,8 @@ __global__ __launch_bounds__(256) void attn_local_paged_kv8_kernel(const half_t*
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -148,6 +158,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kv8_kernel(const h
   constexpr bool VARLEN = false;
   constexpr bool BF16 = false;
   const DecodeVarlen vl{};
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

@@ -39,6 +39,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kernel(const half_t* __
   const DecodeVarlen vl{cu_q, T_rows};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -63,6 +65,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kernel(const half
   const DecodeVarlen vl{cu_q, T_rows};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -88,6 +92,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_kernel(const half_t
   // (the body takes the pools as byte bases only: page_base)
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -114,6 +120,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_kernel(const 
   const DecodeVarlen vl{cu_q, T_rows};
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

@@ -32,6 +32,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_bf16_kernel(const half_
   const DecodeVarlen vl{cu_q, T_rows};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -57,6 +59,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_bf16_kernel(const
   const DecodeVarlen vl{cu_q, T_rows};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -83,6 +87,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_bf16_kernel(const h
   // (the body takes the pools as byte bases only: page_base)
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 
@@ -109,6 +115,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_bf16_kernel(c
   const DecodeVarlen vl{cu_q, T_rows};
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
+  constexpr bool LSE = false;
+  const DecodeLse ls{};
 #include "attn_decode_body.inc"
 }
 

@@ -87,17 +87,20 @@ DecodeCall decode_local(DecodeCall c, int window, const float* sinks = nullptr) 
 }
 // the lc_attn_varlen_paged_* entries: the paged local call of Nq = max_nq on T token-major rows
 // bf16: the lc_attn_varlen_paged_*bf16 entries — the same call on bfloat16 elements
-DecodeCall decode_varlen(DecodeCall c, int T, bool bf16 = false) {
+// lse: the lc_attn_varlen_paged_lse_* entries — the same call, which also writes each row's log-sum-exp
+DecodeCall decode_varlen(DecodeCall c, int T, bool bf16 = false, bool lse = false) {
   c.varlen = true;
   c.T = T;
   c.max_nq = c.Nq;
   c.bf16 = bf16;
+  c.lse = lse;
   return c;
 }
 // block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local or varlen call, or nullptr; cu_q: a varlen call
 int decode_run(const DecodeCall& c, const void* Q, const void* K, const void* V, void* O, const int* kv_len, const int* block_table, const float* k_scale,
-               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr, const int* cu_q = nullptr) {
-  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks, cu_q};
+               const float* v_scale, void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr, const int* cu_q = nullptr,
+               float* lse = nullptr) {
+  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks, cu_q, lse};
   DecodePlan p;
   if (int rc = check_attn_decode(c, &a, &p)) return rc;
   if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
@@ -114,6 +117,17 @@ int decode_name(const DecodeCall& c, char* buf, int buflen) {
   if (int rc = check_attn_decode(c, nullptr, &p)) return rc;
   format_attn_decode(p, buf, buflen);
   return LC_OK;
+}
+
+// The two state-merge entries state a MergeCall; check_attn_merge (tu_plan.hip) checks it, launch_attn_merge (tu_attn_merge.hip) runs it
+int merge_run(bool bf16, const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out, const int* cu_q, int B,
+              int T, int H, int D, void* stream) {
+  const MergeCall c{B, T, H, D, bf16};
+  const MergePtrs p{static_cast<const half_t*>(Oa), lse_a, static_cast<const half_t*>(Ob), lse_b, static_cast<half_t*>(Oout), lse_out, cu_q,
+                    static_cast<hipStream_t>(stream)};
+  if (int rc = check_attn_merge(c, p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_merge(c, p);
 }
 
 // The two append-to-cache entries (fp16 and fp8 pools) each state an AppendCall; check_kv_append (tu_plan.hip) checks it; append_run and append_name
@@ -560,6 +574,68 @@ int lc_attn_varlen_paged_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int 
                                               char* buf, int buflen) {
   return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true), buf,
                      buflen);
+}
+
+// The varlen entries that also write each row's log-sum-exp: the four entries above with `lse` right behind O, as a DecodeCall
+// with lse = true.  The checks (lse joins the NULL check), the plan and the workspace bytes are the twin's; the kernels and their names are the
+// twin's with "_lse" in them
+int lc_attn_varlen_paged_lse_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* cu_q, const int* block_table,
+    const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+    const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, false, true),
+                    Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse);
+}
+
+int lc_attn_varlen_paged_lse_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, false, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_lse_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const int* cu_q, const int* block_table,
+    const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+    const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, false, true),
+                    Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse);
+}
+
+int lc_attn_varlen_paged_lse_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, false, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_lse_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* cu_q, const int* block_table,
+    const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+    const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, true, true),
+                    Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse);
+}
+
+int lc_attn_varlen_paged_lse_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, true, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_lse_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const int* cu_q, const int* block_table,
+    const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+    const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, true, true),
+                    Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse);
+}
+
+int lc_attn_varlen_paged_lse_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true, true), buf,
+                     buflen);
+}
+
+// The merge of two (O, lse) states over disjoint key sets (attn_merge.hip): merge_run above states a MergeCall
+int lc_attn_merge_states_f16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out, const int* cu_q, int B,
+                             int T, int H, int D, void* stream) {
+  return merge_run(false, Oa, lse_a, Ob, lse_b, Oout, lse_out, cu_q, B, T, H, D, stream);
+}
+
+int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out, const int* cu_q, int B,
+                              int T, int H, int D, void* stream) {
+  return merge_run(true, Oa, lse_a, Ob, lse_b, Oout, lse_out, cu_q, B, T, H, D, stream);
 }
 
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,

@@ -163,6 +163,8 @@ struct DecodeCall {
   int T = 0, max_nq = 0;                 // varlen only: the rows of Q and O, and the host's bound on every Nq_b
   bool bf16 = false;                     // lc_attn_varlen_paged_*bf16: Q, O and a 16-bit cache are bfloat16 (varlen only).  It picks the
                                          // kernels (and their names) and nothing else: every check and RT, RB, S, grid, LDS, workspace are the fp16 call's
+  bool lse = false;                      // lc_attn_varlen_paged_lse_* (DESIGN.md §4.3n): the call also writes each row's log-sum-exp (varlen only).  It picks
+                                         // the kernels (and their names) and adds DecodePtrs::lse to the NULL check; the plan and the workspace are the twin's
 };
 enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
 // ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
@@ -200,6 +202,7 @@ struct DecodePtrs {
   const float *k_scale, *v_scale;   // PAGED_KV8: device float[Hkv] or nullptr = 1.0; else nullptr
   const float* sinks;               // a local or varlen call: device float[H] or nullptr = no sinks; else nullptr
   const int* cu_q = nullptr;        // a varlen call: device int32[B + 1]; else nullptr
+  float* lse = nullptr;             // a call with DecodeCall::lse: device float[T H]; else nullptr
 };
 // The checks of the three decode entry points, in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's
 // pointers (nullptr: a query call, which has none)
@@ -233,6 +236,35 @@ int launch_attn_varlen_combine(const DecodePlan& p, int S, const DecodePtrs& a, 
 template <DecodeCache C>
 int launch_attn_varlen_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 int launch_attn_varlen_combine_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
+// ... and of a varlen plan that also writes the log-sum-exp (DecodeCall::lse): the same launcher on the attn_varlen_*_lse_kernel / _lse_bf16_kernel,
+// instantiated in tu_attn_varlen_paged_lse.hip / _paged_kv8_lse.hip / _paged_lse_bf16.hip / _paged_kv8_lse_bf16.hip; the combine launches
+// (attn_varlen_combine_lse_kernel<D> / _lse_bf16_kernel<D>): tu_attn_varlen_paged_lse.hip / _paged_lse_bf16.hip
+template <DecodeCache C>
+int launch_attn_varlen_lse_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+int launch_attn_varlen_combine_lse(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
+template <DecodeCache C>
+int launch_attn_varlen_lse_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+int launch_attn_varlen_combine_lse_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
+
+// What a caller of a state-merge entry states (lc_attn_merge_states_f16 / _bf16): two (O [T,H,D], lse [T H]) states over disjoint
+// key sets become the state over their union.  There is nothing to plan: attn_merge_states_kernel<D> / attn_merge_states_bf16_kernel<D> on
+// ceil(T H / (2048 / D)) workgroups, no workspace.
+struct MergeCall {
+  int B, T, H, D;                        // B: entries of cu_q - 1 (unused without cu_q)
+  bool bf16;
+};
+struct MergePtrs {
+  const half_t* Oa;                      // (16-bit lanes: fp16 or, MergeCall::bf16, bfloat16)
+  const float* lse_a;
+  const half_t* Ob;
+  const float* lse_b;
+  half_t* Oout;                          // may be Oa or Ob
+  float* lse_out;                        // may be lse_a or lse_b
+  const int* cu_q;                       // device int32[B + 1] or nullptr = every row
+  hipStream_t st;
+};
+int check_attn_merge(const MergeCall& c, const MergePtrs& p);    // tu_plan.hip
+int launch_attn_merge(const MergeCall& c, const MergePtrs& p);   // tu_attn_merge.hip; checked arguments
 
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on

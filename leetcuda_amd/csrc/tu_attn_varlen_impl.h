@@ -6,11 +6,17 @@
 //   varlen_mid(a), varlen_tail(c)   tuples of what its kernels take between kv_len and part_o, and between rows and window
 // and gets launch_attn_varlen_ranges<VARLEN_CACHE> (lc_plan.h): the D / RT dispatch, the grid of B x Hkv x RB x S workgroups, the LDS size.
 // The two bf16 units (tu_attn_varlen_paged_bf16.hip, _paged_kv8_bf16.hip) define VARLEN_RANGES launch_attn_varlen_bf16_ranges and get that one
-// instead: the same arguments, grid and LDS size on their own kernels.
+// instead: the same arguments, grid and LDS size on their own kernels.  The four LSE units (tu_attn_varlen_paged*_lse*.hip) define
+// VARLEN_RANGES launch_attn_varlen_lse_ranges / _lse_bf16_ranges and VARLEN_LSE: their kernels take `lse` behind T, one more tuple element.
 #include "lc_plan.h"
 
 #ifndef VARLEN_RANGES
 #define VARLEN_RANGES launch_attn_varlen_ranges
+#endif
+#ifdef VARLEN_LSE
+#define VARLEN_LSE_ARG(a) std::make_tuple((a).lse)
+#else
+#define VARLEN_LSE_ARG(a) std::make_tuple()
 #endif
 
 namespace lc {
@@ -23,7 +29,7 @@ int launch_varlen(Kern kern, const DecodePlan& p, int S, const DecodePtrs& a, fl
   const int grid = c.B * c.Hkv * p.RB * S;   // (<= 2^31 - 1: check_attn_decode)
   const auto args = std::tuple_cat(std::make_tuple(a.Q, static_cast<const VARLEN_KV_T*>(a.K), static_cast<const VARLEN_KV_T*>(a.V), a.O, a.kv_len), varlen_mid(a),
                                    std::make_tuple(part_o, part_lse, c.H, c.Hkv, c.max_nq, p.Ncap, (c.flags & LC_ATTN_CAUSAL) ? 1 : 0, S, attn_scale_log2e(D), rows),
-                                   varlen_tail(c), std::make_tuple(c.window, a.sinks, a.cu_q, c.T));
+                                   varlen_tail(c), std::make_tuple(c.window, a.sinks, a.cu_q, c.T), VARLEN_LSE_ARG(a));
   return std::apply([&](auto... x) { return launch_attn_kernel(kern, dim3(grid), dim3(256), DecodeLds<D, RT>::kTotal, a.st, x...); }, args);
 }
 

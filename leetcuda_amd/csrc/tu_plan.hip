@@ -743,7 +743,7 @@ int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
   if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
   if (c.window < 0 || (c.window > 0 && !(c.flags & LC_ATTN_CAUSAL))) return LC_ERR_ARG;   // a window is a lower edge of the causal mask
-  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)) || (c.varlen && !a->cu_q))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
+  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)) || (c.varlen && !a->cu_q) || (c.lse && !a->lse))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
   if (c.H <= 0 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return LC_ERR_SHAPE;
   if (c.B <= 0 || c.Nq <= 0 || c.D <= 0) return LC_ERR_SHAPE;
   if (c.varlen && (c.T < 1 || c.max_nq > c.T)) return LC_ERR_SHAPE;   // (Nq IS max_nq: < 1 is refused above)
@@ -769,19 +769,35 @@ void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   static const char* const kLocal[] = {"attn_local_kernel", "attn_local_paged_kernel", "attn_local_paged_kv8_kernel"};
   static const char* const kVarlen[] = {"", "attn_varlen_paged_kernel", "attn_varlen_paged_kv8_kernel"};
   static const char* const kVarlenBf16[] = {"", "attn_varlen_paged_bf16_kernel", "attn_varlen_paged_kv8_bf16_kernel"};   // (DecodeCall::bf16: varlen only)
-  const char* kern = (p.call.bf16 ? kVarlenBf16 : p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
+  // (DecodeCall::lse: varlen only — the twin plan's name with "_lse" in it)
+  static const char* const kVarlenLse[] = {"", "attn_varlen_paged_lse_kernel", "attn_varlen_paged_kv8_lse_kernel"};
+  static const char* const kVarlenLseBf16[] = {"", "attn_varlen_paged_lse_bf16_kernel", "attn_varlen_paged_kv8_lse_bf16_kernel"};
+  const char* kern = (p.call.lse ? (p.call.bf16 ? kVarlenLseBf16 : kVarlenLse) : p.call.bf16 ? kVarlenBf16 : p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
   if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
     static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
     static const char* const kLocalChunk[] = {"attn_local_chunk_kernel", "attn_local_chunk_paged_kernel", "attn_local_chunk_paged_kv8_kernel"};
     static const char* const kVarlenChunk[] = {"", "attn_varlen_chunk_paged_kernel", "attn_varlen_chunk_paged_kv8_kernel"};
     static const char* const kVarlenChunkBf16[] = {"", "attn_varlen_chunk_paged_bf16_kernel", "attn_varlen_chunk_paged_kv8_bf16_kernel"};
-    const char* chunk = (p.call.bf16 ? kVarlenChunkBf16 : p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
+    static const char* const kVarlenChunkLse[] = {"", "attn_varlen_chunk_paged_lse_kernel", "attn_varlen_chunk_paged_kv8_lse_kernel"};
+    static const char* const kVarlenChunkLseBf16[] = {"", "attn_varlen_chunk_paged_lse_bf16_kernel", "attn_varlen_chunk_paged_kv8_lse_bf16_kernel"};
+    const char* chunk = (p.call.lse ? (p.call.bf16 ? kVarlenChunkLseBf16 : kVarlenChunkLse) : p.call.bf16 ? kVarlenChunkBf16 : p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
     if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", chunk, p.call.D, p.S);
     else snprintf(buf, buflen, "%s<%d>", chunk, p.call.D);
     return;
   }
   if (p.S > 1) snprintf(buf, buflen, "%s<%d,%d> x%d", kern, p.call.D, p.RT, p.S);   // (x KV ranges, + attn_decode_combine_kernel<D>)
   else snprintf(buf, buflen, "%s<%d,%d>", kern, p.call.D, p.RT);
+}
+
+// The merge of two attention states (lc_plan.h MergeCall): the statuses of the decode entries, in their order — a NULL pointer (cu_q may be one),
+// the shape, the alignment of the 16-byte lanes, the head dim.
+int check_attn_merge(const MergeCall& c, const MergePtrs& p) {
+  if (!p.Oa || !p.lse_a || !p.Ob || !p.lse_b || !p.Oout || !p.lse_out) return LC_ERR_ARG;
+  if (c.B < 1 || c.T < 1 || c.H < 1 || c.D <= 0) return LC_ERR_SHAPE;
+  if ((long)c.T * c.H > 0x7fffffffL) return LC_ERR_SHAPE;   // rows are counted in 32 bits by the grid
+  if (!aligned16(p.Oa) || !aligned16(p.Ob) || !aligned16(p.Oout)) return LC_ERR_SHAPE;
+  if (c.D != 64 && c.D != 128) return LC_ERR_HEADDIM;
+  return LC_OK;
 }
 
 // Append to the paged cache (lc_plan.h AppendCall).  The page geometry and the span bound are check_attn_decode's, so that every pool an append
