@@ -776,6 +776,94 @@ int lc_attn_merge_states_f16(const void* Oa, const float* lse_a, const void* Ob,
 int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out,
                               const int* cu_q, int B, int T, int H, int D, void* stream);
 
+/* EXTENSION: tree-structured speculative decoding on the ragged entries — a look-back visibility mask per query token, and per-token rotary
+ * positions (attn_varlen_tree.hip, rope_append_varlen_pos.hip).  The new tokens of a sequence are the nodes of a draft
+ * tree (Medusa, EAGLE, SpecInfer), appended to neighbouring cache slots: a node must see the prefix and its own ancestors, never its siblings,
+ * and its rotary position is prefix length + depth, not its slot.
+ * lc_attn_varlen_paged_tree_f16 / _tree_kv8 / _tree_bf16 / _tree_kv8_bf16 take the arguments of lc_attn_varlen_paged_lse_f16 / _lse_kv8 /
+ * _lse_bf16 / _lse_kv8_bf16 with `tree_mask` right behind lse:
+ *   tree_mask  device uint64 [T], 8-byte aligned: one word per token row of Q.  Token i of sequence b sits at cache slot p = L_b - Nq_b + i
+ *         (the clamps of the ragged entries).  The twin's rule is unchanged: key j is visible iff j <= p, and iff j > p - W when a window is
+ *         given.  The tree rule adds ONE condition: for d = p - j in [0, 64) the key is visible only if bit d of tree_mask[q0 + i] is set.
+ *         Bit 0 is the token's own key.  Keys with d >= 64 are not governed by the mask.
+ * A word of all ones is exactly the twin (same O and lse, bit for bit): an ordinary decoding or prefilling sequence of any Nq_b rides in the same
+ * ragged batch with all-ones words.  A tree of up to 64 draft tokens is fully described: the ancestors of token i are at most i <= 63 slots
+ * back.  A row whose mask hides every key behaves as "no visible key" does: O = 0 and lse = -inf, or the sink alone when sinks are given.
+ * `window` keeps counting cache slots, not tree depth.
+ * The checks, their order and the statuses are the twin's, with three additions: tree_mask == NULL among the NULL pointers (LC_ERR_ARG), a
+ * tree_mask off 8 bytes among the misaligned pointers (LC_ERR_SHAPE), and a call without LC_ATTN_CAUSAL refused where a window without
+ * LC_ATTN_CAUSAL is (LC_ERR_ARG).  The plan — RT, RB, S, grid, LDS — the workspace (lc_attn_varlen_paged_workspace_bytes / _kv8_workspace_bytes)
+ * and the capture rules are the twin's: the mask only removes keys from the tiles the twin walks.  The name calls report the twin's plan with
+ * "tree" in place of "lse": attn_varlen_paged_tree_kernel<D,RT>, attn_varlen_chunk_paged_kv8_tree_bf16_kernel<D>, ... (S > 1: + the twin's
+ * attn_varlen_combine_lse_kernel<D> / attn_varlen_combine_lse_bf16_kernel<D>).
+ * lc_rope_append_varlen_pos_f16 / _pos_kv8 / _pos_bf16 / _pos_kv8_bf16 take the arguments of lc_rope_append_varlen_f16 / _kv8 / _bf16 /
+ * _kv8_bf16 with `pos_ids` right behind cu_q:
+ *   pos_ids  device int32 [T]: the cos_sin row used for token t is clamp(pos_ids[t], 0, max_pos - 1).  Everything else is the twin's: the cache
+ *         slot p = L_b - Nq_b + i the token is written to, the p < 0 rule, dropped tokens, quantisation, strides and in-place Q.
+ *         pos_ids[t] = p for every token gives the twin's bytes.  pos_ids == NULL: LC_ERR_ARG.
+ * rope_append_varlen_pos_kernel<D,INTERLEAVED>, _pos_kv8_kernel, _pos_bf16_kernel, _pos_kv8_bf16_kernel.
+ * Not here: trees of more than 64 tokens; masks on the rectangular, contiguous-cache or lc_attn_fwd_* entries; tree forms without lse; a tree
+ * mask inside a cascade's prefix pass; compacting the accepted path's K / V after verification; M-RoPE (several position streams); a window
+ * counted in tree depth. */
+int lc_attn_varlen_paged_tree_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const uint64_t* tree_mask,
+                                  const int* cu_q, const int* block_table, const int* kv_len,
+                                  int B, int H, int Hkv, int T, int max_nq,
+                                  int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_tree_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                          int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_tree_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const uint64_t* tree_mask,
+                                  const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                                  int B, int H, int Hkv, int T, int max_nq,
+                                  int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_tree_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                              int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_tree_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const uint64_t* tree_mask,
+                                   const int* cu_q, const int* block_table, const int* kv_len,
+                                   int B, int H, int Hkv, int T, int max_nq,
+                                   int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_tree_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                               int flags, char* buf, int buflen);
+int lc_attn_varlen_paged_tree_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const uint64_t* tree_mask,
+                                       const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
+                                       int B, int H, int Hkv, int T, int max_nq,
+                                       int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_varlen_paged_tree_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window,
+                                                   int flags, char* buf, int buflen);
+int lc_rope_append_varlen_pos_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                  const float* cos_sin, const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len,
+                                  int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                                  int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_pos_kv8(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8,
+                                  const float* cos_sin, const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len,
+                                  const float* k_scale, const float* v_scale,
+                                  int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                                  int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_pos_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
+                                   const float* cos_sin, const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len,
+                                   int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                                   int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_pos_kv8_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8,
+                                       const float* cos_sin, const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len,
+                                       const float* k_scale, const float* v_scale,
+                                       int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                                       int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream);
+int lc_rope_append_varlen_pos_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                          int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                          char* buf, int buflen);
+int lc_rope_append_varlen_pos_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                              int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                              char* buf, int buflen);
+int lc_rope_append_varlen_pos_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                               int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                               char* buf, int buflen);
+int lc_rope_append_varlen_pos_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D,
+                                                   int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
+                                                   char* buf, int buflen);
+
 /* EXTENSION (BASELINE config 5 "FFPA-style QKV fine-grained tiling D=512 bf16"; the reference has no bf16
  * entry): the large-head-dim d-slice tiling kernel on bfloat16 Q,K,V,O [B,H,N,D], D in {256, 512}. */
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

@@ -39,7 +39,11 @@ AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_a
                     "tu_rope_append_varlen_bf16": "isa_audit_rope_append_varlen_bf16.json",
                     "tu_attn_varlen_paged_lse": "isa_audit_varlen_paged_lse.json", "tu_attn_varlen_paged_kv8_lse": "isa_audit_varlen_paged_kv8_lse.json",
                     "tu_attn_varlen_paged_lse_bf16": "isa_audit_varlen_paged_lse_bf16.json",
-                    "tu_attn_varlen_paged_kv8_lse_bf16": "isa_audit_varlen_paged_kv8_lse_bf16.json", "tu_attn_merge": "isa_audit_merge.json"}
+                    "tu_attn_varlen_paged_kv8_lse_bf16": "isa_audit_varlen_paged_kv8_lse_bf16.json", "tu_attn_merge": "isa_audit_merge.json",
+                    "tu_attn_varlen_paged_tree": "isa_audit_varlen_paged_tree.json", "tu_attn_varlen_paged_kv8_tree": "isa_audit_varlen_paged_kv8_tree.json",
+                    "tu_attn_varlen_paged_tree_bf16": "isa_audit_varlen_paged_tree_bf16.json",
+                    "tu_attn_varlen_paged_kv8_tree_bf16": "isa_audit_varlen_paged_kv8_tree_bf16.json",
+                    "tu_rope_append_varlen_pos": "isa_audit_rope_append_varlen_pos.json"}
 
 
 def _newer(target: Path, sources) -> bool:

@@ -116,6 +116,24 @@ SYMBOLS = {
     "lc_attn_varlen_paged_lse_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
     "lc_attn_varlen_paged_lse_kv8_bf16": (_i, [_vp] * 10 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_varlen_paged_lse_kv8_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    # the ragged entries with a look-back visibility mask: their lse twins with `tree_mask` right behind lse (the workspace queries above serve them)
+    "lc_attn_varlen_paged_tree_f16": (_i, [_vp] * 9 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_tree_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_tree_kv8": (_i, [_vp] * 11 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_tree_kv8_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_tree_bf16": (_i, [_vp] * 9 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_tree_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_varlen_paged_tree_kv8_bf16": (_i, [_vp] * 11 + [_i] * 10 + [_vp, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_varlen_paged_tree_kv8_bf16_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    # the ragged rope + append entries with per-token rotary positions: their twins with `pos_ids` right behind cu_q
+    "lc_rope_append_varlen_pos_f16": (_i, [_vp] * 11 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_pos_kv8": (_i, [_vp] * 13 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_pos_bf16": (_i, [_vp] * 11 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_pos_kv8_bf16": (_i, [_vp] * 13 + [_i] * 11 + [C.c_longlong, C.c_longlong, _i, _vp]),
+    "lc_rope_append_varlen_pos_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_varlen_pos_kv8_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_varlen_pos_bf16_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
+    "lc_rope_append_varlen_pos_kv8_bf16_kernel_name": (_i, [_i] * 10 + [C.c_longlong, C.c_longlong, _i, _cp, _i]),
     # merge of two (O, lse) states: Oa, lse_a, Ob, lse_b, Oout, lse_out, cu_q (or NULL), B, T, H, D, stream
     "lc_attn_merge_states_f16": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
     "lc_attn_merge_states_bf16": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
@@ -1097,22 +1115,31 @@ def _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_tabl
 
 
 def _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, kv8,
-                        bf16=False):
+                        bf16=False, pos_ids=None):
     import torch
     args = _rope_varlen_args(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, k_scale, v_scale, kv8, bf16)
+    pos = ()
+    if pos_ids is not None:      # the _pos_ entries: the rotary position of every token, behind cu_q
+        if pos_ids.dtype != torch.int32:
+            raise TypeError(f"pos_ids must be int32, got {pos_ids.dtype}")
+        if tuple(pos_ids.shape) != (q.shape[0],):
+            _shape_err(f"pos_ids {tuple(pos_ids.shape)} for q {tuple(q.shape)}: [T] expected")
+        pos = (pos_ids,)
     for t in (q, k_new, v_new):      # (views into a projection output are not contiguous: the kernel strides)
         if not t.is_cuda:
             raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
     if q_out is None:
         q_out = torch.empty((args[3], args[1], args[8]), dtype=q.dtype, device=q.device)
-    _need_gpu(q_out, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
+    _need_gpu(q_out, k_pool, v_pool, cos_sin, cu_q, *pos, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
     scale_ptrs = [_ptr(s) if s is not None else None for s in (k_scale, v_scale)] if kv8 else []
+    stem = "lc_rope_append_varlen_pos_" if pos else "lc_rope_append_varlen_"
     if bf16:
-        symbol = "lc_rope_append_varlen_kv8_bf16" if kv8 else "lc_rope_append_varlen_bf16"
+        symbol = stem + ("kv8_bf16" if kv8 else "bf16")
     else:
-        symbol = "lc_rope_append_varlen_kv8" if kv8 else "lc_rope_append_varlen_f16"
+        symbol = stem + ("kv8" if kv8 else "f16")
     check(getattr(load(), symbol)(_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(q_out), _ptr(k_pool), _ptr(v_pool), _ptr(cos_sin), _ptr(cu_q),
-                                  _ptr(block_table), _ptr(kv_len), *scale_ptrs, *args, ROPE_INTERLEAVED if interleaved else 0, _stream()), symbol)
+                                  *(_ptr(t) for t in pos), _ptr(block_table), _ptr(kv_len), *scale_ptrs, *args, ROPE_INTERLEAVED if interleaved else 0,
+                                  _stream()), symbol)
     return q_out
 
 
@@ -1234,7 +1261,9 @@ def _lse_out(q, lse):
     return lse
 
 
-def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, kv8, bf16):
+def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, kv8, bf16,
+                tree=None):
+    """the four lse calls and, with `tree` (an int64 [T] tensor of look-back words), the four tree calls: the same checks, `tree` behind lse"""
     import torch
     el, el_name = (torch.bfloat16, "bfloat16") if bf16 else (torch.half, "float16")
     fp8 = (torch.float8_e4m3fn, torch.uint8)
@@ -1258,10 +1287,18 @@ def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_
         scales = (_ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None)
     local = _varlen_local(q, window, sinks)
     lse = _lse_out(q, lse)
-    _need_gpu(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if kv8 and s is not None))
-    symbol = "lc_attn_varlen_paged_lse_" + (("kv8_bf16" if bf16 else "kv8") if kv8 else ("bf16" if bf16 else "f16"))
-    check(getattr(load(), symbol)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(lse), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *scales, *dims,
-                                  *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), symbol)
+    masks = ()
+    if tree is not None:
+        if tree.dtype != torch.int64:
+            raise TypeError(f"tree_mask must be int64 (the bits of a uint64 word), got {tree.dtype}")
+        if tuple(tree.shape) != (q.shape[0],) or not tree.is_contiguous():
+            _shape_err(f"tree_mask {tuple(tree.shape)} for q {tuple(q.shape)}: contiguous [T] expected")
+        masks = (tree,)
+    _need_gpu(q, k_pool, v_pool, o, lse, *masks, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if kv8 and s is not None))
+    symbol = ("lc_attn_varlen_paged_lse_" if tree is None else "lc_attn_varlen_paged_tree_") + (("kv8_bf16" if bf16 else "kv8") if kv8 else ("bf16" if bf16 else "f16"))
+    check(getattr(load(), symbol)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(lse), *(_ptr(t) for t in masks), _ptr(cu_q), _ptr(block_table),
+                                  _ptr(kv_len), *scales, *dims, *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace),
+                                  _stream()), symbol)
     return o, lse
 
 
@@ -1294,6 +1331,162 @@ def attn_varlen_paged_lse_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages
     "attn_varlen_paged_lse_kernel<D,RT>", "attn_varlen_chunk_paged_kv8_lse_bf16_kernel<D>", + " xS" with S > 1."""
     symbol = "lc_attn_varlen_paged_lse_" + ("kv8_" if kv8 else "") + ("bf16_" if bf16 else "") + "kernel_name"
     return _decode_kernel_name(symbol, B, H, Hkv, T, max_nq, page_size, max_pages, D, window, causal=causal)
+
+
+# Tree-structured speculative decoding on the ragged calls (lc_attn_varlen_paged_tree_*, lc_rope_append_varlen_pos_*; DESIGN.md section 4.3o): the
+# new tokens of a sequence are the nodes of a draft tree in neighbouring cache slots.  tree_mask is int64 [T], the bits of one uint64 look-back
+# word per token: bit d lets the token at slot p see key p - d (d < 64; keys further back are not governed); pos_ids is int32 [T], the rotary
+# position of every token.  tree_mask() and tree_positions() build both on the host from each sequence's parent array.
+
+def attn_varlen_paged_tree(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, window=0, sinks=None, workspace=None):
+    """attn_varlen_paged_lse under a look-back visibility mask (lc_attn_varlen_paged_tree_f16), always causal: tree_mask DEVICE int64 [T], one word
+    per token row of q; the token at cache slot p sees key j <= p (j > p - window) with d = p - j >= 64, or with bit d of its word set.  A word
+    of all ones (-1) is attn_varlen_paged_lse(causal=True), bit for bit.  Plan and workspace are attn_varlen_paged's.  Returns (o, lse)."""
+    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, True, window, sinks, workspace, False, False, tree_mask)
+
+
+def attn_varlen_paged_kv8_tree(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, k_scale=None, v_scale=None, window=0,
+                               sinks=None, workspace=None):
+    """attn_varlen_paged_tree over fp8 pools (lc_attn_varlen_paged_tree_kv8)."""
+    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, True, window, sinks, workspace, True, False,
+                       tree_mask)
+
+
+def attn_varlen_paged_tree_bf16(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, window=0, sinks=None, workspace=None):
+    """attn_varlen_paged_tree with bfloat16 q, o and pools (lc_attn_varlen_paged_tree_bf16); lse stays float32."""
+    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, True, window, sinks, workspace, False, True, tree_mask)
+
+
+def attn_varlen_paged_kv8_tree_bf16(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, k_scale=None, v_scale=None,
+                                    window=0, sinks=None, workspace=None):
+    """attn_varlen_paged_kv8_tree with bfloat16 q, o (lc_attn_varlen_paged_tree_kv8_bf16)."""
+    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, True, window, sinks, workspace, True, True,
+                       tree_mask)
+
+
+def attn_varlen_paged_tree_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=True, window=0, kv8=False, bf16=False) -> str:
+    """attn_varlen_paged_lse_kernel_name's plan with `tree` in place of `lse`: "attn_varlen_paged_tree_kernel<D,RT>",
+    "attn_varlen_chunk_paged_kv8_tree_bf16_kernel<D>", + " xS" with S > 1.  (causal=False: the call is refused, as the run call would be)"""
+    symbol = "lc_attn_varlen_paged_tree_" + ("kv8_" if kv8 else "") + ("bf16_" if bf16 else "") + "kernel_name"
+    return _decode_kernel_name(symbol, B, H, Hkv, T, max_nq, page_size, max_pages, D, window, causal=causal)
+
+
+def attn_varlen_paged_kv8_tree_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=True, window=0) -> str:
+    return attn_varlen_paged_tree_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal, window, kv8=True)
+
+
+def attn_varlen_paged_tree_bf16_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=True, window=0) -> str:
+    return attn_varlen_paged_tree_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal, window, bf16=True)
+
+
+def attn_varlen_paged_kv8_tree_bf16_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=True, window=0) -> str:
+    return attn_varlen_paged_tree_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal, window, kv8=True, bf16=True)
+
+
+def rope_append_varlen_pos(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, pos_ids, block_table, kv_len, max_nq, q_out=None, interleaved=False):
+    """rope_append_varlen with the rotary position of every token stated (lc_rope_append_varlen_pos_f16): pos_ids DEVICE int32 [T]; token t is
+    rotated by row clamp(pos_ids[t], 0, max_pos - 1) of cos_sin and still written to its cache slot kv_len[b] - Nq_b + i.  pos_ids = the slots
+    gives rope_append_varlen's bytes."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, None, None, False,
+                               False, pos_ids)
+
+
+def rope_append_varlen_pos_kv8(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, pos_ids, block_table, kv_len, max_nq, q_out=None, interleaved=False,
+                               k_scale=None, v_scale=None):
+    """rope_append_varlen_pos into fp8 pools (lc_rope_append_varlen_pos_kv8)."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, True,
+                               False, pos_ids)
+
+
+def rope_append_varlen_pos_bf16(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, pos_ids, block_table, kv_len, max_nq, q_out=None, interleaved=False):
+    """rope_append_varlen_pos with bfloat16 sources, pools and q_out (lc_rope_append_varlen_pos_bf16)."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool, v_pool, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, None, None, False,
+                               True, pos_ids)
+
+
+def rope_append_varlen_pos_kv8_bf16(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, pos_ids, block_table, kv_len, max_nq, q_out=None,
+                                    interleaved=False, k_scale=None, v_scale=None):
+    """rope_append_varlen_pos_bf16 into fp8 pools (lc_rope_append_varlen_pos_kv8_bf16)."""
+    return _rope_varlen_launch(q, k_new, v_new, k_pool8, v_pool8, cos_sin, cu_q, block_table, kv_len, max_nq, q_out, interleaved, k_scale, v_scale, True,
+                               True, pos_ids)
+
+
+def rope_append_varlen_pos_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, interleaved=False, kv8=False, bf16=False,
+                                       q_row_stride=None, kv_row_stride=None) -> str:
+    """"rope_append_varlen_pos_kernel<D,INTERLEAVED>" / "_pos_kv8_kernel" / "_pos_bf16_kernel" / "_pos_kv8_bf16_kernel" (strides None: dense)."""
+    symbol = "lc_rope_append_varlen_pos_" + ("kv8_" if kv8 else "") + ("bf16_" if bf16 else "") + "kernel_name"
+    buf = C.create_string_buffer(128)
+    check(getattr(load(), symbol)(B, H, Hkv, T, max_nq, page_size, max_pages, D, rot_dim, max_pos, H * D if q_row_stride is None else q_row_stride,
+                                  Hkv * D if kv_row_stride is None else kv_row_stride, ROPE_INTERLEAVED if interleaved else 0, buf, 128), symbol)
+    return buf.value.decode()
+
+
+TREE_MAX_TOKENS = 64      # a look-back word has 64 bits: the ancestors of token i of a tree are at most i <= 63 slots back
+
+
+def _tree_host(parents, cu_q):
+    """(list of python ints cu_q, device of cu_q or None) after the checks tree_mask and tree_positions share"""
+    import torch
+    dev = cu_q.device if isinstance(cu_q, torch.Tensor) else None
+    cu = [int(x) for x in (cu_q.tolist() if isinstance(cu_q, torch.Tensor) else cu_q)]
+    if len(cu) != len(parents) + 1:
+        raise ValueError(f"{len(parents)} sequences need {len(parents) + 1} entries of cu_q, got {len(cu)}")
+    if cu[0] < 0 or any(b < a for a, b in zip(cu, cu[1:])):
+        raise ValueError(f"cu_q must start at >= 0 and not decrease, got {cu}")
+    for b, par in enumerate(parents):
+        if par is None:
+            continue
+        par = [int(x) for x in par]
+        if len(par) > TREE_MAX_TOKENS:
+            raise ValueError(f"sequence {b}: a tree of {len(par)} tokens (at most {TREE_MAX_TOKENS} fit a 64-bit look-back word)")
+        if len(par) != cu[b + 1] - cu[b]:
+            raise ValueError(f"sequence {b}: {len(par)} parents for {cu[b + 1] - cu[b]} tokens")
+        for i, a in enumerate(par):
+            if not -1 <= a < i:
+                raise ValueError(f"sequence {b}: parents[{i}] = {a} (an earlier token of the tree, or -1 for the prefix, is expected)")
+    return cu, dev
+
+
+def tree_mask(parents, cu_q):
+    """The look-back words of a ragged batch for attn_varlen_paged_tree*: int64 [T], T = cu_q[B], on cu_q's device (a host sequence: the CPU).
+    parents has one entry per sequence: None = an ordinary decoding or prefilling sequence (all ones), else the parent of each of its tokens —
+    parents[i] < i an earlier token of the tree, -1 the prefix; at most 64 tokens (ValueError).  Bit d of row i is set iff token i - d is i
+    itself or an ancestor of i, or d > i (the prefix).  Rows in front of cu_q[0] are all ones.  No kernel runs."""
+    import torch
+    cu, dev = _tree_host(parents, cu_q)
+    words = [-1] * cu[-1]
+    for b, par in enumerate(parents):
+        if par is None:
+            continue
+        for i in range(len(par)):
+            w = (~0 << (i + 1)) & 0xFFFFFFFFFFFFFFFF     # the prefix: every key more than i slots back
+            a = i
+            while a >= 0:
+                w |= 1 << (i - a)
+                a = int(par[a])
+            words[cu[b] + i] = w - (1 << 64) if w >> 63 else w     # the same bits as a signed 64-bit value
+    out = torch.tensor(words, dtype=torch.int64)
+    return out.to(dev) if dev is not None else out
+
+
+def tree_positions(parents, cu_q, kv_len):
+    """The rotary positions of a ragged batch for rope_append_varlen_pos*: int32 [T], T = cu_q[B], on cu_q's device.  kv_len[b] is the length
+    AFTER the step's append.  A tree sequence (parents as tree_mask's): (kv_len[b] - Nq_b) + depth of token i, a child of the prefix having depth
+    0; an ordinary sequence (None): the token's cache slot kv_len[b] - Nq_b + i.  Rows in front of cu_q[0] are 0.  No kernel runs."""
+    import torch
+    cu, dev = _tree_host(parents, cu_q)
+    lens = [int(x) for x in (kv_len.tolist() if isinstance(kv_len, torch.Tensor) else kv_len)]
+    if len(lens) != len(parents):
+        raise ValueError(f"{len(parents)} sequences need {len(parents)} entries of kv_len, got {len(lens)}")
+    pos = [0] * cu[-1]
+    for b, par in enumerate(parents):
+        nq = cu[b + 1] - cu[b]
+        depth = []
+        for i in range(nq):
+            depth.append(i if par is None else (0 if int(par[i]) < 0 else depth[int(par[i])] + 1))
+            pos[cu[b] + i] = lens[b] - nq + depth[i]
+    out = torch.tensor(pos, dtype=torch.int32)
+    return out.to(dev) if dev is not None else out
 
 
 def attn_merge_states(o_a, lse_a, o_b, lse_b, out=None, lse_out=None, cu_q=None):

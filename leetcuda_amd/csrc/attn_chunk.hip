@@ -34,6 +34,8 @@ __global__ __launch_bounds__(256) void attn_chunk_kernel(const half_t* __restric
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -59,6 +61,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kernel(const half_t* __r
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -86,6 +90,8 @@ __global__ __launch_bounds__(256) void attn_chunk_paged_kv8_kernel(const half_t*
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

@@ -23,6 +23,8 @@
 // The body is shared with the paged-cache kernel (attn_decode_paged.hip), which replaces the address of a key row and nothing else,
 // and with the fp8-cache kernel (attn_decode_paged_kv8.hip, §4.3g), which loads bytes and converts them in registers.
 #pragma once
+#include <type_traits>
+
 #include "lc_common.h"
 
 namespace lc {
@@ -83,6 +85,11 @@ struct DecodeLse {
   float* lse;   // device float[rows of O]: ln(sum over the row's visible keys of exp(score), the sink included); -inf: no key, no sink
 };
 
+// A look-back visibility mask per query token (attn_varlen_tree.hip).  Every other kernel leaves the field unused.
+struct DecodeTree {
+  const uint64_t* mask;   // device uint64[T]: bit d of word t lets token t, at cache slot p, see key p - d (d < 64); keys 64 or more slots back are not governed
+};
+
 // eight e4m3 bytes (a: bytes 0 .. 3, b: bytes 4 .. 7, memory order) as eight fp16 values, element i = byte i: one v_cvt_scalef32_pk_f16_fp8 per two
 // elements, scale 1.0 — every e4m3 value is an fp16 value (the smallest, 2^-9, a normal one), so the conversion is exact; 0x7f / 0xff give NaN
 LC_DEVINL u32x4_t kv8_half8(uint32_t a, uint32_t b) {
@@ -132,6 +139,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const half_t* __restri
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

@@ -29,6 +29,16 @@
 // attn_varlen_lse.hip; DESIGN.md §4.3n): where wave 0 stores a row's O (S == 1) its h == 0 lanes also store the row's log-sum-exp in NATURAL
 // units, ls.lse[row] with the global row of O and O's row guard.  The S > 1 path is untouched: part_lse always carried it, and the combine
 // kernel of an LSE plan stores it.  With LSE = false nothing changes: every other kernel's code does not depend on the parameter (§4.3n compares it).
+// A `constexpr bool TREE` with a `const DecodeTree tr` (TREE = false: unused) follows it.  TREE = true (the attn_varlen_*_tree*_kernel of
+// attn_varlen_tree.hip; DESIGN.md §4.3o): every query token carries a 64-bit look-back word, and key j of the row at slot p = lim - 1 is visible
+// only if the compare below holds AND, for d = p - j < 64, bit d of the word is set; keys 64 or more slots back are not governed.  The mask only
+// REMOVES keys: Lw, tile_lo, the range partition, the page ids and the source clamps do not know it.  A row's word sits in the padding of its
+// Q row in LDS (no more LDS, no register across the loop), and a step whose every key lies 64 or more slots below the workgroup's lowest row
+// slot takes the unmasked select through ONE wave-uniform branch per step: the scores and the softmax of a step are a text of their own
+// (attn_decode_scores.inc) that a TREE kernel includes twice, with the bit test and without, so that either side of the branch stays one
+// straight run of code (a branch per row tile cost the four-row-tile kernels 24 % on EVERY tile: hipcc no longer ran a row tile's MFMAs
+// under the softmax of the one before).  With TREE = false the text is included once, where it stood: every other kernel's code does not
+// depend on the parameter (§4.3o compares it).
   using L = DecodeLds<D, RT>;
   constexpr int KS = D / 32;    // k-steps of Sᵀ = K Qᵀ
   constexpr int DB = D / 16;    // 16-wide blocks of d
@@ -125,6 +135,11 @@
       *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Q + vrow(rs) * D + ch * 8);
     else
       *reinterpret_cast<u32x4_t*>(lds + r * L::kQStride + ch * 16) = *reinterpret_cast<const u32x4_t*>(Qg + (long)rs * D + ch * 8);
+    // TREE: the row's look-back word travels with its Q row, in the first 8 of the row's 16 padding bytes (token q0 + rs % Nqb < T: the clamps
+    // above; padding rows take row R - 1's, as they take its Q).  No register holds a word across the steps that do not test it
+    if constexpr (TREE) {
+      if (ch == 0) *reinterpret_cast<uint64_t*>(lds + r * L::kQStride + D * 2) = tr.mask[q0 + rs % Nqb];
+    }
   }
   __syncthreads();
 
@@ -140,6 +155,18 @@
   // LOCAL: key j is visible to a row iff lim - W <= j < lim, one unsigned compare of j - lim + W against W; no window is the widest one
   // (j - lim >= -(2^31 - 1): the sum does not wrap below 0)
   const unsigned wlo = LOCAL && lc.window > 0 ? (unsigned)lc.window : 0x7fffffffu;
+  // TREE: the lowest key ANY row of the workgroup has a bit for: tree_lo = p_min - 63 with p_min the slot of the workgroup's lowest token (i_min
+  // as for LOCAL: 0 unless a row block lies inside one head).  A step below it does not look at the words
+  int tree_lo = 0;
+  if constexpr (TREE) {
+    int imin = 0;
+    if constexpr (CHUNK) {
+      const int span = (R - rbase < 64 ? R - rbase : 64) - 1;
+      const int i0 = __builtin_amdgcn_readfirstlane(rbase % Nqb);
+      imin = i0 + span >= Nqb ? 0 : i0;
+    }
+    tree_lo = Lb - Nqb + imin - 63;
+  }
 
   float m[RT], l[RT];
   f32x4_t o[RT][DB];
@@ -276,48 +303,20 @@
     const int k0 = key0(u) + 4 * h;
     half8_t pf[RT][NPS];
     float alpha[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      half8_t qf[KS];
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-        qf[s] = *reinterpret_cast<const half8_t*>(lds + (16 * rt + i16) * L::kQStride + (h * (D / 4) + 8 * s) * 2);
-      f32x4_t st[NKB];
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) acc = mfma16_16<BF16>(k_frag(kb, s), qf[s], acc);
-        st[kb] = acc;
+    // (the scores and the softmax of the step: attn_decode_scores.inc, included with a `constexpr bool MASKED` in scope.  TREE: ONE wave-uniform
+    // branch per step picks the text with the bit test or the text without it, each one straight run of code; every other kernel includes
+    // the text without it once, where the loop always stood)
+    if constexpr (TREE) {
+      if (key0(u) + STEP - 1 >= tree_lo) {   // some row of the workgroup has a bit for a key of the step
+        constexpr bool MASKED = true;
+#include "attn_decode_scores.inc"
+      } else {
+        constexpr bool MASKED = false;
+#include "attn_decode_scores.inc"
       }
-      float mx = DEC_NEG_INF;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          bool vis;   // select on the INDEX: the score may be anything
-          if constexpr (LOCAL) vis = (unsigned)(k0 + 16 * kb + r - lim[rt]) + wlo < wlo;
-          else vis = k0 + 16 * kb + r < lim[rt];
-          const float x = vis ? st[kb][r] * sc2 : DEC_NEG_INF;
-          st[kb][r] = x;
-          mx = fmaxf(mx, x);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mn = fmaxf(m[rt], mx);
-      const float mu = (mn == DEC_NEG_INF) ? 0.f : mn;   // no visible key yet: every exponent below is exp2(-inf) = 0
-      alpha[rt] = __builtin_amdgcn_exp2f(m[rt] - mu);
-      m[rt] = mn;
-      float ps = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __builtin_amdgcn_exp2f(st[kb][r] - mu);
-          ps += p;
-          pf[rt][kb >> 1][4 * (kb & 1) + r] = cvt16<BF16>(p);
-        }
-      l[rt] = l[rt] * alpha[rt] + ps;   // (this lane's keys of the step: the four lane groups of a row are summed once, behind the loop)
+    } else {
+      constexpr bool MASKED = false;
+#include "attn_decode_scores.inc"
     }
     // ---- the next tile's K and V loads into the registers that are free now: a whole tile in flight under the rest of the arithmetic (the
     // scheduling barrier keeps hipcc from hoisting them over the scores: that is what keeps the four-row-tile kernel inside the register file)

@@ -36,6 +36,8 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const half_t* __
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

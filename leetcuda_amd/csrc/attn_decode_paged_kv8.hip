@@ -42,6 +42,8 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kv8_kernel(const half_t
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

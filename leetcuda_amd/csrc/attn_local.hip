@@ -34,6 +34,8 @@ __global__ __launch_bounds__(256) void attn_local_kernel(const half_t* __restric
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -56,6 +58,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_kernel(const half_t* __r
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -80,6 +84,8 @@ __global__ __launch_bounds__(256) void attn_local_paged_kernel(const half_t* __r
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -106,6 +112,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kernel(const half_
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -133,6 +141,8 @@ __global__ __launch_bounds__(256) void attn_local_paged_kv8_kernel(const half_t*
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -160,6 +170,8 @@ __global__ __launch_bounds__(256) void attn_local_chunk_paged_kv8_kernel(const h
   const DecodeVarlen vl{};
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

@@ -41,6 +41,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kernel(const half_t* __
   const half_t* __restrict__ V = Vpool;
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -67,6 +69,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kernel(const half
   const half_t* __restrict__ V = Vpool;
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -94,6 +98,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_kernel(const half_t
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -122,6 +128,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_kernel(const 
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

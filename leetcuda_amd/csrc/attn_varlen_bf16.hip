@@ -34,6 +34,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_bf16_kernel(const half_
   const half_t* __restrict__ V = Vpool;
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -61,6 +63,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_bf16_kernel(const
   const half_t* __restrict__ V = Vpool;
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -89,6 +93,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_bf16_kernel(const h
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 
@@ -117,6 +123,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_bf16_kernel(c
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
   constexpr bool LSE = false;
   const DecodeLse ls{};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
 #include "attn_decode_body.inc"
 }
 

@@ -33,6 +33,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_lse_kernel(const half_t
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
 #include "attn_decode_body.inc"
@@ -60,6 +62,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_lse_kernel(const 
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
 #include "attn_decode_body.inc"
@@ -87,6 +91,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_lse_kernel(const ha
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   // (the body takes the pools as byte bases only: page_base)
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
@@ -116,6 +122,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_lse_kernel(co
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
 #include "attn_decode_body.inc"
@@ -144,6 +152,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_lse_bf16_kernel(const h
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
 #include "attn_decode_body.inc"
@@ -171,6 +181,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_lse_bf16_kernel(c
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = Kpool;
   const half_t* __restrict__ V = Vpool;
 #include "attn_decode_body.inc"
@@ -198,6 +210,8 @@ __global__ __launch_bounds__(256) void attn_varlen_paged_kv8_lse_bf16_kernel(con
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
 #include "attn_decode_body.inc"
@@ -223,6 +237,8 @@ __global__ __launch_bounds__(256) void attn_varlen_chunk_paged_kv8_lse_bf16_kern
   const DecodeLocal lc{window, sinks};
   const DecodeVarlen vl{cu_q, T_rows};
   const DecodeLse ls{lse};
+  constexpr bool TREE = false;
+  const DecodeTree tr{};
   const half_t* __restrict__ K = reinterpret_cast<const half_t*>(Kpool8);
   const half_t* __restrict__ V = reinterpret_cast<const half_t*>(Vpool8);
 #include "attn_decode_body.inc"

@@ -88,19 +88,21 @@ DecodeCall decode_local(DecodeCall c, int window, const float* sinks = nullptr) 
 // the lc_attn_varlen_paged_* entries: the paged local call of Nq = max_nq on T token-major rows
 // bf16: the lc_attn_varlen_paged_*bf16 entries — the same call on bfloat16 elements
 // lse: the lc_attn_varlen_paged_lse_* entries — the same call, which also writes each row's log-sum-exp
-DecodeCall decode_varlen(DecodeCall c, int T, bool bf16 = false, bool lse = false) {
+// tree: the lc_attn_varlen_paged_tree_* entries — the lse call with a look-back visibility word per query token
+DecodeCall decode_varlen(DecodeCall c, int T, bool bf16 = false, bool lse = false, bool tree = false) {
   c.varlen = true;
   c.T = T;
   c.max_nq = c.Nq;
   c.bf16 = bf16;
   c.lse = lse;
+  c.tree = tree;
   return c;
 }
 // block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local or varlen call, or nullptr; cu_q: a varlen call
 int decode_run(const DecodeCall& c, const void* Q, const void* K, const void* V, void* O, const int* kv_len, const int* block_table, const float* k_scale,
                const float* v_scale, void* workspace, size_t workspace_bytes, void* stream, const float* sinks = nullptr, const int* cu_q = nullptr,
-               float* lse = nullptr) {
-  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks, cu_q, lse};
+               float* lse = nullptr, const uint64_t* tree_mask = nullptr) {
+  const DecodePtrs a{static_cast<const half_t*>(Q), K, V, static_cast<half_t*>(O), kv_len, static_cast<hipStream_t>(stream), block_table, k_scale, v_scale, sinks, cu_q, lse, tree_mask};
   DecodePlan p;
   if (int rc = check_attn_decode(c, &a, &p)) return rc;
   if (workspace && (workspace_bytes < decode_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
@@ -164,23 +166,25 @@ int rope_run(const RopeAppendCall& c, const void* Q, const void* Knew, const voi
 }
 // the lc_rope_append_varlen_* entries: the rope call of Nq = max_nq on T token-major rows with a stride each
 RopeAppendCall rope_varlen_call(int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
-                                long long q_row_stride, long long kv_row_stride, int flags, int kv_bytes, bool bf16 = false) {
+                                long long q_row_stride, long long kv_row_stride, int flags, int kv_bytes, bool bf16 = false, bool pos = false) {
   RopeAppendCall c = rope_call(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, flags, kv_bytes);
   c.varlen = true;
   c.T = T;
   c.max_nq = max_nq;
   c.kv_row_stride = kv_row_stride;
   c.bf16 = bf16;   // the lc_rope_append_varlen_*bf16 entries
+  c.pos = pos;     // the lc_rope_append_varlen_pos_* entries
   return c;
 }
 int rope_varlen_run(const RopeAppendCall& c, const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
                     const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale,
-                    void* stream) {
+                    void* stream, const int* pos_ids = nullptr) {
   const RopeAppendPtrs p{AppendPtrs{static_cast<const half_t*>(Knew), static_cast<const half_t*>(Vnew), Kpool, Vpool, block_table, kv_len, k_scale, v_scale,
                                     static_cast<hipStream_t>(stream)},
-                         static_cast<const half_t*>(Q), static_cast<half_t*>(Qout), cos_sin, cu_q};
+                         static_cast<const half_t*>(Q), static_cast<half_t*>(Qout), cos_sin, cu_q, pos_ids};
   if (int rc = check_rope_append(c, &p)) return rc;
   if (int rc = launch_guard()) return rc;
+  if (c.pos) return launch_rope_append_varlen_pos(c, p);
   return c.bf16 ? launch_rope_append_varlen_bf16(c, p) : launch_rope_append_varlen(c, p);
 }
 int rope_name(const RopeAppendCall& c, char* buf, int buflen) {
@@ -627,6 +631,57 @@ int lc_attn_varlen_paged_lse_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, 
                      buflen);
 }
 
+// The varlen entries with a look-back visibility mask per query token: the four lse entries above with `tree_mask` right behind
+// lse, as a DecodeCall with lse = true and tree = true.  tree_mask joins the NULL and alignment checks and LC_ATTN_CAUSAL is required; the plan
+// and the workspace bytes are the twin's; the kernels and their names are the twin's with "tree" in place of "lse"
+int lc_attn_varlen_paged_tree_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
+    const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+    const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, false, true, true),
+                    Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
+}
+
+int lc_attn_varlen_paged_tree_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, false, true, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_tree_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
+    const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size,
+    int max_pages, int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, false, true, true),
+                    Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
+}
+
+int lc_attn_varlen_paged_tree_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, false, true, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_tree_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
+    const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+    const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, true, true, true),
+                    Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
+}
+
+int lc_attn_varlen_paged_tree_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, true, true, true), buf,
+                     buflen);
+}
+
+int lc_attn_varlen_paged_tree_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
+    const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size,
+    int max_pages, int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, true, true, true),
+                    Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
+}
+
+int lc_attn_varlen_paged_tree_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
+  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true, true, true), buf,
+                     buflen);
+}
+
 // The merge of two (O, lse) states over disjoint key sets (attn_merge.hip): merge_run above states a MergeCall
 int lc_attn_merge_states_f16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out, const int* cu_q, int B,
                              int T, int H, int D, void* stream) {
@@ -742,6 +797,68 @@ int lc_rope_append_varlen_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int
                                                long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
   return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true), buf,
                    buflen);
+}
+
+// the twins with per-token rotary positions: the same RopeAppendCall with pos = true and `pos_ids` right behind cu_q
+int lc_rope_append_varlen_pos_f16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool, const float* cos_sin,
+                                  const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq,
+                                  int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride,
+                                  long long kv_row_stride, int flags, void* stream) {
+  return rope_varlen_run(
+      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, false, true), Q,
+      Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream, pos_ids);
+}
+
+int lc_rope_append_varlen_pos_kv8(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8, const float* cos_sin,
+                                  const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len, const float* k_scale,
+                                  const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
+                                  int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
+  return rope_varlen_run(
+      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, false, true), Q,
+      Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream, pos_ids);
+}
+
+int lc_rope_append_varlen_pos_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool, const float* cos_sin,
+                                   const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len, int B, int H, int Hkv, int T,
+                                   int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride,
+                                   long long kv_row_stride, int flags, void* stream) {
+  return rope_varlen_run(
+      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true, true), Q,
+      Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream, pos_ids);
+}
+
+int lc_rope_append_varlen_pos_kv8_bf16(const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool8, void* Vpool8, const float* cos_sin,
+                                       const int* cu_q, const int* pos_ids, const int* block_table, const int* kv_len, const float* k_scale,
+                                       const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                                       int D, int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
+  return rope_varlen_run(
+      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true, true), Q,
+      Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream, pos_ids);
+}
+
+// (the name calls take no num_pages: it decides nothing)
+int lc_rope_append_varlen_pos_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                          long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, false, true),
+                   buf, buflen);
+}
+
+int lc_rope_append_varlen_pos_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                              long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, false, true),
+                   buf, buflen);
+}
+
+int lc_rope_append_varlen_pos_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
+                                               long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true, true),
+                   buf, buflen);
+}
+
+int lc_rope_append_varlen_pos_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim,
+                                                   int max_pos, long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
+  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true, true),
+                   buf, buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

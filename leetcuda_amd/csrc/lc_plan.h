@@ -165,6 +165,9 @@ struct DecodeCall {
                                          // kernels (and their names) and nothing else: every check and RT, RB, S, grid, LDS, workspace are the fp16 call's
   bool lse = false;                      // lc_attn_varlen_paged_lse_* (DESIGN.md §4.3n): the call also writes each row's log-sum-exp (varlen only).  It picks
                                          // the kernels (and their names) and adds DecodePtrs::lse to the NULL check; the plan and the workspace are the twin's
+  bool tree = false;                     // lc_attn_varlen_paged_tree_* (DESIGN.md §4.3o): a look-back visibility word per query token (lse calls only).  It picks
+                                         // the kernels (and their names), adds DecodePtrs::tree_mask to the NULL and alignment checks and requires
+                                         // LC_ATTN_CAUSAL; the plan and the workspace are the twin's
 };
 enum class DecodeCache { FLAT, PAGED, PAGED_KV8 };   // which kernel family reads the cache (indexes launch_attn_decode's table of range launchers)
 // ONE decision per decode-attention call and ONE path for the three cache kinds: an entry point (lc_abi.hip) states a DecodeCall, check_attn_decode
@@ -203,6 +206,7 @@ struct DecodePtrs {
   const float* sinks;               // a local or varlen call: device float[H] or nullptr = no sinks; else nullptr
   const int* cu_q = nullptr;        // a varlen call: device int32[B + 1]; else nullptr
   float* lse = nullptr;             // a call with DecodeCall::lse: device float[T H]; else nullptr
+  const uint64_t* tree_mask = nullptr;   // a call with DecodeCall::tree: device uint64[T]; else nullptr
 };
 // The checks of the three decode entry points, in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's
 // pointers (nullptr: a query call, which has none)
@@ -245,6 +249,13 @@ int launch_attn_varlen_combine_lse(const DecodePlan& p, int S, const DecodePtrs&
 template <DecodeCache C>
 int launch_attn_varlen_lse_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 int launch_attn_varlen_combine_lse_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
+// ... and of a varlen plan with a look-back visibility mask (DecodeCall::tree; always with lse): the same launcher on the attn_varlen_*_tree_kernel /
+// _tree_bf16_kernel, instantiated in tu_attn_varlen_paged_tree.hip / _paged_kv8_tree.hip / _paged_tree_bf16.hip / _paged_kv8_tree_bf16.hip; the
+// combine launches are the LSE plan's
+template <DecodeCache C>
+int launch_attn_varlen_tree_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+template <DecodeCache C>
+int launch_attn_varlen_tree_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 // What a caller of a state-merge entry states (lc_attn_merge_states_f16 / _bf16): two (O [T,H,D], lse [T H]) states over disjoint
 // key sets become the state over their union.  There is nothing to plan: attn_merge_states_kernel<D> / attn_merge_states_bf16_kernel<D> on
@@ -304,6 +315,8 @@ struct RopeAppendCall {
   long long kv_row_stride = 0;           // elements; Knew and Vnew
   bool bf16 = false;                     // lc_rope_append_varlen_*bf16: sources, Qout and 16-bit pools are bfloat16 (varlen only); it
                                          // picks rope_append_varlen_bf16_kernel / _kv8_bf16_kernel and nothing else
+  bool pos = false;                      // lc_rope_append_varlen_pos_* (DESIGN.md §4.3o): the cos_sin row of token t is pos_ids[t], not its cache slot (varlen
+                                         // only); it picks the rope_append_varlen_pos_*kernel and adds RopeAppendPtrs::pos_ids to the NULL check
 };
 struct RopeAppendPtrs {
   AppendPtrs a;
@@ -311,6 +324,7 @@ struct RopeAppendPtrs {
   half_t* Qout;                          // dense [B,H,Nq,D]; may be Q itself for a dense source
   const float* cos_sin;                  // device float[max_pos, rot_dim]
   const int* cu_q = nullptr;             // a varlen call: device int32[B + 1]; else nullptr
+  const int* pos_ids = nullptr;          // a call with RopeAppendCall::pos: device int32[T]; else nullptr
 };
 // The checks of the two entry points in the order that decides the status of a doubly-bad call; everything the append call shares is
 // check_kv_append's, so a pool geometry that append accepts is accepted here.  p: the run call's pointers (nullptr: a name call)
@@ -318,6 +332,7 @@ int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p);
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen);   // "rope_append_paged_kernel<128,false>" / "rope_append_paged_kv8_kernel<64,true>"
 int launch_rope_append(const RopeAppendCall& c, const RopeAppendPtrs& p);  // tu_rope_append.hip; checked arguments; a varlen call: ...
 int launch_rope_append_varlen(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen.hip; with bf16 elements: ...
-int launch_rope_append_varlen_bf16(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen_bf16.hip
+int launch_rope_append_varlen_bf16(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen_bf16.hip; with pos_ids, fp16 or bf16: ...
+int launch_rope_append_varlen_pos(const RopeAppendCall& c, const RopeAppendPtrs& p);    // ... tu_rope_append_varlen_pos.hip
 
 }  // namespace lc

@@ -17,13 +17,15 @@ namespace lc {
 
 // BF16 (rope_append_varlen_bf16.hip): the 16-bit elements are bfloat16 — rope_rotate8_bf16 and kv8_quantize8_bf16 in place of
 // rope_rotate8 and kv8_quantize8, nothing else
-template <int D, bool INTERLEAVED, bool KV8, bool BF16 = false>
+// POS (rope_append_varlen_pos.hip): the cos_sin row of token t is pos_ids[t] (device int32[T]) under the same clamp, not the
+// cache slot p; where the token is written, the p < 0 rule and the drop rules keep following p
+template <int D, bool INTERLEAVED, bool KV8, bool BF16 = false, bool POS = false>
 LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew, half_t* Qout,
                                        void* __restrict__ Kpool, void* __restrict__ Vpool, const float* __restrict__ cos_sin,
                                        const int* __restrict__ cu_q, const int* __restrict__ block_table, const int* __restrict__ kv_len,
                                        const float* __restrict__ k_scale, const float* __restrict__ v_scale, int B, int H, int Hkv, int T,
                                        int max_nq, int num_pages, int lps, int max_pages, int nblk, int rot_dim, int max_pos,
-                                       long long q_row_stride, long long kv_row_stride) {
+                                       long long q_row_stride, long long kv_row_stride, const int* __restrict__ pos_ids = nullptr) {
   constexpr int LPR = D / 8, TPB = 256 / LPR;   // lanes per row, tokens per workgroup
   // uniform: the role, the head and the token block of this workgroup
   const unsigned blk0 = __builtin_amdgcn_workgroup_id_x(), tid = __builtin_amdgcn_workitem_id_x();
@@ -52,7 +54,9 @@ LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict
   const int p = L - nqb + i;
   const size_t rowq = (size_t)t * (size_t)q_row_stride + (size_t)h * D, rowkv = (size_t)t * (size_t)kv_row_stride + (size_t)h * D;
   const unsigned cp = rope_partner_chunk<INTERLEAVED>(c, rot_dim);   // the partner chunk of the same row
-  const float* cs = cos_sin + (size_t)min(max(p, 0), max_pos - 1) * (unsigned)rot_dim;   // the row read is clamped: nothing outside the table
+  int rp = p;   // the rotary position (POS: the caller's, read only for an owned token t < T)
+  if constexpr (POS) rp = pos_ids[t];
+  const float* cs = cos_sin + (size_t)min(max(rp, 0), max_pos - 1) * (unsigned)rot_dim;   // the row read is clamped: nothing outside the table
   if (isq) {
     u32x4_t* dst = reinterpret_cast<u32x4_t*>(Qout + ((size_t)t * (unsigned)H + h) * D + c * 8);
     if (p < 0) {                                                 // more tokens than keys: no visible key, a defined value

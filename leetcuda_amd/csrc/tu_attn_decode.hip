@@ -41,6 +41,11 @@ constexpr DecodeRanges kVarlenLseRanges[] = {nullptr, launch_attn_varlen_lse_ran
                                              launch_attn_varlen_lse_ranges<DecodeCache::PAGED_KV8>};
 constexpr DecodeRanges kVarlenLseBf16Ranges[] = {nullptr, launch_attn_varlen_lse_bf16_ranges<DecodeCache::PAGED>,
                                                  launch_attn_varlen_lse_bf16_ranges<DecodeCache::PAGED_KV8>};
+// ... with a look-back visibility mask per query token (tu_attn_varlen_paged*_tree*.hip); tree implies lse: the combine launches are the LSE plan's
+constexpr DecodeRanges kVarlenTreeRanges[] = {nullptr, launch_attn_varlen_tree_ranges<DecodeCache::PAGED>,
+                                              launch_attn_varlen_tree_ranges<DecodeCache::PAGED_KV8>};
+constexpr DecodeRanges kVarlenTreeBf16Ranges[] = {nullptr, launch_attn_varlen_tree_bf16_ranges<DecodeCache::PAGED>,
+                                                  launch_attn_varlen_tree_bf16_ranges<DecodeCache::PAGED_KV8>};
 
 template <int D>
 int launch_decode_combine(long rows, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
@@ -67,7 +72,7 @@ int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace
   const long rows = (long)decode_rows(p.call);
   float* part_o = S > 1 ? part : nullptr;
   float* part_lse = S > 1 ? part + (size_t)S * rows * p.call.D : nullptr;
-  const int rc = (p.call.lse ? (p.call.bf16 ? kVarlenLseBf16Ranges : kVarlenLseRanges) : p.call.bf16 ? kVarlenBf16Ranges : p.call.varlen ? kVarlenRanges : p.local ? kLocalRanges : p.RB > 1 ? kChunkRanges : kDecodeRanges)[(int)p.cache](p, S, a, part_o, part_lse);
+  const int rc = (p.call.tree ? (p.call.bf16 ? kVarlenTreeBf16Ranges : kVarlenTreeRanges) : p.call.lse ? (p.call.bf16 ? kVarlenLseBf16Ranges : kVarlenLseRanges) : p.call.bf16 ? kVarlenBf16Ranges : p.call.varlen ? kVarlenRanges : p.local ? kLocalRanges : p.RB > 1 ? kChunkRanges : kDecodeRanges)[(int)p.cache](p, S, a, part_o, part_lse);
   if (rc != LC_OK || S == 1) return rc;
   if (p.call.lse) return p.call.bf16 ? launch_attn_varlen_combine_lse_bf16(p, S, a, part_o, part_lse) : launch_attn_varlen_combine_lse(p, S, a, part_o, part_lse);
   if (p.call.bf16) return launch_attn_varlen_combine_bf16(p, S, a, part_o, part_lse);

@@ -8,12 +8,16 @@
 // The two bf16 units (tu_attn_varlen_paged_bf16.hip, _paged_kv8_bf16.hip) define VARLEN_RANGES launch_attn_varlen_bf16_ranges and get that one
 // instead: the same arguments, grid and LDS size on their own kernels.  The four LSE units (tu_attn_varlen_paged*_lse*.hip) define
 // VARLEN_RANGES launch_attn_varlen_lse_ranges / _lse_bf16_ranges and VARLEN_LSE: their kernels take `lse` behind T, one more tuple element.
+// The four tree units (tu_attn_varlen_paged*_tree*.hip) define VARLEN_RANGES launch_attn_varlen_tree_ranges / _tree_bf16_ranges
+// and VARLEN_TREE: their kernels take `lse` and `tree_mask` behind T, two more tuple elements.
 #include "lc_plan.h"
 
 #ifndef VARLEN_RANGES
 #define VARLEN_RANGES launch_attn_varlen_ranges
 #endif
-#ifdef VARLEN_LSE
+#if defined(VARLEN_TREE)
+#define VARLEN_LSE_ARG(a) std::make_tuple((a).lse, (a).tree_mask)
+#elif defined(VARLEN_LSE)
 #define VARLEN_LSE_ARG(a) std::make_tuple((a).lse)
 #else
 #define VARLEN_LSE_ARG(a) std::make_tuple()

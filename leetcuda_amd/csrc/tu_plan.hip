@@ -742,8 +742,8 @@ int plan_attn_decode(const Knobs& k, const DecodeCall& c, DecodePlan* p) {
 }
 int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
   if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;   // (LC_ATTN_V_TRANSPOSED: a cache grows along N, there is no [D,N] cache)
-  if (c.window < 0 || (c.window > 0 && !(c.flags & LC_ATTN_CAUSAL))) return LC_ERR_ARG;   // a window is a lower edge of the causal mask
-  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)) || (c.varlen && !a->cu_q) || (c.lse && !a->lse))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
+  if (c.window < 0 || ((c.window > 0 || c.tree) && !(c.flags & LC_ATTN_CAUSAL))) return LC_ERR_ARG;   // a window is a lower edge of the causal mask, a tree mask (§4.3o) a set of holes in it
+  if (a && (!a->Q || !a->K || !a->V || !a->O || (c.paged && (!a->block_table || !a->kv_len)) || (c.varlen && !a->cu_q) || (c.lse && !a->lse) || (c.tree && !a->tree_mask))) return LC_ERR_ARG;   // (k_scale / v_scale: NULL = 1.0)
   if (c.H <= 0 || c.Hkv < 1 || c.Hkv > c.H || c.H % c.Hkv != 0) return LC_ERR_SHAPE;
   if (c.B <= 0 || c.Nq <= 0 || c.D <= 0) return LC_ERR_SHAPE;
   if (c.varlen && (c.T < 1 || c.max_nq > c.T)) return LC_ERR_SHAPE;   // (Nq IS max_nq: < 1 is refused above)
@@ -760,7 +760,7 @@ int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
   // one head's Ncap rows (an upper bound of one page run) stay below 2 GiB: the kernel's 32-bit offsets (attn_span_fits at kv_bytes an element)
   if ((size_t)ncap * (size_t)c.D * (size_t)c.kv_bytes >= 0x80000000ull) return LC_ERR_SHAPE;
   if ((size_t)c.B * c.Hkv * (size_t)((R + 63) / 64) * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x Hkv x RB x S workgroups, S <= 64
-  if (a && (!aligned16(a->Q) || !aligned16(a->K) || !aligned16(a->V) || !aligned16(a->O))) return LC_ERR_SHAPE;
+  if (a && (!aligned16(a->Q) || !aligned16(a->K) || !aligned16(a->V) || !aligned16(a->O) || (c.tree && !aligned8(a->tree_mask)))) return LC_ERR_SHAPE;
   if (c.D != 64 && c.D != 128) return LC_ERR_HEADDIM;
   return plan_attn_decode(read_knobs(), c, p);
 }
@@ -772,7 +772,10 @@ void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   // (DecodeCall::lse: varlen only — the twin plan's name with "_lse" in it)
   static const char* const kVarlenLse[] = {"", "attn_varlen_paged_lse_kernel", "attn_varlen_paged_kv8_lse_kernel"};
   static const char* const kVarlenLseBf16[] = {"", "attn_varlen_paged_lse_bf16_kernel", "attn_varlen_paged_kv8_lse_bf16_kernel"};
-  const char* kern = (p.call.lse ? (p.call.bf16 ? kVarlenLseBf16 : kVarlenLse) : p.call.bf16 ? kVarlenBf16 : p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
+  // (DecodeCall::tree: lse calls only — the LSE plan's name with "tree" in place of "lse")
+  static const char* const kVarlenTree[] = {"", "attn_varlen_paged_tree_kernel", "attn_varlen_paged_kv8_tree_kernel"};
+  static const char* const kVarlenTreeBf16[] = {"", "attn_varlen_paged_tree_bf16_kernel", "attn_varlen_paged_kv8_tree_bf16_kernel"};
+  const char* kern = (p.call.tree ? (p.call.bf16 ? kVarlenTreeBf16 : kVarlenTree) : p.call.lse ? (p.call.bf16 ? kVarlenLseBf16 : kVarlenLse) : p.call.bf16 ? kVarlenBf16 : p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
   if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
     static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
     static const char* const kLocalChunk[] = {"attn_local_chunk_kernel", "attn_local_chunk_paged_kernel", "attn_local_chunk_paged_kv8_kernel"};
@@ -780,7 +783,9 @@ void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
     static const char* const kVarlenChunkBf16[] = {"", "attn_varlen_chunk_paged_bf16_kernel", "attn_varlen_chunk_paged_kv8_bf16_kernel"};
     static const char* const kVarlenChunkLse[] = {"", "attn_varlen_chunk_paged_lse_kernel", "attn_varlen_chunk_paged_kv8_lse_kernel"};
     static const char* const kVarlenChunkLseBf16[] = {"", "attn_varlen_chunk_paged_lse_bf16_kernel", "attn_varlen_chunk_paged_kv8_lse_bf16_kernel"};
-    const char* chunk = (p.call.lse ? (p.call.bf16 ? kVarlenChunkLseBf16 : kVarlenChunkLse) : p.call.bf16 ? kVarlenChunkBf16 : p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
+    static const char* const kVarlenChunkTree[] = {"", "attn_varlen_chunk_paged_tree_kernel", "attn_varlen_chunk_paged_kv8_tree_kernel"};
+    static const char* const kVarlenChunkTreeBf16[] = {"", "attn_varlen_chunk_paged_tree_bf16_kernel", "attn_varlen_chunk_paged_kv8_tree_bf16_kernel"};
+    const char* chunk = (p.call.tree ? (p.call.bf16 ? kVarlenChunkTreeBf16 : kVarlenChunkTree) : p.call.lse ? (p.call.bf16 ? kVarlenChunkLseBf16 : kVarlenChunkLse) : p.call.bf16 ? kVarlenChunkBf16 : p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
     if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", chunk, p.call.D, p.S);
     else snprintf(buf, buflen, "%s<%d>", chunk, p.call.D);
     return;
@@ -829,7 +834,7 @@ void format_kv_append(const AppendCall& c, char* buf, int buflen) {
 // Nq = max_nq: its grid bound is that of the rectangular call the ragged one replaces.)
 int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p) {
   if (c.flags & ~(c.varlen ? LC_ROPE_INTERLEAVED : LC_ROPE_INTERLEAVED | LC_ROPE_PACKED_SRC)) return LC_ERR_ARG;
-  if (p && (!p->Q || !p->Qout || !p->cos_sin || (c.varlen && !p->cu_q))) return LC_ERR_ARG;
+  if (p && (!p->Q || !p->Qout || !p->cos_sin || (c.varlen && !p->cu_q) || (c.pos && !p->pos_ids))) return LC_ERR_ARG;
   const int rc = check_kv_append(c.a, p ? &p->a : nullptr);
   if (rc != LC_OK && rc != LC_ERR_HEADDIM) return rc;
   const int D = c.a.D;
@@ -857,6 +862,9 @@ void format_rope_append(const RopeAppendCall& c, char* buf, int buflen) {
   const char* fmt = c.a.kv_bytes == 1 ? "rope_append_paged_kv8_kernel<%d,%s>" : "rope_append_paged_kernel<%d,%s>";
   if (c.varlen) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_kernel<%d,%s>" : "rope_append_varlen_kernel<%d,%s>";
   if (c.bf16) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_bf16_kernel<%d,%s>" : "rope_append_varlen_bf16_kernel<%d,%s>";   // (varlen only)
+  if (c.pos)   // (varlen only)
+    fmt = c.bf16 ? (c.a.kv_bytes == 1 ? "rope_append_varlen_pos_kv8_bf16_kernel<%d,%s>" : "rope_append_varlen_pos_bf16_kernel<%d,%s>")
+                 : (c.a.kv_bytes == 1 ? "rope_append_varlen_pos_kv8_kernel<%d,%s>" : "rope_append_varlen_pos_kernel<%d,%s>");
   snprintf(buf, buflen, fmt, c.a.D, c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
 }
 
