@@ -1003,43 +1003,14 @@ def attn_varlen_paged(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, c
     cu_q[b] .. cu_q[b + 1] - 1 (cu_q a DEVICE int32 [B + 1] tensor, read by the kernel only and clamped there into the T rows and to max_nq
     rows a sequence); kv_len[b] is the length after the step's append, query i of sequence b sits at kv_len[b] - Nq_b + i.  Pools, block_table,
     causal, window, sinks and workspace: attn_local_paged's.  Rows at or past cu_q[B] are not written."""
-    import torch
-    if q.dtype != torch.half or o.dtype != torch.half or k_pool.dtype != torch.half or v_pool.dtype != torch.half:
-        raise TypeError(f"q / o / k_pool / v_pool must be float16, got {q.dtype} / {o.dtype} / {k_pool.dtype} / {v_pool.dtype}")
-    dims = _varlen_dims(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq)
-    local = _varlen_local(q, window, sinks)
-    _need_gpu(q, k_pool, v_pool, o, cu_q, block_table, kv_len)
-    check(load().lc_attn_varlen_paged_f16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *dims,
-                                          *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
-          "lc_attn_varlen_paged_f16")
-    return o
+    return _varlen_attn(q, k_pool, v_pool, o, False, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, False)
 
 
 def attn_varlen_paged_kv8(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, k_scale=None, v_scale=None, causal=False, window=0,
                           sinks=None, workspace=None):
     """attn_varlen_paged over fp8 pools (lc_attn_varlen_paged_kv8): k_pool8, v_pool8 of torch.float8_e4m3fn (or its bytes as uint8), k_scale,
     v_scale DEVICE float32 [Hkv] or None = 1.0, as attn_local_paged_kv8."""
-    import torch
-    fp8 = (torch.float8_e4m3fn, torch.uint8)
-    if q.dtype != torch.half or o.dtype != torch.half:
-        raise TypeError(f"q / o must be float16, got {q.dtype} / {o.dtype}")
-    if k_pool8.dtype not in fp8 or v_pool8.dtype not in fp8:
-        raise TypeError(f"k_pool8 / v_pool8 must be float8_e4m3fn or uint8, got {k_pool8.dtype} / {v_pool8.dtype}")
-    dims = _varlen_dims(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq)
-    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-        if s is None:
-            continue
-        if s.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {s.dtype}")
-        if tuple(s.shape) != (dims[2],):
-            _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
-    local = _varlen_local(q, window, sinks)
-    _need_gpu(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
-    check(load().lc_attn_varlen_paged_kv8(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len),
-                                          _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None, *dims,
-                                          *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
-          "lc_attn_varlen_paged_kv8")
-    return o
+    return _varlen_attn(q, k_pool8, v_pool8, o, False, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, False)
 
 
 def attn_varlen_paged_workspace_bytes(B, H, Hkv, T, max_nq, page_size, max_pages, D, window=0, kv8=False) -> int:
@@ -1176,43 +1147,14 @@ def rope_append_varlen_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D
 def attn_varlen_paged_bf16(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, causal=False, window=0, sinks=None, workspace=None):
     """attn_varlen_paged with bfloat16 q, o [T,H,D] and bfloat16 pools (lc_attn_varlen_paged_bf16): every other argument, the clamps and the
     plan are attn_varlen_paged's."""
-    import torch
-    if q.dtype != torch.bfloat16 or o.dtype != torch.bfloat16 or k_pool.dtype != torch.bfloat16 or v_pool.dtype != torch.bfloat16:
-        raise TypeError(f"q / o / k_pool / v_pool must be bfloat16, got {q.dtype} / {o.dtype} / {k_pool.dtype} / {v_pool.dtype}")
-    dims = _varlen_dims(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq)
-    local = _varlen_local(q, window, sinks)
-    _need_gpu(q, k_pool, v_pool, o, cu_q, block_table, kv_len)
-    check(load().lc_attn_varlen_paged_bf16(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *dims,
-                                           *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
-          "lc_attn_varlen_paged_bf16")
-    return o
+    return _varlen_attn(q, k_pool, v_pool, o, False, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, True)
 
 
 def attn_varlen_paged_kv8_bf16(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, k_scale=None, v_scale=None, causal=False, window=0,
                                sinks=None, workspace=None):
     """attn_varlen_paged_kv8 with bfloat16 q, o (lc_attn_varlen_paged_kv8_bf16): the pools are the same e4m3 bytes under the same float32
     scales — a cache written by either element type is read by both."""
-    import torch
-    fp8 = (torch.float8_e4m3fn, torch.uint8)
-    if q.dtype != torch.bfloat16 or o.dtype != torch.bfloat16:
-        raise TypeError(f"q / o must be bfloat16, got {q.dtype} / {o.dtype}")
-    if k_pool8.dtype not in fp8 or v_pool8.dtype not in fp8:
-        raise TypeError(f"k_pool8 / v_pool8 must be float8_e4m3fn or uint8, got {k_pool8.dtype} / {v_pool8.dtype}")
-    dims = _varlen_dims(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq)
-    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
-        if s is None:
-            continue
-        if s.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {s.dtype}")
-        if tuple(s.shape) != (dims[2],):
-            _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
-    local = _varlen_local(q, window, sinks)
-    _need_gpu(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if s is not None))
-    check(load().lc_attn_varlen_paged_kv8_bf16(_ptr(q), _ptr(k_pool8), _ptr(v_pool8), _ptr(o), _ptr(cu_q), _ptr(block_table), _ptr(kv_len),
-                                               _ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None,
-                                               *dims, *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()),
-          "lc_attn_varlen_paged_kv8_bf16")
-    return o
+    return _varlen_attn(q, k_pool8, v_pool8, o, False, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, True)
 
 
 def attn_varlen_paged_bf16_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=False, window=0, kv8=False) -> str:
@@ -1261,9 +1203,11 @@ def _lse_out(q, lse):
     return lse
 
 
-def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, kv8, bf16,
-                tree=None):
-    """the four lse calls and, with `tree` (an int64 [T] tensor of look-back words), the four tree calls: the same checks, `tree` behind lse"""
+def _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, kv8, bf16,
+                 tree=None):
+    """The twelve ragged attention calls: the same checks in the same order.  lse False: a plain call (lc_attn_varlen_paged_f16 / _kv8 / _bf16 /
+    _kv8_bf16), which returns o; lse None or a tensor: an lse call (`lse` behind o), which returns (o, lse); with `tree` (an int64 [T] tensor of
+    look-back words) a tree call, `tree` behind lse"""
     import torch
     el, el_name = (torch.bfloat16, "bfloat16") if bf16 else (torch.half, "float16")
     fp8 = (torch.float8_e4m3fn, torch.uint8)
@@ -1286,7 +1230,8 @@ def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_
                 _shape_err(f"{name} {tuple(s.shape)} for {dims[2]} K/V heads")
         scales = (_ptr(k_scale) if k_scale is not None else None, _ptr(v_scale) if v_scale is not None else None)
     local = _varlen_local(q, window, sinks)
-    lse = _lse_out(q, lse)
+    plain = lse is False
+    outs = () if plain else (_lse_out(q, lse),)
     masks = ()
     if tree is not None:
         if tree.dtype != torch.int64:
@@ -1294,36 +1239,36 @@ def _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, k_
         if tuple(tree.shape) != (q.shape[0],) or not tree.is_contiguous():
             _shape_err(f"tree_mask {tuple(tree.shape)} for q {tuple(q.shape)}: contiguous [T] expected")
         masks = (tree,)
-    _need_gpu(q, k_pool, v_pool, o, lse, *masks, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if kv8 and s is not None))
-    symbol = ("lc_attn_varlen_paged_lse_" if tree is None else "lc_attn_varlen_paged_tree_") + (("kv8_bf16" if bf16 else "kv8") if kv8 else ("bf16" if bf16 else "f16"))
-    check(getattr(load(), symbol)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), _ptr(lse), *(_ptr(t) for t in masks), _ptr(cu_q), _ptr(block_table),
+    _need_gpu(q, k_pool, v_pool, o, *outs, *masks, cu_q, block_table, kv_len, *(s for s in (k_scale, v_scale) if kv8 and s is not None))
+    symbol = "lc_attn_varlen_paged_" + ("" if plain else "lse_" if tree is None else "tree_") + (("kv8_bf16" if bf16 else "kv8") if kv8 else ("bf16" if bf16 else "f16"))
+    check(getattr(load(), symbol)(_ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o), *(_ptr(t) for t in outs + masks), _ptr(cu_q), _ptr(block_table),
                                   _ptr(kv_len), *scales, *dims, *_local_ptrs(local), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace),
                                   _stream()), symbol)
-    return o, lse
+    return o if plain else (o, outs[0])
 
 
 def attn_varlen_paged_lse(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, lse=None, causal=False, window=0, sinks=None, workspace=None):
     """attn_varlen_paged that also writes each row's log-sum-exp (lc_attn_varlen_paged_lse_f16): lse float32 [T,H] (None: allocated).  O is
     attn_varlen_paged's, bit for bit; the workspace is attn_varlen_paged_workspace_bytes'.  Returns (o, lse)."""
-    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, False)
+    return _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, False)
 
 
 def attn_varlen_paged_kv8_lse(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, lse=None, k_scale=None, v_scale=None, causal=False,
                               window=0, sinks=None, workspace=None):
     """attn_varlen_paged_kv8 + lse (lc_attn_varlen_paged_lse_kv8): the scores under the log are q.k k_scale / sqrt(D); v_scale does not enter."""
-    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, False)
+    return _varlen_attn(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, False)
 
 
 def attn_varlen_paged_lse_bf16(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, lse=None, causal=False, window=0, sinks=None,
                                workspace=None):
     """attn_varlen_paged_bf16 + lse (lc_attn_varlen_paged_lse_bf16); lse stays float32."""
-    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, True)
+    return _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, causal, window, sinks, workspace, False, True)
 
 
 def attn_varlen_paged_kv8_lse_bf16(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, lse=None, k_scale=None, v_scale=None, causal=False,
                                    window=0, sinks=None, workspace=None):
     """attn_varlen_paged_kv8_bf16 + lse (lc_attn_varlen_paged_lse_kv8_bf16)."""
-    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, True)
+    return _varlen_attn(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, causal, window, sinks, workspace, True, True)
 
 
 def attn_varlen_paged_lse_kernel_name(B, H, Hkv, T, max_nq, page_size, max_pages, D, causal=False, window=0, kv8=False, bf16=False) -> str:
@@ -1342,25 +1287,25 @@ def attn_varlen_paged_tree(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_
     """attn_varlen_paged_lse under a look-back visibility mask (lc_attn_varlen_paged_tree_f16), always causal: tree_mask DEVICE int64 [T], one word
     per token row of q; the token at cache slot p sees key j <= p (j > p - window) with d = p - j >= 64, or with bit d of its word set.  A word
     of all ones (-1) is attn_varlen_paged_lse(causal=True), bit for bit.  Plan and workspace are attn_varlen_paged's.  Returns (o, lse)."""
-    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, True, window, sinks, workspace, False, False, tree_mask)
+    return _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, True, window, sinks, workspace, False, False, tree_mask)
 
 
 def attn_varlen_paged_kv8_tree(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, k_scale=None, v_scale=None, window=0,
                                sinks=None, workspace=None):
     """attn_varlen_paged_tree over fp8 pools (lc_attn_varlen_paged_tree_kv8)."""
-    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, True, window, sinks, workspace, True, False,
+    return _varlen_attn(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, True, window, sinks, workspace, True, False,
                        tree_mask)
 
 
 def attn_varlen_paged_tree_bf16(q, k_pool, v_pool, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, window=0, sinks=None, workspace=None):
     """attn_varlen_paged_tree with bfloat16 q, o and pools (lc_attn_varlen_paged_tree_bf16); lse stays float32."""
-    return _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, True, window, sinks, workspace, False, True, tree_mask)
+    return _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, None, None, True, window, sinks, workspace, False, True, tree_mask)
 
 
 def attn_varlen_paged_kv8_tree_bf16(q, k_pool8, v_pool8, o, cu_q, block_table, kv_len, max_nq, tree_mask, lse=None, k_scale=None, v_scale=None,
                                     window=0, sinks=None, workspace=None):
     """attn_varlen_paged_kv8_tree with bfloat16 q, o (lc_attn_varlen_paged_tree_kv8_bf16)."""
-    return _varlen_lse(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, True, window, sinks, workspace, True, True,
+    return _varlen_attn(q, k_pool8, v_pool8, o, lse, cu_q, block_table, kv_len, max_nq, k_scale, v_scale, True, window, sinks, workspace, True, True,
                        tree_mask)
 
 
@@ -1552,8 +1497,8 @@ def attn_cascade_paged(q, k_pool, v_pool, o, cu_groups, prefix_table, prefix_len
         raise TypeError("sinks must be a float32 tensor or None")
     bf16 = q.dtype == torch.bfloat16
     ks, vs = (k_scale, v_scale) if kv8 else (None, None)
-    _varlen_lse(q, k_pool, v_pool, o_p, lse_p, cu_groups, prefix_table, prefix_len, max_nq_prefix, ks, vs, False, 0, None, workspaces[0], kv8, bf16)
-    _varlen_lse(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, ks, vs, True, 0, sinks, workspaces[1], kv8, bf16)
+    _varlen_attn(q, k_pool, v_pool, o_p, lse_p, cu_groups, prefix_table, prefix_len, max_nq_prefix, ks, vs, False, 0, None, workspaces[0], kv8, bf16)
+    _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, ks, vs, True, 0, sinks, workspaces[1], kv8, bf16)
     return attn_merge_states(o, lse, o_p, lse_p, out=o, lse_out=lse, cu_q=cu_q)
 
 

@@ -80,12 +80,12 @@ struct DecodeVarlen {
   int T;             // rows of Q and O
 };
 
-// The row's log-sum-exp next to O (attn_varlen_lse.hip).  Every other kernel leaves the field unused.
+// The row's log-sum-exp next to O (attn_varlen.hip).  Every other kernel leaves the field unused.
 struct DecodeLse {
   float* lse;   // device float[rows of O]: ln(sum over the row's visible keys of exp(score), the sink included); -inf: no key, no sink
 };
 
-// A look-back visibility mask per query token (attn_varlen_tree.hip).  Every other kernel leaves the field unused.
+// A look-back visibility mask per query token (attn_varlen.hip).  Every other kernel leaves the field unused.
 struct DecodeTree {
   const uint64_t* mask;   // device uint64[T]: bit d of word t lets token t, at cache slot p, see key p - d (d < 64); keys 64 or more slots back are not governed
 };

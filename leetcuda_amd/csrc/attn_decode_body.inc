@@ -20,17 +20,17 @@
 // other use is the workgroup-uniform `Nqb` = Nq_b.  The row order inside a (sequence, K / V head) stays r = g Nq_b + i: only the ADDRESS of a row
 // changes, global row (q0 + r % Nq_b) H + kvh G + r / Nq_b in place of row0 + r.  A workgroup whose row block starts at or past R_b returns in
 // front of the first LDS access and barrier.  With VARLEN = false Nqb IS Nq: the 36 other kernels' code does not depend on the parameter.
-// A `constexpr bool BF16` closes the list.  BF16 = true (the attn_varlen_*_bf16_kernel of attn_varlen_bf16.hip; DESIGN.md §4.3m): the 16-bit lanes
+// A `constexpr bool BF16` closes the list.  BF16 = true (the attn_varlen_*_bf16_kernel of attn_varlen.hip; DESIGN.md §4.3m): the 16-bit lanes
 // of Q, O and a 16-bit cache are bfloat16.  Four places read them as numbers and only those change: the two MFMA sites (mfma16_16<BF16>), the
 // rounding of P and of O (cvt16<BF16>, RNE), and the e4m3 -> 16-bit conversion of an fp8 cache (kv8_16x8<BF16>).  Loads, LDS images, transposed
 // reads, masks, (m, l) and the partials do not know the element type.  With BF16 = false the three helpers ARE mfma16, (half_t)x and kv8_half8:
 // every fp16 kernel's code is what it was without the parameter (§4.3m compares it).
 // A `constexpr bool LSE` with a `const DecodeLse ls` (LSE = false: unused) is the newest.  LSE = true (the attn_varlen_*_lse*_kernel of
-// attn_varlen_lse.hip; DESIGN.md §4.3n): where wave 0 stores a row's O (S == 1) its h == 0 lanes also store the row's log-sum-exp in NATURAL
+// attn_varlen.hip; DESIGN.md §4.3n): where wave 0 stores a row's O (S == 1) its h == 0 lanes also store the row's log-sum-exp in NATURAL
 // units, ls.lse[row] with the global row of O and O's row guard.  The S > 1 path is untouched: part_lse always carried it, and the combine
 // kernel of an LSE plan stores it.  With LSE = false nothing changes: every other kernel's code does not depend on the parameter (§4.3n compares it).
 // A `constexpr bool TREE` with a `const DecodeTree tr` (TREE = false: unused) follows it.  TREE = true (the attn_varlen_*_tree*_kernel of
-// attn_varlen_tree.hip; DESIGN.md §4.3o): every query token carries a 64-bit look-back word, and key j of the row at slot p = lim - 1 is visible
+// attn_varlen.hip; DESIGN.md §4.3o): every query token carries a 64-bit look-back word, and key j of the row at slot p = lim - 1 is visible
 // only if the compare below holds AND, for d = p - j < 64, bit d of the word is set; keys 64 or more slots back are not governed.  The mask only
 // REMOVES keys: Lw, tile_lo, the range partition, the page ids and the source clamps do not know it.  A row's word sits in the padding of its
 // Q row in LDS (no more LDS, no register across the loop), and a step whose every key lies 64 or more slots below the workgroup's lowest row

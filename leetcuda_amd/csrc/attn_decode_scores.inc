@@ -1,6 +1,6 @@
 // attn_decode_scores.inc — the scores and the online softmax of ONE pipeline step of attn_decode_body.inc, for all RT row tiles: included there,
 // inside the step loop, with everything that body declares in scope and a `constexpr bool MASKED` in front of it.  MASKED = false: the loop
-// as it always stood in the body.  MASKED = true (the TREE kernels of attn_varlen_tree.hip, on the steps near the workgroup's rows; DESIGN.md
+// as it always stood in the body.  MASKED = true (the TREE kernels of attn_varlen.hip, on the steps near the workgroup's rows; DESIGN.md
 // §4.3o): the row's look-back bit joins the visibility compare.  A text of its own so that a TREE kernel can hold both forms behind one
 // wave-uniform branch per step, each a straight run of code in which hipcc runs a row tile's MFMAs under the softmax of the one before (a
 // branch per row tile cost the four-row-tile kernels 24 % on every tile; a generic lambda moved the other kernels' schedules).

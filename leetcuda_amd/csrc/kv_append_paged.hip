@@ -52,7 +52,7 @@ LC_DEVINL u32x2_t kv8_quantize8(u32x4_t raw, float s) {
   return out;
 }
 
-// The bfloat16 flavours of the two functions above (rope_append_varlen_bf16.hip): a bf16 element IS the upper half of its fp32
+// The bfloat16 flavours of the two functions above (rope_append_varlen.hip): a bf16 element IS the upper half of its fp32
 // value, so the decode is a shift; the quotient, the clamp, the conversion and the NaN rule are the same, the NaN test on the bf16 bits
 LC_DEVINL bool nan_bits_bf16(uint32_t h) { return (h & 0x7fffu) > 0x7f80u; }
 LC_DEVINL float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }           // element 0 of a dword of two bf16

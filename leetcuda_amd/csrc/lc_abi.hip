@@ -85,17 +85,26 @@ DecodeCall decode_local(DecodeCall c, int window, const float* sinks = nullptr) 
   c.sinks = sinks != nullptr;
   return c;
 }
-// the lc_attn_varlen_paged_* entries: the paged local call of Nq = max_nq on T token-major rows
-// bf16: the lc_attn_varlen_paged_*bf16 entries — the same call on bfloat16 elements
-// lse: the lc_attn_varlen_paged_lse_* entries — the same call, which also writes each row's log-sum-exp
-// tree: the lc_attn_varlen_paged_tree_* entries — the lse call with a look-back visibility word per query token
-DecodeCall decode_varlen(DecodeCall c, int T, bool bf16 = false, bool lse = false, bool tree = false) {
+// What a ragged entry (lc_attn_varlen_paged_*, lc_rope_append_varlen_*) is a variant of, as a set of bits: its name says them
+enum : unsigned {
+  VL_F16 = 0,             // fp16 elements, 16-bit pools, O alone (attention) / the cache slot as rotary position (rope)
+  VL_KV8 = 1,             // *_kv8: e4m3 pools under k_scale, v_scale
+  VL_BF16 = 2,            // *_bf16: the same call on bfloat16 elements
+  VL_LSE = 4,             // lc_attn_varlen_paged_lse_* (§4.3n): the same call, which also writes each row's log-sum-exp
+  VL_TREE = 8 | VL_LSE,   // lc_attn_varlen_paged_tree_* (§4.3o): the lse call with a look-back visibility word per query token
+  VL_POS = 16             // lc_rope_append_varlen_pos_* (§4.3o): the rotary position of token t is pos_ids[t]
+};
+// the lc_attn_varlen_paged_* entries: the paged local call of Nq = max_nq on T token-major rows.  The query calls state
+// num_pages = 1 and sinks = nullptr
+DecodeCall varlen_call(unsigned variant, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
+                       const float* sinks, int flags) {
+  DecodeCall c = decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, variant & VL_KV8 ? 1 : 2, true), window, sinks);
   c.varlen = true;
   c.T = T;
-  c.max_nq = c.Nq;
-  c.bf16 = bf16;
-  c.lse = lse;
-  c.tree = tree;
+  c.max_nq = max_nq;
+  c.bf16 = (variant & VL_BF16) != 0;
+  c.lse = (variant & VL_LSE) != 0;
+  c.tree = (variant & VL_TREE) == VL_TREE;
   return c;
 }
 // block_table: paged calls; k_scale / v_scale: the fp8 call (nullptr elsewhere); sinks: a local or varlen call, or nullptr; cu_q: a varlen call
@@ -165,15 +174,15 @@ int rope_run(const RopeAppendCall& c, const void* Q, const void* Knew, const voi
   return launch_rope_append(c, p);
 }
 // the lc_rope_append_varlen_* entries: the rope call of Nq = max_nq on T token-major rows with a stride each
-RopeAppendCall rope_varlen_call(int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
-                                long long q_row_stride, long long kv_row_stride, int flags, int kv_bytes, bool bf16 = false, bool pos = false) {
-  RopeAppendCall c = rope_call(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, flags, kv_bytes);
+RopeAppendCall rope_varlen_call(unsigned variant, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim,
+                                int max_pos, long long q_row_stride, long long kv_row_stride, int flags) {
+  RopeAppendCall c = rope_call(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, flags, variant & VL_KV8 ? 1 : 2);
   c.varlen = true;
   c.T = T;
   c.max_nq = max_nq;
   c.kv_row_stride = kv_row_stride;
-  c.bf16 = bf16;   // the lc_rope_append_varlen_*bf16 entries
-  c.pos = pos;     // the lc_rope_append_varlen_pos_* entries
+  c.bf16 = (variant & VL_BF16) != 0;
+  c.pos = (variant & VL_POS) != 0;
   return c;
 }
 int rope_varlen_run(const RopeAppendCall& c, const void* Q, const void* Knew, const void* Vnew, void* Qout, void* Kpool, void* Vpool,
@@ -184,8 +193,8 @@ int rope_varlen_run(const RopeAppendCall& c, const void* Q, const void* Knew, co
                          static_cast<const half_t*>(Q), static_cast<half_t*>(Qout), cos_sin, cu_q, pos_ids};
   if (int rc = check_rope_append(c, &p)) return rc;
   if (int rc = launch_guard()) return rc;
-  if (c.pos) return launch_rope_append_varlen_pos(c, p);
-  return c.bf16 ? launch_rope_append_varlen_bf16(c, p) : launch_rope_append_varlen(c, p);
+  if (c.pos) return launch_rope_append_varlen<RopeVarlenUnit::POS>(c, p);
+  return c.bf16 ? launch_rope_append_varlen<RopeVarlenUnit::BF16>(c, p) : launch_rope_append_varlen<RopeVarlenUnit::F16>(c, p);
 }
 int rope_name(const RopeAppendCall& c, char* buf, int buflen) {
   if (!buf || buflen < 8) return LC_ERR_ARG;
@@ -519,36 +528,34 @@ int lc_attn_local_paged_kv8_kernel_name(int B, int H, int Hkv, int Nq, int page_
 int lc_attn_varlen_paged_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* cu_q, const int* block_table, const int* kv_len,
                              int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
                              const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T), Q,
+  return decode_run(varlen_call(VL_F16, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags), Q,
                     Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q);
 }
 
 size_t lc_attn_varlen_paged_workspace_bytes(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window) {
-  return decode_bytes(
-      decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, window > 0 ? LC_ATTN_CAUSAL : 0, 2, true), window), T));
+  return decode_bytes(varlen_call(VL_F16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, window > 0 ? LC_ATTN_CAUSAL : 0));
 }
 
 int lc_attn_varlen_paged_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf,
                                      int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T), buf, buflen);
+  return decode_name(varlen_call(VL_F16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* cu_q, const int* block_table,
                              const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages,
                              int page_size, int max_pages, int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes,
                              void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T), Q,
+  return decode_run(varlen_call(VL_KV8, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags), Q,
                     Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q);
 }
 
 size_t lc_attn_varlen_paged_kv8_workspace_bytes(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window) {
-  return decode_bytes(
-      decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, window > 0 ? LC_ATTN_CAUSAL : 0, 1, true), window), T));
+  return decode_bytes(varlen_call(VL_KV8, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, window > 0 ? LC_ATTN_CAUSAL : 0));
 }
 
 int lc_attn_varlen_paged_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf,
                                          int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T), buf, buflen);
+  return decode_name(varlen_call(VL_KV8, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 // The bfloat16 varlen entries: the two entries above, argument for argument, as a DecodeCall with bf16 = true.  The checks,
@@ -556,28 +563,26 @@ int lc_attn_varlen_paged_kv8_kernel_name(int B, int H, int Hkv, int T, int max_n
 int lc_attn_varlen_paged_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, const int* cu_q, const int* block_table, const int* kv_len,
                               int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
                               const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, true),
+  return decode_run(varlen_call(VL_BF16, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q);
 }
 
 int lc_attn_varlen_paged_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags,
                                           char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_BF16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, const int* cu_q, const int* block_table,
                                   const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq,
                                   int num_pages, int page_size, int max_pages, int D, int window, const float* sinks, int flags, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, true),
+  return decode_run(varlen_call(VL_KV8 | VL_BF16, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q);
 }
 
 int lc_attn_varlen_paged_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags,
                                               char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_KV8 | VL_BF16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 // The varlen entries that also write each row's log-sum-exp: the four entries above with `lse` right behind O, as a DecodeCall
@@ -586,49 +591,45 @@ int lc_attn_varlen_paged_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int 
 int lc_attn_varlen_paged_lse_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* cu_q, const int* block_table,
     const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
     const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, false, true),
+  return decode_run(varlen_call(VL_LSE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse);
 }
 
 int lc_attn_varlen_paged_lse_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, false, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_LSE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_lse_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const int* cu_q, const int* block_table,
     const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
     const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, false, true),
+  return decode_run(varlen_call(VL_KV8 | VL_LSE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse);
 }
 
 int lc_attn_varlen_paged_lse_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, false, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_KV8 | VL_LSE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_lse_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const int* cu_q, const int* block_table,
     const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
     const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, true, true),
+  return decode_run(varlen_call(VL_BF16 | VL_LSE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse);
 }
 
 int lc_attn_varlen_paged_lse_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, true, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_BF16 | VL_LSE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_lse_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const int* cu_q, const int* block_table,
     const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
     const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, true, true),
+  return decode_run(varlen_call(VL_KV8 | VL_BF16 | VL_LSE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse);
 }
 
 int lc_attn_varlen_paged_lse_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_KV8 | VL_BF16 | VL_LSE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 // The varlen entries with a look-back visibility mask per query token: the four lse entries above with `tree_mask` right behind
@@ -637,49 +638,45 @@ int lc_attn_varlen_paged_lse_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, 
 int lc_attn_varlen_paged_tree_f16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
     const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
     const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, false, true, true),
+  return decode_run(varlen_call(VL_TREE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
 }
 
 int lc_attn_varlen_paged_tree_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, false, true, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_TREE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_tree_kv8(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
     const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size,
     int max_pages, int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, false, true, true),
+  return decode_run(varlen_call(VL_KV8 | VL_TREE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
 }
 
 int lc_attn_varlen_paged_tree_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, false, true, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_KV8 | VL_TREE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_tree_bf16(const void* Q, const void* Kpool, const void* Vpool, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
     const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int window,
     const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 2, true), window, sinks), T, true, true, true),
+  return decode_run(varlen_call(VL_BF16 | VL_TREE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool, Vpool, O, kv_len, block_table, nullptr, nullptr, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
 }
 
 int lc_attn_varlen_paged_tree_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 2, true), window), T, true, true, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_BF16 | VL_TREE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 int lc_attn_varlen_paged_tree_kv8_bf16(const void* Q, const void* Kpool8, const void* Vpool8, void* O, float* lse, const uint64_t* tree_mask, const int* cu_q,
     const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size,
     int max_pages, int D, int window, const float* sinks, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  return decode_run(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, num_pages, page_size, max_pages, D, flags, 1, true), window, sinks), T, true, true, true),
+  return decode_run(varlen_call(VL_KV8 | VL_BF16 | VL_TREE, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, window, sinks, flags),
                     Q, Kpool8, Vpool8, O, kv_len, block_table, k_scale, v_scale, workspace, workspace_bytes, stream, sinks, cu_q, lse, tree_mask);
 }
 
 int lc_attn_varlen_paged_tree_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int window, int flags, char* buf, int buflen) {
-  return decode_name(decode_varlen(decode_local(decode_paged(B, H, Hkv, max_nq, 1, page_size, max_pages, D, flags, 1, true), window), T, true, true, true), buf,
-                     buflen);
+  return decode_name(varlen_call(VL_KV8 | VL_BF16 | VL_TREE, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, window, nullptr, flags), buf, buflen);
 }
 
 // The merge of two (O, lse) states over disjoint key sets (attn_merge.hip): merge_run above states a MergeCall
@@ -745,7 +742,7 @@ int lc_rope_append_varlen_f16(const void* Q, const void* Knew, const void* Vnew,
                               const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int Hkv, int T, int max_nq, int num_pages,
                               int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags,
                               void* stream) {
-  return rope_varlen_run(rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2),
+  return rope_varlen_run(rope_varlen_call(VL_F16, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags),
                          Q, Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream);
 }
 
@@ -753,19 +750,19 @@ int lc_rope_append_varlen_kv8(const void* Q, const void* Knew, const void* Vnew,
                               const int* cu_q, const int* block_table, const int* kv_len, const float* k_scale, const float* v_scale, int B, int H,
                               int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                               long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
-  return rope_varlen_run(rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1),
+  return rope_varlen_run(rope_varlen_call(VL_KV8, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags),
                          Q, Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream);
 }
 
 // (the name calls take no num_pages: it decides nothing)
 int lc_rope_append_varlen_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                       long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2), buf, buflen);
+  return rope_name(rope_varlen_call(VL_F16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 int lc_rope_append_varlen_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                           long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1), buf, buflen);
+  return rope_name(rope_varlen_call(VL_KV8, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 // the bfloat16 twins: the same RopeAppendCall with bf16 = true
@@ -774,7 +771,7 @@ int lc_rope_append_varlen_bf16(const void* Q, const void* Knew, const void* Vnew
                                int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride,
                                int flags, void* stream) {
   return rope_varlen_run(
-      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true), Q, Knew,
+      rope_varlen_call(VL_BF16, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), Q, Knew,
       Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream);
 }
 
@@ -783,20 +780,18 @@ int lc_rope_append_varlen_kv8_bf16(const void* Q, const void* Knew, const void* 
                                    int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                    long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
   return rope_varlen_run(
-      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true), Q, Knew,
+      rope_varlen_call(VL_KV8 | VL_BF16, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), Q, Knew,
       Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream);
 }
 
 int lc_rope_append_varlen_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                            long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true), buf,
-                   buflen);
+  return rope_name(rope_varlen_call(VL_BF16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 int lc_rope_append_varlen_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                                long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true), buf,
-                   buflen);
+  return rope_name(rope_varlen_call(VL_KV8 | VL_BF16, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 // the twins with per-token rotary positions: the same RopeAppendCall with pos = true and `pos_ids` right behind cu_q
@@ -805,7 +800,7 @@ int lc_rope_append_varlen_pos_f16(const void* Q, const void* Knew, const void* V
                                   int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride,
                                   long long kv_row_stride, int flags, void* stream) {
   return rope_varlen_run(
-      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, false, true), Q,
+      rope_varlen_call(VL_POS, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), Q,
       Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream, pos_ids);
 }
 
@@ -814,7 +809,7 @@ int lc_rope_append_varlen_pos_kv8(const void* Q, const void* Knew, const void* V
                                   const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages, int D,
                                   int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
   return rope_varlen_run(
-      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, false, true), Q,
+      rope_varlen_call(VL_KV8 | VL_POS, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), Q,
       Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream, pos_ids);
 }
 
@@ -823,7 +818,7 @@ int lc_rope_append_varlen_pos_bf16(const void* Q, const void* Knew, const void* 
                                    int max_nq, int num_pages, int page_size, int max_pages, int D, int rot_dim, int max_pos, long long q_row_stride,
                                    long long kv_row_stride, int flags, void* stream) {
   return rope_varlen_run(
-      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true, true), Q,
+      rope_varlen_call(VL_BF16 | VL_POS, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), Q,
       Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, stream, pos_ids);
 }
 
@@ -832,33 +827,29 @@ int lc_rope_append_varlen_pos_kv8_bf16(const void* Q, const void* Knew, const vo
                                        const float* v_scale, int B, int H, int Hkv, int T, int max_nq, int num_pages, int page_size, int max_pages,
                                        int D, int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride, int flags, void* stream) {
   return rope_varlen_run(
-      rope_varlen_call(B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true, true), Q,
+      rope_varlen_call(VL_KV8 | VL_BF16 | VL_POS, B, H, Hkv, T, max_nq, num_pages, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), Q,
       Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, stream, pos_ids);
 }
 
 // (the name calls take no num_pages: it decides nothing)
 int lc_rope_append_varlen_pos_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                           long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, false, true),
-                   buf, buflen);
+  return rope_name(rope_varlen_call(VL_POS, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 int lc_rope_append_varlen_pos_kv8_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                               long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, false, true),
-                   buf, buflen);
+  return rope_name(rope_varlen_call(VL_KV8 | VL_POS, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 int lc_rope_append_varlen_pos_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim, int max_pos,
                                                long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 2, true, true),
-                   buf, buflen);
+  return rope_name(rope_varlen_call(VL_BF16 | VL_POS, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 int lc_rope_append_varlen_pos_kv8_bf16_kernel_name(int B, int H, int Hkv, int T, int max_nq, int page_size, int max_pages, int D, int rot_dim,
                                                    int max_pos, long long q_row_stride, long long kv_row_stride, int flags, char* buf, int buflen) {
-  return rope_name(rope_varlen_call(B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags, 1, true, true),
-                   buf, buflen);
+  return rope_name(rope_varlen_call(VL_KV8 | VL_BF16 | VL_POS, B, H, Hkv, T, max_nq, 1, page_size, max_pages, D, rot_dim, max_pos, q_row_stride, kv_row_stride, flags), buf, buflen);
 }
 
 int lc_attn_fwd_bf16(const void* Q, const void* K, const void* V, void* O, int B, int H, int N, int D,

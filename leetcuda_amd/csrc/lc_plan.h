@@ -230,32 +230,16 @@ int launch_attn_chunk_ranges(const DecodePlan& p, int S, const DecodePtrs& a, fl
 // ... and of a local plan, RB = 1 or more: tu_attn_local_impl.h, instantiated in tu_attn_local.hip / _paged.hip / _paged_kv8.hip
 template <DecodeCache C>
 int launch_attn_local_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
-// ... and of a varlen plan (PAGED and PAGED_KV8 only): tu_attn_varlen_impl.h, instantiated in tu_attn_varlen_paged.hip / _paged_kv8.hip; its
-// combine launch (attn_varlen_combine_kernel<D>, both kinds): tu_attn_varlen_paged.hip
-template <DecodeCache C>
+// ... and of a varlen plan (PAGED and PAGED_KV8 only): tu_attn_varlen_impl.h, instantiated once per variant in the twelve tu_attn_varlen_paged*.hip,
+// each next to its own kernels.  BF16: DecodeCall::bf16; OUT: what the kernels write besides O and so take behind T — nothing, `lse`
+// (DecodeCall::lse) or `lse` under a `tree_mask` (DecodeCall::tree).  launch_attn_decode picks the instantiation from the call's fields
+enum class VarlenOut { PLAIN, LSE, TREE };
+template <DecodeCache C, bool BF16, VarlenOut OUT>
 int launch_attn_varlen_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
+// ... and its combine launch (attn_varlen_combine_kernel<D> / _bf16 / _lse / _lse_bf16, each for both cache kinds; a tree plan's is the LSE plan's):
+// the same header, instantiated in tu_attn_varlen_paged.hip / _paged_bf16.hip / _paged_lse.hip / _paged_lse_bf16.hip
+template <bool BF16, bool LSE>
 int launch_attn_varlen_combine(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
-// ... and of a varlen plan with bf16 elements (DecodeCall::bf16): the same launcher on the attn_varlen_*_bf16_kernel, instantiated in
-// tu_attn_varlen_paged_bf16.hip / _paged_kv8_bf16.hip; its combine launch (attn_varlen_combine_bf16_kernel<D>): tu_attn_varlen_paged_bf16.hip
-template <DecodeCache C>
-int launch_attn_varlen_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
-int launch_attn_varlen_combine_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
-// ... and of a varlen plan that also writes the log-sum-exp (DecodeCall::lse): the same launcher on the attn_varlen_*_lse_kernel / _lse_bf16_kernel,
-// instantiated in tu_attn_varlen_paged_lse.hip / _paged_kv8_lse.hip / _paged_lse_bf16.hip / _paged_kv8_lse_bf16.hip; the combine launches
-// (attn_varlen_combine_lse_kernel<D> / _lse_bf16_kernel<D>): tu_attn_varlen_paged_lse.hip / _paged_lse_bf16.hip
-template <DecodeCache C>
-int launch_attn_varlen_lse_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
-int launch_attn_varlen_combine_lse(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
-template <DecodeCache C>
-int launch_attn_varlen_lse_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
-int launch_attn_varlen_combine_lse_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse);
-// ... and of a varlen plan with a look-back visibility mask (DecodeCall::tree; always with lse): the same launcher on the attn_varlen_*_tree_kernel /
-// _tree_bf16_kernel, instantiated in tu_attn_varlen_paged_tree.hip / _paged_kv8_tree.hip / _paged_tree_bf16.hip / _paged_kv8_tree_bf16.hip; the
-// combine launches are the LSE plan's
-template <DecodeCache C>
-int launch_attn_varlen_tree_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
-template <DecodeCache C>
-int launch_attn_varlen_tree_bf16_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse);
 
 // What a caller of a state-merge entry states (lc_attn_merge_states_f16 / _bf16): two (O [T,H,D], lse [T H]) states over disjoint
 // key sets become the state over their union.  There is nothing to plan: attn_merge_states_kernel<D> / attn_merge_states_bf16_kernel<D> on
@@ -331,8 +315,10 @@ struct RopeAppendPtrs {
 int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p);
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen);   // "rope_append_paged_kernel<128,false>" / "rope_append_paged_kv8_kernel<64,true>"
 int launch_rope_append(const RopeAppendCall& c, const RopeAppendPtrs& p);  // tu_rope_append.hip; checked arguments; a varlen call: ...
-int launch_rope_append_varlen(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen.hip; with bf16 elements: ...
-int launch_rope_append_varlen_bf16(const RopeAppendCall& c, const RopeAppendPtrs& p);   // ... tu_rope_append_varlen_bf16.hip; with pos_ids, fp16 or bf16: ...
-int launch_rope_append_varlen_pos(const RopeAppendCall& c, const RopeAppendPtrs& p);    // ... tu_rope_append_varlen_pos.hip
+// ... tu_rope_append_varlen_impl.h, instantiated once in each unit that holds such kernels: tu_rope_append_varlen.hip (fp16), tu_rope_append_varlen_bf16.hip
+// and tu_rope_append_varlen_pos.hip (RopeAppendCall::pos, fp16 and bf16)
+enum class RopeVarlenUnit { F16, BF16, POS };
+template <RopeVarlenUnit U>
+int launch_rope_append_varlen(const RopeAppendCall& c, const RopeAppendPtrs& p);
 
 }  // namespace lc

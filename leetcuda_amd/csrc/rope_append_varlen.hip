@@ -10,15 +10,30 @@
 //     q0 = clamp(cu_q[b], 0, T), Nq_b = clamp(cu_q[b + 1] - q0, 0, min(max_nq, T - q0)), i = t - q0, position p = L_b - Nq_b + i
 //   - a token no sequence owns (t >= cu_q[B], or i outside [0, Nq_b) under the clamps) writes nothing, in the pools or in Qout
 // Only t < T is ever used as a row: no value in cu_q takes a load or a store outside the T rows.
+//
+// The family is ONE body and three flags, every value of which exists.  A kernel's name states them:
+//   rope_append_varlen_ [pos_] [kv8_] [bf16_] kernel<D, INTERLEAVED>
+// KV8 (§4.3l): the pools are e4m3 bytes, and k_scale, v_scale follow kv_len; a 16-bit pool kernel takes neither.
+// BF16 (lc_rope_append_varlen_*bf16; §4.3m): sources, Qout and 16-bit pools are bfloat16.  The body — the lane map, the binary search of cu_q, the
+//   clamps and the drop rules — is the same, with rope_rotate8_bf16 (rope_append_paged.hip) and kv8_quantize8_bf16 (kv_append_paged.hip) in place
+//   of the fp16 functions:
+//   - a bf16 element IS the upper half of its fp32 value: the decode is a shift, exact, denormals included
+//   - the arithmetic is rope_fma, the fp16 kernels' one rounded product and one fma in fp32, then ONE rounding to bf16 (RNE, v_cvt_pk_bf16_f32;
+//     bf16 denormals are fp32 denormals and are kept).  Elements at or behind rot_dim, and all of V, are copied bit for bit
+//   - fp8 pools: code = e4m3fn_rne(clamp(fp32(x) / s, -448, 448)) with the true division, taken of the rotated row ROUNDED TO bf16 first, so
+//     that the pool equals what a bf16 pool quantised afterwards would hold.  A NaN is found on the bf16 bits ((h & 0x7fff) > 0x7f80) and on the
+//     quotient; its code gets 0x7F or-ed in.  +-inf gives +-448
+//   The fp16 flavours (rope_rotate8, kv8_quot2, kv8_quantize8) stay what they are; the bf16 ones are defined next to them.
+// POS (lc_rope_append_varlen_pos_*; §4.3o): the rotary position of every token is stated by the caller, pos_ids (device int32[T]) behind
+//   kv_row_stride.  The nodes of a draft tree sit in neighbouring cache slots, but a node's rotary position is prefix length + depth: siblings
+//   share one.  It changes ONE thing: the cos_sin row of token t is clamp(pos_ids[t], 0, max_pos - 1) in place of clamp(p, 0, max_pos - 1).  The
+//   cache slot p = L_b - Nq_b + i, the p < 0 rule, dropped tokens, quantisation, strides and in-place Q are the twin's; pos_ids[t] = p for every
+//   token gives the twin's bytes.  pos_ids is read only for a token that a sequence owns.
 #pragma once
 #include "rope_append_paged.hip"
 
 namespace lc {
 
-// BF16 (rope_append_varlen_bf16.hip): the 16-bit elements are bfloat16 — rope_rotate8_bf16 and kv8_quantize8_bf16 in place of
-// rope_rotate8 and kv8_quantize8, nothing else
-// POS (rope_append_varlen_pos.hip): the cos_sin row of token t is pos_ids[t] (device int32[T]) under the same clamp, not the
-// cache slot p; where the token is written, the p < 0 rule and the drop rules keep following p
 template <int D, bool INTERLEAVED, bool KV8, bool BF16 = false, bool POS = false>
 LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew, half_t* Qout,
                                        void* __restrict__ Kpool, void* __restrict__ Vpool, const float* __restrict__ cos_sin,
@@ -95,29 +110,64 @@ LC_DEVINL void rope_append_varlen_body(const half_t* Q, const half_t* __restrict
   }
 }
 
-// grid: nblk x (Hkv + H) workgroups of 256, nblk = ceil(T / (2048 / D)), the first Hkv x nblk of them K/V; lps = log2(page_size)
-template <int D, bool INTERLEAVED>
-__global__ __launch_bounds__(256) void rope_append_varlen_kernel(const half_t* Q, const half_t* __restrict__ Knew, const half_t* __restrict__ Vnew,
-                                                                 half_t* Qout, half_t* __restrict__ Kpool, half_t* __restrict__ Vpool,
-                                                                 const float* __restrict__ cos_sin, const int* __restrict__ cu_q,
-                                                                 const int* __restrict__ block_table, const int* __restrict__ kv_len, int B, int H,
-                                                                 int Hkv, int T, int max_nq, int num_pages, int lps, int max_pages, int nblk,
-                                                                 int rot_dim, int max_pos, long long q_row_stride, long long kv_row_stride) {
-  rope_append_varlen_body<D, INTERLEAVED, false>(Q, Knew, Vnew, Qout, Kpool, Vpool, cos_sin, cu_q, block_table, kv_len, nullptr, nullptr, B, H, Hkv, T,
-                                                 max_nq, num_pages, lps, max_pages, nblk, rot_dim, max_pos, q_row_stride, kv_row_stride);
-}
+// The eight kernels: the body behind the argument list its flags select.  grid: nblk x (Hkv + H) workgroups of 256, nblk = ceil(T / (2048 / D)),
+// the first Hkv x nblk of them K/V; lps = log2(page_size).  RopeVarlenKernel<KV8, BF16, POS>::kernel<D, INTERLEAVED>() hands a kernel to the
+// launcher (tu_rope_append_varlen_impl.h), so a launcher cannot name a kernel of other flags
+template <bool KV8, bool BF16, bool POS>
+struct RopeVarlenKernel;
 
-template <int D, bool INTERLEAVED>
-__global__ __launch_bounds__(256) void rope_append_varlen_kv8_kernel(const half_t* Q, const half_t* __restrict__ Knew,
-                                                                     const half_t* __restrict__ Vnew, half_t* Qout, uint8_t* __restrict__ Kpool8,
-                                                                     uint8_t* __restrict__ Vpool8, const float* __restrict__ cos_sin,
-                                                                     const int* __restrict__ cu_q, const int* __restrict__ block_table,
-                                                                     const int* __restrict__ kv_len, const float* __restrict__ k_scale,
-                                                                     const float* __restrict__ v_scale, int B, int H, int Hkv, int T, int max_nq,
-                                                                     int num_pages, int lps, int max_pages, int nblk, int rot_dim, int max_pos,
-                                                                     long long q_row_stride, long long kv_row_stride) {
-  rope_append_varlen_body<D, INTERLEAVED, true>(Q, Knew, Vnew, Qout, Kpool8, Vpool8, cos_sin, cu_q, block_table, kv_len, k_scale, v_scale, B, H, Hkv, T,
-                                                max_nq, num_pages, lps, max_pages, nblk, rot_dim, max_pos, q_row_stride, kv_row_stride);
-}
+#define LC_ROPE_VARLEN_POOLS_false half_t *__restrict__ Kpool, half_t *__restrict__ Vpool
+#define LC_ROPE_VARLEN_POOLS_true uint8_t *__restrict__ Kpool8, uint8_t *__restrict__ Vpool8
+#define LC_ROPE_VARLEN_POOLS_USE_false Kpool, Vpool
+#define LC_ROPE_VARLEN_POOLS_USE_true Kpool8, Vpool8
+#define LC_ROPE_VARLEN_SCALES_false
+#define LC_ROPE_VARLEN_SCALES_true const float *__restrict__ k_scale, const float *__restrict__ v_scale,
+#define LC_ROPE_VARLEN_SCALES_USE_false nullptr, nullptr
+#define LC_ROPE_VARLEN_SCALES_USE_true k_scale, v_scale
+#define LC_ROPE_VARLEN_POS_false
+#define LC_ROPE_VARLEN_POS_true , const int *__restrict__ pos_ids
+#define LC_ROPE_VARLEN_POS_USE_false
+#define LC_ROPE_VARLEN_POS_USE_true , pos_ids
+#define LC_ROPE_VARLEN_KERNEL(NAME, KV8_, BF16_, POS_)                                                                                          \
+  template <int D, bool INTERLEAVED>                                                                                                           \
+  __global__ __launch_bounds__(256) void NAME(const half_t *Q, const half_t *__restrict__ Knew, const half_t *__restrict__ Vnew, half_t *Qout, \
+                                              LC_ROPE_VARLEN_POOLS_##KV8_, const float *__restrict__ cos_sin, const int *__restrict__ cu_q,    \
+                                              const int *__restrict__ block_table, const int *__restrict__ kv_len, LC_ROPE_VARLEN_SCALES_##KV8_ \
+                                              int B, int H, int Hkv, int T, int max_nq, int num_pages, int lps, int max_pages, int nblk,       \
+                                              int rot_dim, int max_pos, long long q_row_stride,                                                \
+                                              long long kv_row_stride LC_ROPE_VARLEN_POS_##POS_) {                                             \
+    rope_append_varlen_body<D, INTERLEAVED, KV8_, BF16_, POS_>(Q, Knew, Vnew, Qout, LC_ROPE_VARLEN_POOLS_USE_##KV8_, cos_sin, cu_q, block_table, \
+                                                               kv_len, LC_ROPE_VARLEN_SCALES_USE_##KV8_, B, H, Hkv, T, max_nq, num_pages, lps, \
+                                                               max_pages, nblk, rot_dim, max_pos, q_row_stride,                                \
+                                                               kv_row_stride LC_ROPE_VARLEN_POS_USE_##POS_);                                   \
+  }                                                                                                                                            \
+  template <>                                                                                                                                  \
+  struct RopeVarlenKernel<KV8_, BF16_, POS_> {                                                                                                 \
+    template <int D, bool INTERLEAVED>                                                                                                         \
+    static auto kernel() { return NAME<D, INTERLEAVED>; }                                                                                      \
+  };
+
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_kernel, false, false, false)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_kv8_kernel, true, false, false)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_bf16_kernel, false, true, false)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_kv8_bf16_kernel, true, true, false)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_pos_kernel, false, false, true)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_pos_kv8_kernel, true, false, true)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_pos_bf16_kernel, false, true, true)
+LC_ROPE_VARLEN_KERNEL(rope_append_varlen_pos_kv8_bf16_kernel, true, true, true)
+
+#undef LC_ROPE_VARLEN_POOLS_false
+#undef LC_ROPE_VARLEN_POOLS_true
+#undef LC_ROPE_VARLEN_POOLS_USE_false
+#undef LC_ROPE_VARLEN_POOLS_USE_true
+#undef LC_ROPE_VARLEN_SCALES_false
+#undef LC_ROPE_VARLEN_SCALES_true
+#undef LC_ROPE_VARLEN_SCALES_USE_false
+#undef LC_ROPE_VARLEN_SCALES_USE_true
+#undef LC_ROPE_VARLEN_POS_false
+#undef LC_ROPE_VARLEN_POS_true
+#undef LC_ROPE_VARLEN_POS_USE_false
+#undef LC_ROPE_VARLEN_POS_USE_true
+#undef LC_ROPE_VARLEN_KERNEL
 
 }  // namespace lc

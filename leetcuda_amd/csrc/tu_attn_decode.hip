@@ -31,21 +31,31 @@ constexpr DecodeRanges kChunkRanges[] = {launch_attn_chunk_ranges<DecodeCache::F
 // ... and of a local plan, whatever its RB (tu_attn_local*.hip)
 constexpr DecodeRanges kLocalRanges[] = {launch_attn_local_ranges<DecodeCache::FLAT>, launch_attn_local_ranges<DecodeCache::PAGED>,
                                          launch_attn_local_ranges<DecodeCache::PAGED_KV8>};
-// ... and of a varlen plan (tu_attn_varlen_paged*.hip): a ragged batch only exists on a paged cache
-constexpr DecodeRanges kVarlenRanges[] = {nullptr, launch_attn_varlen_ranges<DecodeCache::PAGED>, launch_attn_varlen_ranges<DecodeCache::PAGED_KV8>};
-// ... with bf16 elements (tu_attn_varlen_paged*_bf16.hip)
-constexpr DecodeRanges kVarlenBf16Ranges[] = {nullptr, launch_attn_varlen_bf16_ranges<DecodeCache::PAGED>,
-                                              launch_attn_varlen_bf16_ranges<DecodeCache::PAGED_KV8>};
-// ... that also write the log-sum-exp (tu_attn_varlen_paged*_lse*.hip)
-constexpr DecodeRanges kVarlenLseRanges[] = {nullptr, launch_attn_varlen_lse_ranges<DecodeCache::PAGED>,
-                                             launch_attn_varlen_lse_ranges<DecodeCache::PAGED_KV8>};
-constexpr DecodeRanges kVarlenLseBf16Ranges[] = {nullptr, launch_attn_varlen_lse_bf16_ranges<DecodeCache::PAGED>,
-                                                 launch_attn_varlen_lse_bf16_ranges<DecodeCache::PAGED_KV8>};
-// ... with a look-back visibility mask per query token (tu_attn_varlen_paged*_tree*.hip); tree implies lse: the combine launches are the LSE plan's
-constexpr DecodeRanges kVarlenTreeRanges[] = {nullptr, launch_attn_varlen_tree_ranges<DecodeCache::PAGED>,
-                                              launch_attn_varlen_tree_ranges<DecodeCache::PAGED_KV8>};
-constexpr DecodeRanges kVarlenTreeBf16Ranges[] = {nullptr, launch_attn_varlen_tree_bf16_ranges<DecodeCache::PAGED>,
-                                                  launch_attn_varlen_tree_bf16_ranges<DecodeCache::PAGED_KV8>};
+
+// ... and of a varlen plan (tu_attn_varlen_paged*.hip; a ragged batch only exists on a paged cache): a ladder from the call's cache kind, bf16, lse
+// and tree to the one launcher instantiated for them — what a call states is what it launches
+template <DecodeCache C, bool BF16>
+int varlen_ranges_out(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
+  if (p.call.tree) return launch_attn_varlen_ranges<C, BF16, VarlenOut::TREE>(p, S, a, part_o, part_lse);
+  if (p.call.lse) return launch_attn_varlen_ranges<C, BF16, VarlenOut::LSE>(p, S, a, part_o, part_lse);
+  return launch_attn_varlen_ranges<C, BF16, VarlenOut::PLAIN>(p, S, a, part_o, part_lse);
+}
+template <DecodeCache C>
+int varlen_ranges_bf16(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
+  return p.call.bf16 ? varlen_ranges_out<C, true>(p, S, a, part_o, part_lse) : varlen_ranges_out<C, false>(p, S, a, part_o, part_lse);
+}
+int varlen_ranges(const DecodePlan& p, int S, const DecodePtrs& a, float* part_o, float* part_lse) {
+  return p.cache == DecodeCache::PAGED_KV8 ? varlen_ranges_bf16<DecodeCache::PAGED_KV8>(p, S, a, part_o, part_lse)
+                                           : varlen_ranges_bf16<DecodeCache::PAGED>(p, S, a, part_o, part_lse);
+}
+// (rows past cu_q[B] are nobody's: a varlen plan has combine kernels of its own, by bf16 and lse)
+template <bool BF16>
+int varlen_combine_lse(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
+  return p.call.lse ? launch_attn_varlen_combine<BF16, true>(p, S, a, part_o, part_lse) : launch_attn_varlen_combine<BF16, false>(p, S, a, part_o, part_lse);
+}
+int varlen_combine(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
+  return p.call.bf16 ? varlen_combine_lse<true>(p, S, a, part_o, part_lse) : varlen_combine_lse<false>(p, S, a, part_o, part_lse);
+}
 
 template <int D>
 int launch_decode_combine(long rows, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
@@ -72,11 +82,10 @@ int launch_attn_decode(const DecodePlan& p, const DecodePtrs& a, void* workspace
   const long rows = (long)decode_rows(p.call);
   float* part_o = S > 1 ? part : nullptr;
   float* part_lse = S > 1 ? part + (size_t)S * rows * p.call.D : nullptr;
-  const int rc = (p.call.tree ? (p.call.bf16 ? kVarlenTreeBf16Ranges : kVarlenTreeRanges) : p.call.lse ? (p.call.bf16 ? kVarlenLseBf16Ranges : kVarlenLseRanges) : p.call.bf16 ? kVarlenBf16Ranges : p.call.varlen ? kVarlenRanges : p.local ? kLocalRanges : p.RB > 1 ? kChunkRanges : kDecodeRanges)[(int)p.cache](p, S, a, part_o, part_lse);
+  // (bf16, lse and tree are stated by the varlen entries only)
+  const int rc = p.call.varlen ? varlen_ranges(p, S, a, part_o, part_lse) : (p.local ? kLocalRanges : p.RB > 1 ? kChunkRanges : kDecodeRanges)[(int)p.cache](p, S, a, part_o, part_lse);
   if (rc != LC_OK || S == 1) return rc;
-  if (p.call.lse) return p.call.bf16 ? launch_attn_varlen_combine_lse_bf16(p, S, a, part_o, part_lse) : launch_attn_varlen_combine_lse(p, S, a, part_o, part_lse);
-  if (p.call.bf16) return launch_attn_varlen_combine_bf16(p, S, a, part_o, part_lse);
-  if (p.call.varlen) return launch_attn_varlen_combine(p, S, a, part_o, part_lse);   // (rows past cu_q[B] are nobody's: its own combine kernel)
+  if (p.call.varlen) return varlen_combine(p, S, a, part_o, part_lse);
   return p.call.D == 128 ? launch_decode_combine<128>(rows, S, a, part_o, part_lse) : launch_decode_combine<64>(rows, S, a, part_o, part_lse);
 }
 

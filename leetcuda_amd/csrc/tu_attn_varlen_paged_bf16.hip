@@ -1,40 +1,7 @@
-// tu_attn_varlen_paged_bf16.hip — translation unit of the bfloat16 ragged-batch kernels over the 16-bit paged cache (attn_varlen_bf16.hip:
-// attn_varlen_paged_bf16_kernel<D, RT>, attn_varlen_chunk_paged_bf16_kernel<D>) and of attn_varlen_combine_bf16_kernel<D>, which serves both
-// cache kinds: the range launcher of a bf16 varlen DecodePlan over DecodeCache::PAGED and the combine launch of every bf16 varlen plan.
-// launch_attn_decode (tu_attn_decode.hip) decides S and the partials, as for the fp16 plans
-#include <tuple>
-
-#include "attn_varlen_bf16.hip"
-#include "lc_plan.h"
-
-#define VARLEN_KERNEL attn_varlen_paged_bf16_kernel
-#define VARLEN_CHUNK_KERNEL attn_varlen_chunk_paged_bf16_kernel
+// tu_attn_varlen_paged_bf16.hip — the bfloat16 ragged-batch kernels over the 16-bit paged cache (attn_varlen_paged_bf16_kernel<D, RT>,
+// attn_varlen_chunk_paged_bf16_kernel<D>) and attn_varlen_combine_bf16_kernel<D>, which serves both cache kinds
 #define VARLEN_CACHE DecodeCache::PAGED
-#define VARLEN_KV_T half_t
-#define VARLEN_RANGES launch_attn_varlen_bf16_ranges
-namespace lc {
-namespace {
-auto varlen_mid(const DecodePtrs& a) { return std::make_tuple(a.block_table); }
-auto varlen_tail(const DecodeCall& c) { return std::make_tuple(c.num_pages, __builtin_ctz((unsigned)c.page_size), c.max_pages); }
-}  // namespace
-}  // namespace lc
+#define VARLEN_BF16 true
+#define VARLEN_OUT VarlenOut::PLAIN
+#define VARLEN_COMBINE
 #include "tu_attn_varlen_impl.h"
-
-namespace lc {
-namespace {
-
-template <int D>
-int launch_varlen_combine_bf16_d(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
-  constexpr int rows_per_block = 256 / (D / 4);
-  const long rows = (long)p.call.T * p.call.H;
-  return launch_attn_kernel(attn_varlen_combine_bf16_kernel<D>, dim3((unsigned)((rows + rows_per_block - 1) / rows_per_block)), dim3(256), 0, a.st,
-                            part_o, part_lse, a.O, a.cu_q, p.call.B, p.call.T, p.call.H, S);
-}
-
-}  // namespace
-
-int launch_attn_varlen_combine_bf16(const DecodePlan& p, int S, const DecodePtrs& a, const float* part_o, const float* part_lse) {
-  return p.call.D == 128 ? launch_varlen_combine_bf16_d<128>(p, S, a, part_o, part_lse) : launch_varlen_combine_bf16_d<64>(p, S, a, part_o, part_lse);
-}
-
-}  // namespace lc

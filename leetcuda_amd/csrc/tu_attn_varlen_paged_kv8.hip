@@ -1,19 +1,6 @@
-// tu_attn_varlen_paged_kv8.hip — translation unit of the ragged-batch kernels over the fp8 paged cache (attn_varlen.hip:
-// attn_varlen_paged_kv8_kernel<D, RT>, attn_varlen_chunk_paged_kv8_kernel<D>): the range launcher of a varlen DecodePlan over
-// DecodeCache::PAGED_KV8.  launch_attn_decode (tu_attn_decode.hip) decides S and the partials; the combine kernel lives in tu_attn_varlen_paged.hip
-#include <tuple>
-
-#include "attn_varlen.hip"
-#include "lc_plan.h"
-
-#define VARLEN_KERNEL attn_varlen_paged_kv8_kernel
-#define VARLEN_CHUNK_KERNEL attn_varlen_chunk_paged_kv8_kernel
+// tu_attn_varlen_paged_kv8.hip — the fp16 ragged-batch kernels over the fp8 paged cache (attn_varlen_paged_kv8_kernel<D, RT>,
+// attn_varlen_chunk_paged_kv8_kernel<D>).  The combine kernel is tu_attn_varlen_paged.hip's
 #define VARLEN_CACHE DecodeCache::PAGED_KV8
-#define VARLEN_KV_T uint8_t
-namespace lc {
-namespace {
-auto varlen_mid(const DecodePtrs& a) { return std::make_tuple(a.block_table, a.k_scale, a.v_scale); }
-auto varlen_tail(const DecodeCall& c) { return std::make_tuple(c.num_pages, __builtin_ctz((unsigned)c.page_size), c.max_pages); }
-}  // namespace
-}  // namespace lc
+#define VARLEN_BF16 false
+#define VARLEN_OUT VarlenOut::PLAIN
 #include "tu_attn_varlen_impl.h"

@@ -767,25 +767,17 @@ int check_attn_decode(const DecodeCall& c, const DecodePtrs* a, DecodePlan* p) {
 void format_attn_decode(const DecodePlan& p, char* buf, int buflen) {
   static const char* const kKernels[] = {"attn_decode_kernel", "attn_decode_paged_kernel", "attn_decode_paged_kv8_kernel"};   // by DecodeCache
   static const char* const kLocal[] = {"attn_local_kernel", "attn_local_paged_kernel", "attn_local_paged_kv8_kernel"};
-  static const char* const kVarlen[] = {"", "attn_varlen_paged_kernel", "attn_varlen_paged_kv8_kernel"};
-  static const char* const kVarlenBf16[] = {"", "attn_varlen_paged_bf16_kernel", "attn_varlen_paged_kv8_bf16_kernel"};   // (DecodeCall::bf16: varlen only)
-  // (DecodeCall::lse: varlen only — the twin plan's name with "_lse" in it)
-  static const char* const kVarlenLse[] = {"", "attn_varlen_paged_lse_kernel", "attn_varlen_paged_kv8_lse_kernel"};
-  static const char* const kVarlenLseBf16[] = {"", "attn_varlen_paged_lse_bf16_kernel", "attn_varlen_paged_kv8_lse_bf16_kernel"};
-  // (DecodeCall::tree: lse calls only — the LSE plan's name with "tree" in place of "lse")
-  static const char* const kVarlenTree[] = {"", "attn_varlen_paged_tree_kernel", "attn_varlen_paged_kv8_tree_kernel"};
-  static const char* const kVarlenTreeBf16[] = {"", "attn_varlen_paged_tree_bf16_kernel", "attn_varlen_paged_kv8_tree_bf16_kernel"};
-  const char* kern = (p.call.tree ? (p.call.bf16 ? kVarlenTreeBf16 : kVarlenTree) : p.call.lse ? (p.call.bf16 ? kVarlenLseBf16 : kVarlenLse) : p.call.bf16 ? kVarlenBf16 : p.call.varlen ? kVarlen : p.local ? kLocal : kKernels)[(int)p.cache];
+  const char* kern = (p.local ? kLocal : kKernels)[(int)p.cache];
+  char ragged[64];
+  if (p.call.varlen) {   // attn_varlen_ [chunk_] paged_ [kv8_] [lse_ | tree_] [bf16_] kernel, from the fields the launch is reached by (bf16, lse, tree: varlen only)
+    snprintf(ragged, sizeof ragged, "attn_varlen_%spaged_%s%s%skernel", p.RB > 1 ? "chunk_" : "", p.cache == DecodeCache::PAGED_KV8 ? "kv8_" : "",
+             p.call.tree ? "tree_" : p.call.lse ? "lse_" : "", p.call.bf16 ? "bf16_" : "");
+    kern = ragged;
+  }
   if (p.RB > 1) {   // (the chunk kernels have four row tiles and say so nowhere)
     static const char* const kChunk[] = {"attn_chunk_kernel", "attn_chunk_paged_kernel", "attn_chunk_paged_kv8_kernel"};
     static const char* const kLocalChunk[] = {"attn_local_chunk_kernel", "attn_local_chunk_paged_kernel", "attn_local_chunk_paged_kv8_kernel"};
-    static const char* const kVarlenChunk[] = {"", "attn_varlen_chunk_paged_kernel", "attn_varlen_chunk_paged_kv8_kernel"};
-    static const char* const kVarlenChunkBf16[] = {"", "attn_varlen_chunk_paged_bf16_kernel", "attn_varlen_chunk_paged_kv8_bf16_kernel"};
-    static const char* const kVarlenChunkLse[] = {"", "attn_varlen_chunk_paged_lse_kernel", "attn_varlen_chunk_paged_kv8_lse_kernel"};
-    static const char* const kVarlenChunkLseBf16[] = {"", "attn_varlen_chunk_paged_lse_bf16_kernel", "attn_varlen_chunk_paged_kv8_lse_bf16_kernel"};
-    static const char* const kVarlenChunkTree[] = {"", "attn_varlen_chunk_paged_tree_kernel", "attn_varlen_chunk_paged_kv8_tree_kernel"};
-    static const char* const kVarlenChunkTreeBf16[] = {"", "attn_varlen_chunk_paged_tree_bf16_kernel", "attn_varlen_chunk_paged_kv8_tree_bf16_kernel"};
-    const char* chunk = (p.call.tree ? (p.call.bf16 ? kVarlenChunkTreeBf16 : kVarlenChunkTree) : p.call.lse ? (p.call.bf16 ? kVarlenChunkLseBf16 : kVarlenChunkLse) : p.call.bf16 ? kVarlenChunkBf16 : p.call.varlen ? kVarlenChunk : p.local ? kLocalChunk : kChunk)[(int)p.cache];
+    const char* chunk = p.call.varlen ? kern : (p.local ? kLocalChunk : kChunk)[(int)p.cache];
     if (p.S > 1) snprintf(buf, buflen, "%s<%d> x%d", chunk, p.call.D, p.S);
     else snprintf(buf, buflen, "%s<%d>", chunk, p.call.D);
     return;
@@ -859,13 +851,9 @@ int check_rope_append(const RopeAppendCall& c, const RopeAppendPtrs* p) {
   return rc;
 }
 void format_rope_append(const RopeAppendCall& c, char* buf, int buflen) {
-  const char* fmt = c.a.kv_bytes == 1 ? "rope_append_paged_kv8_kernel<%d,%s>" : "rope_append_paged_kernel<%d,%s>";
-  if (c.varlen) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_kernel<%d,%s>" : "rope_append_varlen_kernel<%d,%s>";
-  if (c.bf16) fmt = c.a.kv_bytes == 1 ? "rope_append_varlen_kv8_bf16_kernel<%d,%s>" : "rope_append_varlen_bf16_kernel<%d,%s>";   // (varlen only)
-  if (c.pos)   // (varlen only)
-    fmt = c.bf16 ? (c.a.kv_bytes == 1 ? "rope_append_varlen_pos_kv8_bf16_kernel<%d,%s>" : "rope_append_varlen_pos_bf16_kernel<%d,%s>")
-                 : (c.a.kv_bytes == 1 ? "rope_append_varlen_pos_kv8_kernel<%d,%s>" : "rope_append_varlen_pos_kernel<%d,%s>");
-  snprintf(buf, buflen, fmt, c.a.D, c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
+  // rope_append_paged_ [kv8_] kernel; a varlen call: rope_append_varlen_ [pos_] [kv8_] [bf16_] kernel (bf16: §4.3m, pos: §4.3o — varlen only)
+  snprintf(buf, buflen, "rope_append_%s%s%s%skernel<%d,%s>", c.varlen ? "varlen_" : "paged_", c.pos ? "pos_" : "", c.a.kv_bytes == 1 ? "kv8_" : "",
+           c.bf16 ? "bf16_" : "", c.a.D, c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
 }
 
 // The name of what an attention plan launches (lc_attn_kernel_name_bh / _ex; bench.py, tools/ and the tests parse these strings).

@@ -64,13 +64,13 @@ OWNED_AGPRS = [
     # ... and the ragged-batch kernels (attn_varlen.hip: the decode body with VARLEN = true; rope_append_varlen.hip)
     (re.compile(r"attn_varlen_(chunk_)?paged_(kv8_)?kernel|attn_varlen_combine_kernel"), []),
     (re.compile(r"rope_append_varlen_kernel|rope_append_varlen_kv8_kernel"), []),
-    # ... and their bfloat16 flavours (attn_varlen_bf16.hip, rope_append_varlen_bf16.hip)
+    # ... and their bfloat16 flavours (attn_varlen.hip, rope_append_varlen.hip)
     (re.compile(r"attn_varlen_(chunk_)?paged_(kv8_)?bf16_kernel|attn_varlen_combine_bf16_kernel"), []),
     (re.compile(r"rope_append_varlen_bf16_kernel|rope_append_varlen_kv8_bf16_kernel"), []),
-    # ... and the ragged-batch kernels that also write the log-sum-exp (attn_varlen_lse.hip), and the merge of two states (attn_merge.hip)
+    # ... and the ragged-batch kernels that also write the log-sum-exp (attn_varlen.hip), and the merge of two states (attn_merge.hip)
     (re.compile(r"attn_varlen_(chunk_)?paged_(kv8_)?lse_(bf16_)?kernel|attn_varlen_combine_lse_(bf16_)?kernel"), []),
     (re.compile(r"attn_merge_states_(bf16_)?kernel"), []),
-    # ... and the ragged-batch kernels with a look-back visibility mask (attn_varlen_tree.hip), and per-token rotary positions (rope_append_varlen_pos.hip)
+    # ... and the ragged-batch kernels with a look-back visibility mask (attn_varlen.hip), and per-token rotary positions (rope_append_varlen.hip)
     (re.compile(r"attn_varlen_(chunk_)?paged_(kv8_)?tree_(bf16_)?kernel"), []),
     (re.compile(r"rope_append_varlen_pos_(kv8_)?(bf16_)?kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
