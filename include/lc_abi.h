@@ -776,6 +776,44 @@ int lc_attn_merge_states_f16(const void* Oa, const float* lse_a, const void* Ob,
 int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out,
                               const int* cu_q, int B, int T, int H, int D, void* stream);
 
+/* EXTENSION: multi-head latent attention (MLA, the absorbed decode form of DeepSeek-V2 / V3 / R1 and Kimi-K2) over a paged LATENT cache
+ * (attn_mla.hip).  The cache holds per token ONE Dc = 512 wide compressed latent row and ONE Dr = 64 wide rotated key
+ * row, shared by every query head; the latent row is both key and value.  For a ragged batch exactly as in lc_attn_varlen_paged_* (cu_q, T,
+ * max_nq and their clamps; kv_len[b] the length after the step's append; query token i of sequence b at position p = L_b - Nq_b + i), query
+ * token t, head h and each visible key j (j < L_b; with LC_ATTN_CAUSAL: j <= p):
+ *   s_j = sm_scale (sum_{d < 512} Qc[t,h,d] CKV[j,d] + sum_{d < 64} Qpe[t,h,d] KPE[j,d]),   O[t,h,:] = sum_j softmax_j(s) CKV[j,:],
+ *   lse[t,h] = ln sum_j exp(s_j)   (natural units; -inf, and O = 0, for a row that sees no key)
+ *   Qc, Qpe, O   [T,H,512], [T,H,64], [T,H,512], token-major, 16-bit (fp16, _bf16: bfloat16), 16-byte aligned
+ *   lse          device float32 [T H], or NULL for none
+ *   CKVpool, KPEpool   [num_pages, page_size, 512] and [num_pages, page_size, 64] in the element type of Q: the library's
+ *                [num_pages, Hkv, page_size, D] with Hkv = 1 (FlashInfer's MLA layout); page_size a power of two >= 16
+ *   block_table [B, max_pages], the clamp of page ids into the pool, the clamp of kv_len to max_pages page_size and "entries past
+ *                ceil(L_b / page_size) are not read": the paged entries' rules.  Rows no sequence owns are written in neither O nor lse.
+ *   sm_scale     the caller's scale, a host float: it depends on the model's qk_nope_head_dim + qk_rope_head_dim and on YaRN's mscale, not on 576
+ * Products accumulate in fp32, the softmax state, the split-KV partials and their merge are fp32, P is rounded to the element type for the
+ * value product while the row sum keeps the unrounded value, O is rounded once (nearest even).
+ * Status, in this order: an unknown flag (only LC_ATTN_CAUSAL is defined), a NULL pointer other than lse, sm_scale not finite or <= 0:
+ * LC_ERR_ARG; a non-positive dim, max_nq > T, a bad page_size, max_pages page_size 512 2 >= 2 GiB, T H > 2^31 - 1, the grid bound, a
+ * pointer off 16 bytes: LC_ERR_SHAPE; (Dc, Dr) != (512, 64): LC_ERR_HEADDIM; a non-NULL workspace that is too small or off 16 bytes:
+ * LC_ERR_ARG.  attn_mla_paged_kernel<BF16> on B x ceil(H max_nq / 64) x S workgroups; S > 1 (never from device data; "attn_decode_split"
+ * forces it): S x T H x 513 floats of workspace — the caller's, which makes S > 1 legal under graph capture, else the stream's cached one; a
+ * captured stream or a failed lease runs S = 1 — and attn_mla_combine_kernel<BF16>.  lc_attn_mla_paged_workspace_bytes: those bytes (0: S = 1
+ * or a refused shape); lc_attn_mla_paged_kernel_name: "attn_mla_paged_kernel" / "attn_mla_paged_bf16_kernel", S > 1:
+ * "... + attn_mla_combine_kernel xS"; it returns the status the run call would give.
+ * Not here: writing the latent cache, an fp8 latent cache, windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed
+ * prefill form (plain attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512. */
+int lc_attn_mla_paged_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
+                          const int* cu_q, const int* block_table, const int* kv_len,
+                          int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                          int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_mla_paged_bf16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
+                           const int* cu_q, const int* block_table, const int* kv_len,
+                           int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                           int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_mla_paged_workspace_bytes(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr);
+int lc_attn_mla_paged_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16,
+                                  char* buf, int buflen);
+
 /* EXTENSION: tree-structured speculative decoding on the ragged entries — a look-back visibility mask per query token, and per-token rotary
  * positions (attn_varlen_tree.hip, rope_append_varlen_pos.hip).  The new tokens of a sequence are the nodes of a draft
  * tree (Medusa, EAGLE, SpecInfer), appended to neighbouring cache slots: a node must see the prefix and its own ancestors, never its siblings,

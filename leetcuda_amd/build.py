@@ -43,7 +43,12 @@ AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_a
                     "tu_attn_varlen_paged_tree": "isa_audit_varlen_paged_tree.json", "tu_attn_varlen_paged_kv8_tree": "isa_audit_varlen_paged_kv8_tree.json",
                     "tu_attn_varlen_paged_tree_bf16": "isa_audit_varlen_paged_tree_bf16.json",
                     "tu_attn_varlen_paged_kv8_tree_bf16": "isa_audit_varlen_paged_kv8_tree_bf16.json",
-                    "tu_rope_append_varlen_pos": "isa_audit_rope_append_varlen_pos.json"}
+                    "tu_rope_append_varlen_pos": "isa_audit_rope_append_varlen_pos.json", "tu_attn_mla": "isa_audit_mla.json"}
+
+# Extra compiler flags of single translation units (object and audit assembly alike; part of the unit's digest).  tu_attn_mla: no packed
+# fp32 VALU instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) from the compiler; the older units keep the flags their assembly was
+# compared under.
+UNIT_FLAGS = {"tu_attn_mla": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(target: Path, sources) -> bool:
@@ -171,7 +176,7 @@ def build_abi(force: bool = False, audit: bool = True) -> Path:
     if os.environ.get("LC_DIAG") == "1":   # the ablation loops (results WRONG by design) exist only inside a diagnosis build
         subprocess.run([sys.executable, str(ROOT / "tools" / "gen_hgemm_w4y.py"), "--diag", str(LIBDIR / "gen")], check=True)
         flags = flags + [f"-I{LIBDIR / 'gen'}"]
-    dg = _digest(srcs, " ".join(_portable(flags)))
+    dg = _digest(srcs, " ".join(_portable(flags)) + repr(sorted(UNIT_FLAGS.items())))
     if not force and _fresh(out, "abi", dg) and _stamp_ok(stamp, flags):
         return out
     # translation units (lc_abi.hip: the C-ABI; tu_plan.hip: the host-only launch planning; the kernels in the other tu_*.hip), compiled in
@@ -189,17 +194,18 @@ def build_abi(force: bool = False, audit: bool = True) -> Path:
         asm = objdir / (u.stem + ".s")
         dep = objdir / (u.stem + ".d")
         # per-unit staleness from the compiler's own dependency file (-MD): only units whose sources changed rebuild
-        if not force and flags_ok and _unit_current(obj, asm if audit else None, dep, flags):
+        uflags = flags + UNIT_FLAGS.get(u.stem, [])
+        if not force and flags_ok and _unit_current(obj, asm if audit else None, dep, uflags):
             procs.append((u, obj, None))
             continue
         for stale in (obj, asm):         # never leave yesterday's object / assembly behind a failed compile
             if stale.exists():
                 stale.unlink()
-        cmd = [hipcc(), *flags, "-MD", "-MF", str(dep), "-c", "-o", str(obj), str(u)]
+        cmd = [hipcc(), *uflags, "-MD", "-MF", str(dep), "-c", "-o", str(obj), str(u)]
         print("[build] " + " ".join(cmd), flush=True)
         procs.append((u, obj, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         if audit:
-            cmd = [hipcc(), *flags, "-S", "--cuda-device-only", "-Wno-unused-command-line-argument", "-o", str(asm), str(u)]
+            cmd = [hipcc(), *uflags, "-S", "--cuda-device-only", "-Wno-unused-command-line-argument", "-o", str(asm), str(u)]
             procs.append((u, None, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     objs = []
     for u, obj, pr in procs:
@@ -211,7 +217,7 @@ def build_abi(force: bool = False, audit: bool = True) -> Path:
         if obj is not None:
             objs.append(obj)
             if pr is not None:     # rebuilt: remember what it was built from
-                _mark("unit:" + obj.stem, _unit_digest(objdir / (obj.stem + ".d"), flags))
+                _mark("unit:" + obj.stem, _unit_digest(objdir / (obj.stem + ".d"), flags + UNIT_FLAGS.get(obj.stem, [])))
     if audit:
         from leetcuda_amd import isa_audit
         reps, bad = [], []

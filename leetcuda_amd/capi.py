@@ -137,6 +137,12 @@ SYMBOLS = {
     # merge of two (O, lse) states: Oa, lse_a, Ob, lse_b, Oout, lse_out, cu_q (or NULL), B, T, H, D, stream
     "lc_attn_merge_states_f16": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
     "lc_attn_merge_states_bf16": (_i, [_vp] * 7 + [_i] * 4 + [_vp]),
+    # multi-head latent attention: Qc, Qpe, CKVpool, KPEpool, O, lse (or NULL), cu_q, block_table, kv_len, B, H, T, max_nq, num_pages, page_size,
+    # max_pages, Dc, Dr, sm_scale, flags, workspace, workspace_bytes, stream
+    "lc_attn_mla_paged_f16": (_i, [_vp] * 9 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_paged_bf16": (_i, [_vp] * 9 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_paged_workspace_bytes": (C.c_size_t, [_i] * 8),
+    "lc_attn_mla_paged_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -1500,6 +1506,55 @@ def attn_cascade_paged(q, k_pool, v_pool, o, cu_groups, prefix_table, prefix_len
     _varlen_attn(q, k_pool, v_pool, o_p, lse_p, cu_groups, prefix_table, prefix_len, max_nq_prefix, ks, vs, False, 0, None, workspaces[0], kv8, bf16)
     _varlen_attn(q, k_pool, v_pool, o, lse, cu_q, block_table, kv_len, max_nq, ks, vs, True, 0, sinks, workspaces[1], kv8, bf16)
     return attn_merge_states(o, lse, o_p, lse_p, out=o, lse_out=lse, cu_q=cu_q)
+
+
+# Multi-head latent attention over a paged latent cache (lc_attn_mla_paged_f16 / _bf16): every query head reads the same
+# 512-wide latent row (key AND value) and 64-wide rotated key row of a token.
+
+def attn_mla_paged(q_c, q_pe, ckv_pool, kpe_pool, o, cu_q, block_table, kv_len, max_nq, sm_scale, lse=False, causal=False, workspace=None):
+    """MLA decode / chunk attention on a ragged batch (lc_attn_mla_paged_f16 / _bf16, picked by q_c's dtype): q_c, o [T,H,512], q_pe [T,H,64],
+    ckv_pool [num_pages,page_size,512], kpe_pool [num_pages,page_size,64], all float16 or all bfloat16; cu_q int32 [B + 1], block_table int32
+    [B,max_pages], kv_len int32 [B] (the lengths AFTER the step's append): DEVICE tensors read by the kernel only; 1 <= max_nq <= T bounds every
+    Nq_b; sm_scale the model's softmax scale (a float > 0).  lse False: returns o; None or a float32 [T,H] tensor: returns (o, lse), lse the
+    natural log of the row's softmax denominator (-inf: no visible key, O = 0).  workspace: None or a device tensor of at least
+    attn_mla_paged_workspace_bytes(...) bytes (makes the split-KV form legal under graph capture)."""
+    import torch
+    if q_c.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q_c must be float16 or bfloat16, got {q_c.dtype}")
+    if any(t.dtype != q_c.dtype for t in (q_pe, ckv_pool, kpe_pool, o)):
+        raise TypeError(f"q_c / q_pe / ckv_pool / kpe_pool / o must share one 16-bit dtype, got {q_c.dtype} / {q_pe.dtype} / {ckv_pool.dtype} / "
+                        f"{kpe_pool.dtype} / {o.dtype}")
+    if q_c.dim() != 3 or q_pe.dim() != 3 or ckv_pool.dim() != 3 or kpe_pool.dim() != 3:
+        _shape_err("3-D [T,H,Dc] / [T,H,Dr] / [num_pages,page_size,Dc] / [num_pages,page_size,Dr] tensors expected")
+    T, H, Dc = q_c.shape
+    Dr = q_pe.shape[2]
+    num_pages, page_size = ckv_pool.shape[:2]
+    if tuple(q_pe.shape) != (T, H, Dr) or tuple(o.shape) != (T, H, Dc) or ckv_pool.shape[2] != Dc or tuple(kpe_pool.shape) != (num_pages, page_size, Dr):
+        _shape_err(f"q_c {tuple(q_c.shape)} q_pe {tuple(q_pe.shape)} ckv_pool {tuple(ckv_pool.shape)} kpe_pool {tuple(kpe_pool.shape)} o {tuple(o.shape)}")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    plain = lse is False
+    outs = () if plain else (_lse_out(q_c, lse),)
+    _need_gpu(q_c, q_pe, ckv_pool, kpe_pool, o, *outs, cu_q, block_table, kv_len)
+    symbol = "lc_attn_mla_paged_bf16" if q_c.dtype == torch.bfloat16 else "lc_attn_mla_paged_f16"
+    check(getattr(load(), symbol)(_ptr(q_c), _ptr(q_pe), _ptr(ckv_pool), _ptr(kpe_pool), _ptr(o), _ptr(outs[0]) if outs else None, _ptr(cu_q),
+                                  _ptr(block_table), _ptr(kv_len), B, H, T, max_nq, num_pages, page_size, block_table.shape[1], Dc, Dr,
+                                  float(sm_scale), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace), _stream()), symbol)
+    return o if plain else (o, outs[0])
+
+
+def attn_mla_paged_workspace_bytes(B, H, T, max_nq, page_size, max_pages, Dc=512, Dr=64) -> int:
+    """Bytes of split-KV partials the current plan of this shape needs: S x T H x (Dc + 1) floats, 0 for one KV range or a refused shape."""
+    return int(load().lc_attn_mla_paged_workspace_bytes(B, H, T, max_nq, page_size, max_pages, Dc, Dr))
+
+
+def attn_mla_paged_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc=512, Dr=64, causal=False, bf16=False) -> str:
+    """"attn_mla_paged_kernel" / "attn_mla_paged_bf16_kernel", + " + attn_mla_combine_[bf16_]kernel xS" with S > 1 KV ranges."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_mla_paged_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc, Dr, ATTN_CAUSAL if causal else 0, int(bf16), buf, 128),
+          "lc_attn_mla_paged_kernel_name")
+    return buf.value.decode()
 
 
 def attn_fwd_bf16(q, k, v, o):

@@ -141,6 +141,20 @@ int merge_run(bool bf16, const void* Oa, const float* lse_a, const void* Ob, con
   return launch_attn_merge(c, p);
 }
 
+// The two latent-attention entries state an MlaCall; check_attn_mla (tu_plan.hip) checks and plans it, launch_attn_mla (tu_attn_mla.hip) runs it
+int mla_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse, const int* cu_q,
+            const int* block_table, const int* kv_len, int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages, int Dc, int Dr,
+            float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  const MlaCall c{B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, flags, sm_scale, bf16};
+  const MlaPtrs a{static_cast<const half_t*>(Qc), static_cast<const half_t*>(Qpe), static_cast<const half_t*>(CKVpool), static_cast<const half_t*>(KPEpool),
+                  static_cast<half_t*>(O), lse, cu_q, block_table, kv_len, static_cast<hipStream_t>(stream)};
+  MlaPlan p;
+  if (int rc = check_attn_mla(c, &a, &p)) return rc;
+  if (workspace && (workspace_bytes < mla_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_mla(p, a, workspace);
+}
+
 // The two append-to-cache entries (fp16 and fp8 pools) each state an AppendCall; check_kv_append (tu_plan.hip) checks it; append_run and append_name
 // run and name it.  (AppendCall: B, Hkv, Nq, D, flags, kv_bytes, num_pages, page_size, max_pages)
 int append_run(const AppendCall& c, const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len,
@@ -688,6 +702,35 @@ int lc_attn_merge_states_f16(const void* Oa, const float* lse_a, const void* Ob,
 int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob, const float* lse_b, void* Oout, float* lse_out, const int* cu_q, int B,
                               int T, int H, int D, void* stream) {
   return merge_run(true, Oa, lse_a, Ob, lse_b, Oout, lse_out, cu_q, B, T, H, D, stream);
+}
+
+// Multi-head latent attention over a paged latent cache (attn_mla.hip): mla_run above states an MlaCall
+int lc_attn_mla_paged_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse, const int* cu_q,
+                          const int* block_table, const int* kv_len, int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                          int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return mla_run(false, Qc, Qpe, CKVpool, KPEpool, O, lse, cu_q, block_table, kv_len, B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, sm_scale,
+                 flags, workspace, workspace_bytes, stream);
+}
+
+int lc_attn_mla_paged_bf16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse, const int* cu_q,
+                           const int* block_table, const int* kv_len, int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                           int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  return mla_run(true, Qc, Qpe, CKVpool, KPEpool, O, lse, cu_q, block_table, kv_len, B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, sm_scale,
+                 flags, workspace, workspace_bytes, stream);
+}
+
+size_t lc_attn_mla_paged_workspace_bytes(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr) {
+  MlaPlan p;
+  return check_attn_mla(MlaCall{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, 0, 1.f, false}, nullptr, &p) == LC_OK ? mla_workspace_bytes(p) : 0;
+}
+
+int lc_attn_mla_paged_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16, char* buf,
+                                  int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaPlan p;
+  if (int rc = check_attn_mla(MlaCall{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, flags, 1.f, bf16 != 0}, nullptr, &p)) return rc;
+  format_attn_mla(p, buf, buflen);
+  return LC_OK;
 }
 
 int lc_kv_append_paged_f16(const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len, int B, int Hkv,

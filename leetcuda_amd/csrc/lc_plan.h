@@ -261,6 +261,37 @@ struct MergePtrs {
 int check_attn_merge(const MergeCall& c, const MergePtrs& p);    // tu_plan.hip
 int launch_attn_merge(const MergeCall& c, const MergePtrs& p);   // tu_attn_merge.hip; checked arguments
 
+// What a caller of a multi-head latent attention entry states (lc_attn_mla_paged_f16 / _bf16 and their two query calls): a
+// ragged batch (cu_q, T, max_nq: the varlen entries' rules) of H query heads over ONE latent cache — pools [num_pages, page_size, Dc] and
+// [num_pages, page_size, Dr] behind a block table.  The plan: attn_mla_paged_kernel<BF16> on B x RB x S workgroups, RB = ceil(H max_nq / 64)
+// row blocks of 64 rows, S key ranges per row block, S > 1 followed by attn_mla_combine_kernel<BF16>.  S is the decode rule
+// (plan_attn_decode) of the varlen call with one K / V head: never from kv_len, forced by "attn_decode_split".
+struct MlaCall {
+  int B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, flags;   // (the query calls state num_pages = 1: it decides nothing)
+  float sm_scale;                        // the caller's softmax scale (the query calls: 1)
+  bool bf16;                             // Q, O and the pools are bfloat16: picks the kernels (and their names) and nothing else
+};
+struct MlaPtrs {
+  const half_t *Qc, *Qpe;                // [T,H,Dc], [T,H,Dr] (16-bit lanes: fp16 or, MlaCall::bf16, bfloat16)
+  const half_t *CKV, *KPE;               // the pools
+  half_t* O;                             // [T,H,Dc]
+  float* lse;                            // device float[T H] or nullptr = none
+  const int *cu_q, *block_table, *kv_len;
+  hipStream_t st;
+};
+struct MlaPlan {
+  MlaCall call;   // what was planned
+  int RB, S;
+};
+// The checks in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's pointers (nullptr: a query call)
+int check_attn_mla(const MlaCall& c, const MlaPtrs* a, MlaPlan* p);   // tu_plan.hip
+void format_attn_mla(const MlaPlan& p, char* buf, int buflen);         // "attn_mla_paged_kernel", "attn_mla_paged_bf16_kernel + attn_mla_combine_bf16_kernel x3"
+// bytes of fp32 partials a plan with S > 1 needs: S x T H x (Dc + 1) floats; 0 for S = 1
+inline size_t mla_workspace_bytes(const MlaPlan& p) {
+  return p.S > 1 ? (size_t)p.S * (size_t)p.call.T * p.call.H * (size_t)(p.call.Dc + 1) * sizeof(float) : 0;
+}
+int launch_attn_mla(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla.hip; checked arguments
+
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on
 // B x Hkv x ceil(Nq / (2048 / D)) workgroups, no workspace.

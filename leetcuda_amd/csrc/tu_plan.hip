@@ -797,6 +797,40 @@ int check_attn_merge(const MergeCall& c, const MergePtrs& p) {
   return LC_OK;
 }
 
+// Multi-head latent attention (lc_plan.h MlaCall).  The statuses in the varlen entries' order: flags, NULL pointers (lse may be
+// one) and the scale, the shape — dims, the 2 GiB span of one sequence's latent rows, the 32-bit row count, the grid —, alignment, the head dims.
+// The plan: RB row blocks of 64 of the H max_nq rows, and the decode rule's S for the varlen call of ONE K / V head on the same cache geometry.
+int check_attn_mla(const MlaCall& c, const MlaPtrs* a, MlaPlan* p) {
+  if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (a && (!a->Qc || !a->Qpe || !a->CKV || !a->KPE || !a->O || !a->cu_q || !a->block_table || !a->kv_len)) return LC_ERR_ARG;   // (lse: NULL = none)
+  // (decided on the bit pattern: this unit is compiled with -fno-honor-nans.)  Finite and > 0: exponent not all ones, sign clear, not zero
+  const uint32_t sb = __builtin_bit_cast(uint32_t, c.sm_scale);
+  if ((sb & 0x7f800000u) == 0x7f800000u || (sb >> 31) != 0 || sb == 0) return LC_ERR_ARG;
+  if (c.B <= 0 || c.H <= 0 || c.T <= 0 || c.max_nq <= 0 || c.num_pages <= 0 || c.max_pages <= 0 || c.Dc <= 0 || c.Dr <= 0) return LC_ERR_SHAPE;
+  if (c.max_nq > c.T) return LC_ERR_SHAPE;
+  if (c.page_size < 16 || (c.page_size & (c.page_size - 1)) != 0) return LC_ERR_SHAPE;   // a power of two >= 16: a 16-key block never straddles a page
+  const long ncap = (long)c.max_pages * c.page_size;
+  if (ncap > 0x7fffffffL || (size_t)ncap * 512 * 2 >= 0x80000000ull) return LC_ERR_SHAPE;   // one sequence's latent rows stay below 2 GiB
+  if ((long)c.T * c.H > 0x7fffffffL) return LC_ERR_SHAPE;                                    // rows are counted in 32 bits
+  const long R = (long)c.H * c.max_nq;
+  if ((size_t)c.B * (size_t)((R + 63) / 64) * 64 > 0x7fffffffull) return LC_ERR_SHAPE;       // 1-D grid of B x RB x S workgroups, S <= 64
+  if (a && (!aligned16(a->Qc) || !aligned16(a->Qpe) || !aligned16(a->CKV) || !aligned16(a->KPE) || !aligned16(a->O))) return LC_ERR_SHAPE;
+  if (c.Dc != 512 || c.Dr != 64) return LC_ERR_HEADDIM;
+  DecodeCall d{c.B, c.H, 1, c.max_nq, 128, c.flags, 2, true, 0, c.num_pages, c.page_size, c.max_pages, true};
+  d.varlen = true;
+  d.T = c.T;
+  d.max_nq = c.max_nq;
+  DecodePlan dp;
+  if (int rc = plan_attn_decode(read_knobs(), d, &dp)) return rc;
+  *p = MlaPlan{c, dp.RB, dp.S};
+  return LC_OK;
+}
+void format_attn_mla(const MlaPlan& p, char* buf, int buflen) {
+  const char* bf = p.call.bf16 ? "bf16_" : "";
+  if (p.S > 1) snprintf(buf, buflen, "attn_mla_paged_%skernel + attn_mla_combine_%skernel x%d", bf, bf, p.S);
+  else snprintf(buf, buflen, "attn_mla_paged_%skernel", bf);
+}
+
 // Append to the paged cache (lc_plan.h AppendCall).  The page geometry and the span bound are check_attn_decode's, so that every pool an append
 // accepts is one the decode call of the same step accepts; Nq is not bounded by the decode kernel's row tiles: a prefill writes whole prompts.
 int check_kv_append(const AppendCall& c, const AppendPtrs* a) {

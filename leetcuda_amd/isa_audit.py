@@ -73,6 +73,8 @@ OWNED_AGPRS = [
     # ... and the ragged-batch kernels with a look-back visibility mask (attn_varlen.hip), and per-token rotary positions (rope_append_varlen.hip)
     (re.compile(r"attn_varlen_(chunk_)?paged_(kv8_)?tree_(bf16_)?kernel"), []),
     (re.compile(r"rope_append_varlen_pos_(kv8_)?(bf16_)?kernel"), []),
+    # ... and the multi-head latent attention kernels (attn_mla.hip: builtins only; its one asm statement is empty)
+    (re.compile(r"attn_mla_paged_kernel|attn_mla_combine_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
 ]
 
