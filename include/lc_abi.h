@@ -800,8 +800,8 @@ int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob
  * captured stream or a failed lease runs S = 1 — and attn_mla_combine_kernel<BF16>.  lc_attn_mla_paged_workspace_bytes: those bytes (0: S = 1
  * or a refused shape); lc_attn_mla_paged_kernel_name: "attn_mla_paged_kernel" / "attn_mla_paged_bf16_kernel", S > 1:
  * "... + attn_mla_combine_kernel xS"; it returns the status the run call would give.
- * Not here: writing the latent cache, an fp8 latent cache, windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed
- * prefill form (plain attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512. */
+ * Not here: writing the latent cache, windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed prefill form (plain
+ * attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512.  (An fp8 latent cache: lc_attn_mla_paged_kv8 below.) */
 int lc_attn_mla_paged_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
                           const int* cu_q, const int* block_table, const int* kv_len,
                           int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
@@ -813,6 +813,33 @@ int lc_attn_mla_paged_bf16(const void* Qc, const void* Qpe, const void* CKVpool,
 size_t lc_attn_mla_paged_workspace_bytes(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr);
 int lc_attn_mla_paged_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16,
                                   char* buf, int buflen);
+
+/* EXTENSION: MLA decode over an fp8 (e4m3) paged LATENT cache (attn_mla_kv8.hip).  lc_attn_mla_paged_kv8 / _kv8_bf16 are
+ * lc_attn_mla_paged_f16 / _bf16, argument for argument and rule for rule (cu_q, T, max_nq, kv_len, block_table and every clamp, sm_scale,
+ * LC_ATTN_CAUSAL, the optional lse, Dc = 512 / Dr = 64 only, page_size a power of two >= 16, the workspace), with two differences:
+ *   CKVpool8    [num_pages, page_size, 512] OCP e4m3fn BYTES, 16-byte aligned: the value of an element is code x ckv_scale[0].  The rule that
+ *               wrote it is the fp8 K / V rows': code = e4m3fn(clamp(x / scale, +-448)), a true division (lc_kv_append_paged_kv8)
+ *   ckv_scale   DEVICE float[1], 4-byte aligned, or NULL = 1.0, right behind kv_len: the library's k_scale[Hkv] at Hkv = 1.  The kernel alone
+ *               reads it, so a replayed graph sees a new scale.  A scale that is NaN, zero or negative is the caller's business
+ *   KPEpool     stays 16-bit [num_pages, page_size, 64] in the element type of Q: the rope dims carry position and are 1/9 of the row (640
+ *               bytes a token instead of 576), and there is one scale and one conversion path
+ * Codes are converted to the element type exactly; the scale is applied in fp32 — to the latent part of a score in front of the rope part, to O
+ * (and the split-KV partials) behind the division by the softmax denominator — so that under a power-of-two scale O and lse equal, bit for
+ * bit, the 16-bit entry's on the dequantised pool (as long as code x scale is a normal number of the element type).  Codes 0x7f / 0xff are NaN.
+ * Status: the 16-bit entries' order, CKVpool8 checked where CKVpool is; a ckv_scale off 4 bytes: LC_ERR_ARG, with the NULL pointers in front of
+ * the shape.  lc_attn_mla_paged_workspace_bytes serves both element widths (the plan — RB, S, the grid — is the 16-bit call's).
+ * lc_attn_mla_paged_kv8_kernel_name: "attn_mla_paged_kv8_kernel" / "attn_mla_paged_kv8_bf16_kernel", S > 1: "... + attn_mla_combine_[bf16_]kernel xS".
+ * Not here: writing the latent cache, an fp8 rope pool (an all-fp8 row of 576 bytes), per-block scales, and what the 16-bit entry lacks. */
+int lc_attn_mla_paged_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
+                          const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale,
+                          int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                          int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_mla_paged_kv8_bf16(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
+                               const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale,
+                               int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                               int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16,
+                                      char* buf, int buflen);
 
 /* EXTENSION: tree-structured speculative decoding on the ragged entries — a look-back visibility mask per query token, and per-token rotary
  * positions (attn_varlen_tree.hip, rope_append_varlen_pos.hip).  The new tokens of a sequence are the nodes of a draft

@@ -143,6 +143,9 @@ SYMBOLS = {
     "lc_attn_mla_paged_bf16": (_i, [_vp] * 9 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_paged_workspace_bytes": (C.c_size_t, [_i] * 8),
     "lc_attn_mla_paged_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    "lc_attn_mla_paged_kv8": (_i, [_vp] * 10 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_paged_kv8_bf16": (_i, [_vp] * 10 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_paged_kv8_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -1554,6 +1557,51 @@ def attn_mla_paged_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc=512, Dr
     buf = C.create_string_buffer(128)
     check(load().lc_attn_mla_paged_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc, Dr, ATTN_CAUSAL if causal else 0, int(bf16), buf, 128),
           "lc_attn_mla_paged_kernel_name")
+    return buf.value.decode()
+
+
+# ... over an fp8 (e4m3) latent pool (lc_attn_mla_paged_kv8 / _kv8_bf16)
+
+def attn_mla_paged_kv8(q_c, q_pe, ckv_pool_u8, kpe_pool, o, cu_q, block_table, kv_len, max_nq, sm_scale, ckv_scale=None, lse=False, causal=False,
+                       workspace=None):
+    """attn_mla_paged over an fp8 latent pool (lc_attn_mla_paged_kv8 / _kv8_bf16, picked by q_c's dtype): ckv_pool_u8 [num_pages,page_size,512]
+    torch.uint8 holding e4m3fn codes, an element's value is code x ckv_scale[0]; ckv_scale a 1-element float32 DEVICE tensor (read by the kernel
+    only) or None = 1.0; kpe_pool stays [num_pages,page_size,64] in q_c's dtype.  Every other argument and the result: attn_mla_paged."""
+    import torch
+    if q_c.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q_c must be float16 or bfloat16, got {q_c.dtype}")
+    if any(t.dtype != q_c.dtype for t in (q_pe, kpe_pool, o)) or ckv_pool_u8.dtype != torch.uint8:
+        raise TypeError(f"q_c / q_pe / kpe_pool / o must share one 16-bit dtype and ckv_pool_u8 be uint8, got {q_c.dtype} / {q_pe.dtype} / "
+                        f"{kpe_pool.dtype} / {o.dtype} and {ckv_pool_u8.dtype}")
+    if ckv_scale is not None and (ckv_scale.dtype != torch.float32 or ckv_scale.numel() != 1):
+        raise TypeError("ckv_scale must be None or a 1-element float32 tensor")
+    if q_c.dim() != 3 or q_pe.dim() != 3 or ckv_pool_u8.dim() != 3 or kpe_pool.dim() != 3:
+        _shape_err("3-D [T,H,Dc] / [T,H,Dr] / [num_pages,page_size,Dc] / [num_pages,page_size,Dr] tensors expected")
+    T, H, Dc = q_c.shape
+    Dr = q_pe.shape[2]
+    num_pages, page_size = ckv_pool_u8.shape[:2]
+    if tuple(q_pe.shape) != (T, H, Dr) or tuple(o.shape) != (T, H, Dc) or ckv_pool_u8.shape[2] != Dc or tuple(kpe_pool.shape) != (num_pages, page_size, Dr):
+        _shape_err(f"q_c {tuple(q_c.shape)} q_pe {tuple(q_pe.shape)} ckv_pool_u8 {tuple(ckv_pool_u8.shape)} kpe_pool {tuple(kpe_pool.shape)} o {tuple(o.shape)}")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    plain = lse is False
+    outs = () if plain else (_lse_out(q_c, lse),)
+    scales = () if ckv_scale is None else (ckv_scale,)
+    _need_gpu(q_c, q_pe, ckv_pool_u8, kpe_pool, o, *outs, cu_q, block_table, kv_len, *scales)
+    symbol = "lc_attn_mla_paged_kv8_bf16" if q_c.dtype == torch.bfloat16 else "lc_attn_mla_paged_kv8"
+    check(getattr(load(), symbol)(_ptr(q_c), _ptr(q_pe), _ptr(ckv_pool_u8), _ptr(kpe_pool), _ptr(o), _ptr(outs[0]) if outs else None, _ptr(cu_q),
+                                  _ptr(block_table), _ptr(kv_len), _ptr(ckv_scale) if scales else None, B, H, T, max_nq, num_pages, page_size,
+                                  block_table.shape[1], Dc, Dr, float(sm_scale), ATTN_CAUSAL if causal else 0, *_workspace_args(workspace),
+                                  _stream()), symbol)
+    return o if plain else (o, outs[0])
+
+
+def attn_mla_paged_kv8_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc=512, Dr=64, causal=False, bf16=False) -> str:
+    """"attn_mla_paged_kv8_kernel" / "attn_mla_paged_kv8_bf16_kernel", + " + attn_mla_combine_[bf16_]kernel xS" with S > 1 KV ranges."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_mla_paged_kv8_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc, Dr, ATTN_CAUSAL if causal else 0, int(bf16), buf, 128),
+          "lc_attn_mla_paged_kv8_kernel_name")
     return buf.value.decode()
 
 

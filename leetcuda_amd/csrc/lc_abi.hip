@@ -155,6 +155,20 @@ int mla_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool, con
   return launch_attn_mla(p, a, workspace);
 }
 
+// ... and the two over an fp8 latent pool: the same MlaCall with kv8 = true and the scale pointer, launch_attn_mla_kv8
+int mla_kv8_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse, const int* cu_q,
+                const int* block_table, const int* kv_len, const float* ckv_scale, int B, int H, int T, int max_nq, int num_pages, int page_size,
+                int max_pages, int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  const MlaCall c{B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, flags, sm_scale, bf16, true};
+  const MlaPtrs a{static_cast<const half_t*>(Qc), static_cast<const half_t*>(Qpe), static_cast<const half_t*>(CKVpool8), static_cast<const half_t*>(KPEpool),
+                  static_cast<half_t*>(O), lse, cu_q, block_table, kv_len, static_cast<hipStream_t>(stream), ckv_scale};
+  MlaPlan p;
+  if (int rc = check_attn_mla(c, &a, &p)) return rc;
+  if (workspace && (workspace_bytes < mla_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_mla_kv8(p, a, workspace);
+}
+
 // The two append-to-cache entries (fp16 and fp8 pools) each state an AppendCall; check_kv_append (tu_plan.hip) checks it; append_run and append_name
 // run and name it.  (AppendCall: B, Hkv, Nq, D, flags, kv_bytes, num_pages, page_size, max_pages)
 int append_run(const AppendCall& c, const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len,
@@ -729,6 +743,32 @@ int lc_attn_mla_paged_kernel_name(int B, int H, int T, int max_nq, int page_size
   if (!buf || buflen < 8) return LC_ERR_ARG;
   MlaPlan p;
   if (int rc = check_attn_mla(MlaCall{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, flags, 1.f, bf16 != 0}, nullptr, &p)) return rc;
+  format_attn_mla(p, buf, buflen);
+  return LC_OK;
+}
+
+// ... over an fp8 (e4m3) latent pool (attn_mla_kv8.hip): mla_kv8_run above
+int lc_attn_mla_paged_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse, const int* cu_q,
+                          const int* block_table, const int* kv_len, const float* ckv_scale, int B, int H, int T, int max_nq, int num_pages,
+                          int page_size, int max_pages, int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  return mla_kv8_run(false, Qc, Qpe, CKVpool8, KPEpool, O, lse, cu_q, block_table, kv_len, ckv_scale, B, H, T, max_nq, num_pages, page_size, max_pages,
+                     Dc, Dr, sm_scale, flags, workspace, workspace_bytes, stream);
+}
+
+int lc_attn_mla_paged_kv8_bf16(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse, const int* cu_q,
+                               const int* block_table, const int* kv_len, const float* ckv_scale, int B, int H, int T, int max_nq, int num_pages,
+                               int page_size, int max_pages, int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  return mla_kv8_run(true, Qc, Qpe, CKVpool8, KPEpool, O, lse, cu_q, block_table, kv_len, ckv_scale, B, H, T, max_nq, num_pages, page_size, max_pages,
+                     Dc, Dr, sm_scale, flags, workspace, workspace_bytes, stream);
+}
+
+int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16, char* buf,
+                                      int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaPlan p;
+  if (int rc = check_attn_mla(MlaCall{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, flags, 1.f, bf16 != 0, true}, nullptr, &p)) return rc;
   format_attn_mla(p, buf, buflen);
   return LC_OK;
 }

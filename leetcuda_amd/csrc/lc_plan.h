@@ -270,6 +270,7 @@ struct MlaCall {
   int B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, flags;   // (the query calls state num_pages = 1: it decides nothing)
   float sm_scale;                        // the caller's softmax scale (the query calls: 1)
   bool bf16;                             // Q, O and the pools are bfloat16: picks the kernels (and their names) and nothing else
+  bool kv8 = false;                      // the latent pool is e4m3fn bytes (§4.3r): attn_mla_paged_kv8_kernel<BF16>; the plan is the 16-bit call's
 };
 struct MlaPtrs {
   const half_t *Qc, *Qpe;                // [T,H,Dc], [T,H,Dr] (16-bit lanes: fp16 or, MlaCall::bf16, bfloat16)
@@ -278,6 +279,7 @@ struct MlaPtrs {
   float* lse;                            // device float[T H] or nullptr = none
   const int *cu_q, *block_table, *kv_len;
   hipStream_t st;
+  const float* ckv_scale = nullptr;      // MlaCall::kv8: device float[1] read by the kernel only, or nullptr = 1.0
 };
 struct MlaPlan {
   MlaCall call;   // what was planned
@@ -285,12 +287,13 @@ struct MlaPlan {
 };
 // The checks in the order that decides which status a doubly-bad call gets, then the plan.  a: the run call's pointers (nullptr: a query call)
 int check_attn_mla(const MlaCall& c, const MlaPtrs* a, MlaPlan* p);   // tu_plan.hip
-void format_attn_mla(const MlaPlan& p, char* buf, int buflen);         // "attn_mla_paged_kernel", "attn_mla_paged_bf16_kernel + attn_mla_combine_bf16_kernel x3"
+void format_attn_mla(const MlaPlan& p, char* buf, int buflen);         // "attn_mla_paged_kernel", "attn_mla_paged_kv8_bf16_kernel + attn_mla_combine_bf16_kernel x3"
 // bytes of fp32 partials a plan with S > 1 needs: S x T H x (Dc + 1) floats; 0 for S = 1
 inline size_t mla_workspace_bytes(const MlaPlan& p) {
   return p.S > 1 ? (size_t)p.S * (size_t)p.call.T * p.call.H * (size_t)(p.call.Dc + 1) * sizeof(float) : 0;
 }
 int launch_attn_mla(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla.hip; checked arguments
+int launch_attn_mla_kv8(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla_kv8.hip; checked arguments, MlaCall::kv8
 
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on

@@ -803,6 +803,7 @@ int check_attn_merge(const MergeCall& c, const MergePtrs& p) {
 int check_attn_mla(const MlaCall& c, const MlaPtrs* a, MlaPlan* p) {
   if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
   if (a && (!a->Qc || !a->Qpe || !a->CKV || !a->KPE || !a->O || !a->cu_q || !a->block_table || !a->kv_len)) return LC_ERR_ARG;   // (lse: NULL = none)
+  if (a && ((uintptr_t)a->ckv_scale & 3) != 0) return LC_ERR_ARG;   // (kv8; NULL = 1.0)
   // (decided on the bit pattern: this unit is compiled with -fno-honor-nans.)  Finite and > 0: exponent not all ones, sign clear, not zero
   const uint32_t sb = __builtin_bit_cast(uint32_t, c.sm_scale);
   if ((sb & 0x7f800000u) == 0x7f800000u || (sb >> 31) != 0 || sb == 0) return LC_ERR_ARG;
@@ -826,9 +827,9 @@ int check_attn_mla(const MlaCall& c, const MlaPtrs* a, MlaPlan* p) {
   return LC_OK;
 }
 void format_attn_mla(const MlaPlan& p, char* buf, int buflen) {
-  const char* bf = p.call.bf16 ? "bf16_" : "";
-  if (p.S > 1) snprintf(buf, buflen, "attn_mla_paged_%skernel + attn_mla_combine_%skernel x%d", bf, bf, p.S);
-  else snprintf(buf, buflen, "attn_mla_paged_%skernel", bf);
+  const char *bf = p.call.bf16 ? "bf16_" : "", *k8 = p.call.kv8 ? "kv8_" : "";
+  if (p.S > 1) snprintf(buf, buflen, "attn_mla_paged_%s%skernel + attn_mla_combine_%skernel x%d", k8, bf, bf, p.S);
+  else snprintf(buf, buflen, "attn_mla_paged_%s%skernel", k8, bf);
 }
 
 // Append to the paged cache (lc_plan.h AppendCall).  The page geometry and the span bound are check_attn_decode's, so that every pool an append

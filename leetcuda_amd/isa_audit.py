@@ -75,6 +75,8 @@ OWNED_AGPRS = [
     (re.compile(r"rope_append_varlen_pos_(kv8_)?(bf16_)?kernel"), []),
     # ... and the multi-head latent attention kernels (attn_mla.hip: builtins only; its one asm statement is empty)
     (re.compile(r"attn_mla_paged_kernel|attn_mla_combine_kernel"), []),
+    # ... and the one over an fp8 latent pool (attn_mla_kv8.hip: the same)
+    (re.compile(r"attn_mla_paged_kv8_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
 ]
 
