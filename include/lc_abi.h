@@ -800,7 +800,7 @@ int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob
  * captured stream or a failed lease runs S = 1 — and attn_mla_combine_kernel<BF16>.  lc_attn_mla_paged_workspace_bytes: those bytes (0: S = 1
  * or a refused shape); lc_attn_mla_paged_kernel_name: "attn_mla_paged_kernel" / "attn_mla_paged_bf16_kernel", S > 1:
  * "... + attn_mla_combine_kernel xS"; it returns the status the run call would give.
- * Not here: writing the latent cache, windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed prefill form (plain
+ * Writing the latent cache: lc_mla_append_paged_* below.  Not here: windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed prefill form (plain
  * attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512.  (An fp8 latent cache: lc_attn_mla_paged_kv8 below.) */
 int lc_attn_mla_paged_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
                           const int* cu_q, const int* block_table, const int* kv_len,
@@ -829,7 +829,8 @@ int lc_attn_mla_paged_kernel_name(int B, int H, int T, int max_nq, int page_size
  * Status: the 16-bit entries' order, CKVpool8 checked where CKVpool is; a ckv_scale off 4 bytes: LC_ERR_ARG, with the NULL pointers in front of
  * the shape.  lc_attn_mla_paged_workspace_bytes serves both element widths (the plan — RB, S, the grid — is the 16-bit call's).
  * lc_attn_mla_paged_kv8_kernel_name: "attn_mla_paged_kv8_kernel" / "attn_mla_paged_kv8_bf16_kernel", S > 1: "... + attn_mla_combine_[bf16_]kernel xS".
- * Not here: writing the latent cache, an fp8 rope pool (an all-fp8 row of 576 bytes), per-block scales, and what the 16-bit entry lacks. */
+ * Writing the latent cache: lc_mla_append_paged_kv8 / _kv8_bf16 below.  Not here: an fp8 rope pool (an all-fp8 row of 576 bytes), per-block
+ * scales, and what the 16-bit entry lacks. */
 int lc_attn_mla_paged_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
                           const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale,
                           int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
@@ -840,6 +841,69 @@ int lc_attn_mla_paged_kv8_bf16(const void* Qc, const void* Qpe, const void* CKVp
                                int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
 int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16,
                                       char* buf, int buflen);
+
+/* EXTENSION: RMSNorm + rotary embedding + append for the paged LATENT cache (mla_append_paged.hip): the write side of
+ * lc_attn_mla_paged_*.  ONE launch takes a step's projection outputs as they sit in memory and leaves what the attention entries read: the
+ * latent row of every new token normalised (kv_a_layernorm) in CKVpool — lc_mla_append_paged_kv8 / _kv8_bf16: quantised to e4m3fn codes —, its
+ * k_pe row rotated in KPEpool, and the q_pe rows of all H heads rotated in Qpe_out.  A ragged batch; cu_q, T, max_nq, kv_len, block_table, the
+ * owner of a token, its position p = L_b - Nq_b + i and every clamp and drop rule are lc_rope_append_varlen_*'s: p < 0 gives a ZERO row in
+ * Qpe_out and no pool write, a page id outside [0, num_pages) drops the token's two pool rows and still writes Qpe_out, the cos_sin row read is
+ * clamp(p, 0, max_pos - 1), a token no sequence owns writes nothing.
+ *   CKVnew     [T,512] with row stride ckv_row_stride, KPEnew [T,64] with row stride kpe_row_stride (two pointers into one kv_a_proj_with_mqa
+ *              output [T,576], or into a wider fused projection); fp16, _bf16: bfloat16
+ *   Qpe        [T,H,64]: element (t, h, d) at Qpe[t q_row_stride + h q_head_stride + d] (a pointer into the q_b_proj output [T,H,192] at offset
+ *              128: q_head_stride = 192, q_row_stride = 192 H).  Qpe_out dense [T,H,64], what lc_attn_mla_paged_* reads; it may be Qpe itself
+ *              when Qpe is dense (q_head_stride = 64, q_row_stride = 64 H)
+ *   strides    in elements, multiples of 8, ckv_row_stride >= 512, kpe_row_stride >= 64, q_head_stride >= 64,
+ *              q_row_stride >= (H - 1) q_head_stride + 64
+ *   CKVpool    [num_pages, page_size, 512] 16-bit, or (_kv8) CKVpool8: e4m3fn bytes; KPEpool [num_pages, page_size, 64] 16-bit in both;
+ *              page_size a power of two >= 16: the pools lc_attn_mla_paged_* / _kv8 read
+ *   gamma      device float[512], the kv_a_layernorm weight: y = x rsqrt(mean(x^2) + eps) gamma in fp32 (the sum of squares, the reciprocal
+ *              root and both products), ONE rounding to the element type.  NULL: no normalisation — the 16-bit pool gets a bit copy of the
+ *              row, the fp8 pool the codes of the row itself.  eps is passed by value
+ *   cos_sin    device float[max_pos, 64] (rot_dim / 2 cosines, then sines; the rotary width is the whole 64); LC_ROPE_INTERLEAVED selects
+ *              GPT-J pairs (2j, 2j + 1) instead of NeoX pairs (j, j + 32).  The arithmetic and its one rounding: lc_rope_append_paged_*
+ *   ckv_scale  (_kv8) device float[1] or NULL = 1.0, right behind kv_len, read by the kernel only — exactly as lc_attn_mla_paged_kv8 reads it.
+ *              code = e4m3fn(clamp(y16 / scale, +-448)) with a true division, y16 the row ROUNDED to the element type: the fp8 pool holds
+ *              what the 16-bit pool quantised afterwards would (lc_kv_append_paged_kv8's rule, NaN and +-inf included)
+ * Status, in this order: a NULL pointer other than gamma and ckv_scale: LC_ERR_ARG; a source, Qpe_out or a pool off 16 bytes, gamma, cos_sin
+ * or ckv_scale off 4 bytes: LC_ERR_SHAPE; a non-positive dim, max_nq > T, a bad page_size, max_pages page_size 512 2 >= 2 GiB,
+ * T H > 2^31 - 1, the grid bound, a bad stride, Qpe_out == Qpe with strides that are not dense: LC_ERR_SHAPE; an unknown flag, eps negative
+ * or not finite: LC_ERR_ARG; (Dc, Dr) != (512, 64): LC_ERR_HEADDIM.  No workspace; every call can be captured into a graph.
+ * mla_append_paged_[kv8_][bf16_]kernel<INTERLEAVED> on ceil(T / (4 tpw)) + ceil(T H / 32) workgroups, tpw = 1 for T <= 2048 and 4 above.
+ * lc_mla_append_paged_kernel_name: that kernel's name for dense strides ("mla_append_paged_kv8_bf16_kernel<true>") and the status the run
+ * call would give.
+ * Not here: per-token position ids, an fp8 rope pool, per-block scales, q_a_layernorm, the W_UK absorption GEMM. */
+int lc_mla_append_paged_f16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out,
+                            void* CKVpool, void* KPEpool, const float* gamma, const float* cos_sin,
+                            const int* cu_q, const int* block_table, const int* kv_len,
+                            int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                            int Dc, int Dr, int max_pos, float eps,
+                            long long ckv_row_stride, long long kpe_row_stride,
+                            long long q_row_stride, long long q_head_stride, int flags, void* stream);
+int lc_mla_append_paged_bf16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out,
+                             void* CKVpool, void* KPEpool, const float* gamma, const float* cos_sin,
+                             const int* cu_q, const int* block_table, const int* kv_len,
+                             int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                             int Dc, int Dr, int max_pos, float eps,
+                             long long ckv_row_stride, long long kpe_row_stride,
+                             long long q_row_stride, long long q_head_stride, int flags, void* stream);
+int lc_mla_append_paged_kv8(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out,
+                            void* CKVpool8, void* KPEpool, const float* gamma, const float* cos_sin,
+                            const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale,
+                            int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                            int Dc, int Dr, int max_pos, float eps,
+                            long long ckv_row_stride, long long kpe_row_stride,
+                            long long q_row_stride, long long q_head_stride, int flags, void* stream);
+int lc_mla_append_paged_kv8_bf16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out,
+                                 void* CKVpool8, void* KPEpool, const float* gamma, const float* cos_sin,
+                                 const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale,
+                                 int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                                 int Dc, int Dr, int max_pos, float eps,
+                                 long long ckv_row_stride, long long kpe_row_stride,
+                                 long long q_row_stride, long long q_head_stride, int flags, void* stream);
+int lc_mla_append_paged_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int max_pos,
+                                    int flags, int kv8, int bf16, char* buf, int buflen);
 
 /* EXTENSION: tree-structured speculative decoding on the ragged entries — a look-back visibility mask per query token, and per-token rotary
  * positions (attn_varlen_tree.hip, rope_append_varlen_pos.hip).  The new tokens of a sequence are the nodes of a draft

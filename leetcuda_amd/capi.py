@@ -146,6 +146,13 @@ SYMBOLS = {
     "lc_attn_mla_paged_kv8": (_i, [_vp] * 10 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_paged_kv8_bf16": (_i, [_vp] * 10 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_paged_kv8_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    # RMSNorm + rope + append to the latent cache: CKVnew, KPEnew, Qpe, Qpe_out, CKVpool, KPEpool, gamma (or NULL), cos_sin, cu_q, block_table,
+    # kv_len, [ckv_scale (or NULL),] B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, the four strides, flags, stream
+    "lc_mla_append_paged_f16": (_i, [_vp] * 11 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
+    "lc_mla_append_paged_bf16": (_i, [_vp] * 11 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
+    "lc_mla_append_paged_kv8": (_i, [_vp] * 12 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
+    "lc_mla_append_paged_kv8_bf16": (_i, [_vp] * 12 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
+    "lc_mla_append_paged_kernel_name": (_i, [_i] * 12 + [_cp, _i]),
     "lc_attn_call": (_i, [_cp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lc_attn_entry_count": (_i, []),
     "lc_attn_entry_name": (_cp, [_i]),
@@ -1602,6 +1609,89 @@ def attn_mla_paged_kv8_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc=512
     buf = C.create_string_buffer(128)
     check(load().lc_attn_mla_paged_kv8_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc, Dr, ATTN_CAUSAL if causal else 0, int(bf16), buf, 128),
           "lc_attn_mla_paged_kv8_kernel_name")
+    return buf.value.decode()
+
+
+# The write side of the latent cache (lc_mla_append_paged_f16 / _bf16 / _kv8 / _kv8_bf16): RMSNorm of the latent row,
+# rotation of k_pe and of the H q_pe rows, and the append through the block table, in one launch.
+
+def _mla_append(ckv_new, kpe_new, q_pe, ckv_pool, kpe_pool, cos_sin, cu_q, block_table, kv_len, max_nq, gamma, eps, q_pe_out, interleaved, kv8,
+                ckv_scale=None):
+    import torch
+    el = q_pe.dtype
+    if el not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q_pe must be float16 or bfloat16, got {el}")
+    pool_type = torch.uint8 if kv8 else el
+    if any(t.dtype != el for t in (ckv_new, kpe_new, kpe_pool)) or ckv_pool.dtype != pool_type or (q_pe_out is not None and q_pe_out.dtype != el):
+        raise TypeError(f"ckv_new / kpe_new / q_pe / kpe_pool / q_pe_out must share one 16-bit dtype and ckv_pool be {pool_type}, got {ckv_new.dtype} / "
+                        f"{kpe_new.dtype} / {el} / {kpe_pool.dtype} / {None if q_pe_out is None else q_pe_out.dtype} and {ckv_pool.dtype}")
+    for name, t, n in (("gamma", gamma, None), ("cos_sin", cos_sin, None), ("ckv_scale", ckv_scale, 1)):
+        if t is not None and (t.dtype != torch.float32 or (n is not None and t.numel() != n)):
+            raise TypeError(f"{name} must be float32{'' if n is None else f' with {n} element'}, got {t.dtype} {tuple(t.shape)}")
+    if ckv_new.dim() != 2 or kpe_new.dim() != 2 or q_pe.dim() != 3 or ckv_pool.dim() != 3 or kpe_pool.dim() != 3 or cos_sin.dim() != 2:
+        _shape_err("[T,Dc] / [T,Dr] / [T,H,Dr] sources, [num_pages,page_size,Dc] / [num_pages,page_size,Dr] pools and cos_sin [max_pos,Dr] expected")
+    T, H, Dr = q_pe.shape
+    Dc = ckv_new.shape[1]
+    num_pages, page_size = ckv_pool.shape[:2]
+    if (ckv_new.shape[0] != T or tuple(kpe_new.shape) != (T, Dr) or ckv_pool.shape[2] != Dc or tuple(kpe_pool.shape) != (num_pages, page_size, Dr)
+            or cos_sin.shape[1] != Dr or cos_sin.shape[0] < 1 or (gamma is not None and tuple(gamma.shape) != (Dc,))
+            or (q_pe_out is not None and tuple(q_pe_out.shape) != (T, H, Dr))):
+        _shape_err(f"ckv_new {tuple(ckv_new.shape)} kpe_new {tuple(kpe_new.shape)} q_pe {tuple(q_pe.shape)} ckv_pool {tuple(ckv_pool.shape)} kpe_pool "
+                   f"{tuple(kpe_pool.shape)} cos_sin {tuple(cos_sin.shape)} gamma {None if gamma is None else tuple(gamma.shape)}")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    # the four strides, in elements: rows of dense elements, views into wider projection outputs accepted (as _row_stride)
+    cs, ks = _row_stride(ckv_new.unsqueeze(1), "ckv_new"), _row_stride(kpe_new.unsqueeze(1), "kpe_new")
+    if q_pe.stride(2) != 1:
+        _shape_err(f"q_pe strides {tuple(q_pe.stride())}: head rows of dense elements are expected")
+    qh = q_pe.stride(1) if H > 1 else Dr
+    qs = q_pe.stride(0) if T > 1 else (H - 1) * qh + Dr
+    if qh < Dr or qh % 8 != 0 or qs < (H - 1) * qh + Dr or qs % 8 != 0:
+        _shape_err(f"q_pe strides {tuple(q_pe.stride())}: a head stride >= {Dr} and a row stride >= (H - 1) head stride + {Dr}, multiples of 8, are expected")
+    if q_pe_out is q_pe and (qh != Dr or qs != H * Dr):
+        _shape_err("in place (q_pe_out is q_pe) needs a dense q_pe")
+    for t in (ckv_new, kpe_new, q_pe):      # (views into a projection output are not contiguous: the kernel strides)
+        if not t.is_cuda:
+            raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    if q_pe_out is None:
+        q_pe_out = torch.empty((T, H, Dr), dtype=el, device=q_pe.device)
+    _need_gpu(q_pe_out, ckv_pool, kpe_pool, cos_sin, cu_q, block_table, kv_len, *(t for t in (gamma, ckv_scale) if t is not None))
+    symbol = "lc_mla_append_paged_" + (("kv8_bf16" if kv8 else "bf16") if el == torch.bfloat16 else ("kv8" if kv8 else "f16"))
+    scale = [None if ckv_scale is None else _ptr(ckv_scale)] if kv8 else []
+    check(getattr(load(), symbol)(_ptr(ckv_new), _ptr(kpe_new), _ptr(q_pe), _ptr(q_pe_out), _ptr(ckv_pool), _ptr(kpe_pool),
+                                  None if gamma is None else _ptr(gamma), _ptr(cos_sin), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), *scale, B, H, T,
+                                  max_nq, num_pages, page_size, block_table.shape[1], Dc, Dr, cos_sin.shape[0], float(eps), cs, ks, qs, qh,
+                                  ROPE_INTERLEAVED if interleaved else 0, _stream()), symbol)
+    return q_pe_out
+
+
+def mla_append_paged(ckv_new, kpe_new, q_pe, ckv_pool, kpe_pool, cos_sin, cu_q, block_table, kv_len, max_nq, gamma=None, eps=1e-6, q_pe_out=None,
+                     interleaved=False):
+    """The write side of attn_mla_paged for a ragged batch, ONE launch (lc_mla_append_paged_f16 / _bf16, picked by q_pe's dtype): ckv_new
+    [T,512] and kpe_new [T,64] — dense, or views into the kv_a_proj_with_mqa output, e.g. kv[:, :512] and kv[:, 512:] —, q_pe [T,H,64] — dense,
+    or a view such as q.view(T, H, 192)[:, :, 128:].  Token t of the sequence b with cu_q[b] <= t < cu_q[b + 1] sits at position
+    kv_len[b] - Nq_b + (t - cu_q[b]): its latent row, normalised by gamma (float32 [512], kv_a_layernorm; None: copied) with eps, goes to
+    ckv_pool [num_pages,page_size,512], its k_pe row rotated by row p of cos_sin (float32 [max_pos,64], rope_table(max_pos, 64)) to kpe_pool
+    [num_pages,page_size,64].  Returns q_pe_out [T,H,64] dense, the rotated q_pe rows (None: allocated; `q_pe_out is q_pe`: in place, dense
+    q_pe only).  cu_q, max_nq, the clamps and the drop rules are rope_append_varlen's."""
+    return _mla_append(ckv_new, kpe_new, q_pe, ckv_pool, kpe_pool, cos_sin, cu_q, block_table, kv_len, max_nq, gamma, eps, q_pe_out, interleaved, False)
+
+
+def mla_append_paged_kv8(ckv_new, kpe_new, q_pe, ckv_pool_u8, kpe_pool, cos_sin, cu_q, block_table, kv_len, max_nq, gamma=None, eps=1e-6,
+                         q_pe_out=None, interleaved=False, ckv_scale=None):
+    """mla_append_paged into an fp8 latent pool (lc_mla_append_paged_kv8 / _kv8_bf16): ckv_pool_u8 [num_pages,page_size,512] torch.uint8 gets
+    the e4m3fn codes of the normalised row rounded to q_pe's dtype, under ckv_scale (a 1-element float32 DEVICE tensor read by the kernel
+    only, or None = 1.0) — what attn_mla_paged_kv8 reads.  kpe_pool stays 16-bit."""
+    return _mla_append(ckv_new, kpe_new, q_pe, ckv_pool_u8, kpe_pool, cos_sin, cu_q, block_table, kv_len, max_nq, gamma, eps, q_pe_out, interleaved, True,
+                       ckv_scale)
+
+
+def mla_append_paged_kernel_name(B, H, T, max_nq, page_size, max_pages, max_pos, Dc=512, Dr=64, interleaved=False, kv8=False, bf16=False) -> str:
+    """"mla_append_paged_kernel<INTERLEAVED>" / "_bf16_kernel" / "_kv8_kernel" / "_kv8_bf16_kernel"."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_mla_append_paged_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc, Dr, max_pos, ROPE_INTERLEAVED if interleaved else 0, int(kv8),
+                                                 int(bf16), buf, 128), "lc_mla_append_paged_kernel_name")
     return buf.value.decode()
 
 

@@ -169,6 +169,22 @@ int mla_kv8_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool8
   return launch_attn_mla_kv8(p, a, workspace);
 }
 
+// The four latent-cache append entries state an MlaAppendCall; check_mla_append (tu_plan.hip) checks it, launch_mla_append
+// (tu_mla_append.hip) runs it
+int mla_append_run(bool kv8, bool bf16, const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool,
+                   const float* gamma, const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale, int B,
+                   int H, int T, int max_nq, int num_pages, int page_size, int max_pages, int Dc, int Dr, int max_pos, float eps,
+                   long long ckv_row_stride, long long kpe_row_stride, long long q_row_stride, long long q_head_stride, int flags, void* stream) {
+  const MlaAppendCall c{B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, ckv_row_stride, kpe_row_stride, q_row_stride,
+                        q_head_stride, flags, kv8, bf16};
+  const MlaAppendPtrs a{static_cast<const half_t*>(CKVnew), static_cast<const half_t*>(KPEnew), static_cast<const half_t*>(Qpe),
+                        static_cast<half_t*>(Qpe_out), CKVpool, static_cast<half_t*>(KPEpool), gamma, cos_sin, cu_q, block_table, kv_len, ckv_scale,
+                        static_cast<hipStream_t>(stream)};
+  if (int rc = check_mla_append(c, &a)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_mla_append(c, a);
+}
+
 // The two append-to-cache entries (fp16 and fp8 pools) each state an AppendCall; check_kv_append (tu_plan.hip) checks it; append_run and append_name
 // run and name it.  (AppendCall: B, Hkv, Nq, D, flags, kv_bytes, num_pages, page_size, max_pages)
 int append_run(const AppendCall& c, const void* Knew, const void* Vnew, void* Kpool, void* Vpool, const int* block_table, const int* kv_len,
@@ -770,6 +786,53 @@ int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_
   MlaPlan p;
   if (int rc = check_attn_mla(MlaCall{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, flags, 1.f, bf16 != 0, true}, nullptr, &p)) return rc;
   format_attn_mla(p, buf, buflen);
+  return LC_OK;
+}
+
+// RMSNorm + rotary embedding + append to the paged latent cache (mla_append_paged.hip): mla_append_run above
+int lc_mla_append_paged_f16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool, const float* gamma,
+                            const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int T, int max_nq,
+                            int num_pages, int page_size, int max_pages, int Dc, int Dr, int max_pos, float eps, long long ckv_row_stride,
+                            long long kpe_row_stride, long long q_row_stride, long long q_head_stride, int flags, void* stream) {
+  return mla_append_run(false, false, CKVnew, KPEnew, Qpe, Qpe_out, CKVpool, KPEpool, gamma, cos_sin, cu_q, block_table, kv_len, nullptr, B, H, T, max_nq,
+                        num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, ckv_row_stride, kpe_row_stride, q_row_stride, q_head_stride, flags, stream);
+}
+
+int lc_mla_append_paged_bf16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool, const float* gamma,
+                             const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int T, int max_nq,
+                             int num_pages, int page_size, int max_pages, int Dc, int Dr, int max_pos, float eps, long long ckv_row_stride,
+                             long long kpe_row_stride, long long q_row_stride, long long q_head_stride, int flags, void* stream) {
+  return mla_append_run(false, true, CKVnew, KPEnew, Qpe, Qpe_out, CKVpool, KPEpool, gamma, cos_sin, cu_q, block_table, kv_len, nullptr, B, H, T, max_nq,
+                        num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, ckv_row_stride, kpe_row_stride, q_row_stride, q_head_stride, flags, stream);
+}
+
+int lc_mla_append_paged_kv8(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool8, void* KPEpool, const float* gamma,
+                            const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale, int B, int H,
+                            int T, int max_nq, int num_pages, int page_size, int max_pages, int Dc, int Dr, int max_pos, float eps,
+                            long long ckv_row_stride, long long kpe_row_stride, long long q_row_stride, long long q_head_stride, int flags,
+                            void* stream) {
+  return mla_append_run(true, false, CKVnew, KPEnew, Qpe, Qpe_out, CKVpool8, KPEpool, gamma, cos_sin, cu_q, block_table, kv_len, ckv_scale, B, H, T,
+                        max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, ckv_row_stride, kpe_row_stride, q_row_stride, q_head_stride, flags,
+                        stream);
+}
+
+int lc_mla_append_paged_kv8_bf16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool8, void* KPEpool,
+                                 const float* gamma, const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len,
+                                 const float* ckv_scale, int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages, int Dc, int Dr,
+                                 int max_pos, float eps, long long ckv_row_stride, long long kpe_row_stride, long long q_row_stride,
+                                 long long q_head_stride, int flags, void* stream) {
+  return mla_append_run(true, true, CKVnew, KPEnew, Qpe, Qpe_out, CKVpool8, KPEpool, gamma, cos_sin, cu_q, block_table, kv_len, ckv_scale, B, H, T,
+                        max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, ckv_row_stride, kpe_row_stride, q_row_stride, q_head_stride, flags,
+                        stream);
+}
+
+// (the name call takes no num_pages, eps or strides: dense rows, and none of them decides the kernel)
+int lc_mla_append_paged_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int max_pos, int flags, int kv8,
+                                    int bf16, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  const MlaAppendCall c{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, max_pos, 0.f, Dc, Dr, (long long)H * Dr, Dr, flags, kv8 != 0, bf16 != 0};
+  if (int rc = check_mla_append(c, nullptr)) return rc;
+  format_mla_append(c, buf, buflen);
   return LC_OK;
 }
 

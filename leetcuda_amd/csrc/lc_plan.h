@@ -295,6 +295,36 @@ inline size_t mla_workspace_bytes(const MlaPlan& p) {
 int launch_attn_mla(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla.hip; checked arguments
 int launch_attn_mla_kv8(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla_kv8.hip; checked arguments, MlaCall::kv8
 
+// What a caller of a latent-cache append entry states (lc_mla_append_paged_f16 / _bf16 / _kv8 / _kv8_bf16 and their name call):
+// the write side of the cache MlaCall reads — RMSNorm of the latent row, rotation of k_pe and of the H q_pe rows, the append through the block
+// table, on a ragged batch.  Nothing to plan: one kernel, mla_append_paged_[kv8_][bf16_]kernel<INTERLEAVED>, on
+// ceil(T / (4 tpw)) + ceil(T H / 32) workgroups, no workspace.
+struct MlaAppendCall {
+  int B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos;   // (the name call states num_pages = 1: it decides nothing)
+  float eps;
+  long long ckv_row_stride, kpe_row_stride, q_row_stride, q_head_stride;   // elements
+  int flags;                             // LC_ROPE_INTERLEAVED
+  bool kv8, bf16;                        // the latent pool is e4m3fn bytes; sources, Qpe_out and 16-bit pools are bfloat16
+};
+struct MlaAppendPtrs {
+  const half_t *CKVnew, *KPEnew, *Qpe;   // (16-bit lanes: fp16 or, MlaAppendCall::bf16, bfloat16)
+  half_t* Qpe_out;                       // dense [T,H,Dr]; may be Qpe itself for a dense Qpe
+  void* CKVpool;                         // [num_pages, page_size, Dc] of 2 bytes or (kv8) 1 byte an element
+  half_t* KPEpool;                       // [num_pages, page_size, Dr]
+  const float *gamma, *cos_sin;          // device float[Dc] or nullptr = no normalisation; device float[max_pos, Dr]
+  const int *cu_q, *block_table, *kv_len;
+  const float* ckv_scale;                // kv8: device float[1] read by the kernel only, or nullptr = 1.0; else nullptr
+  hipStream_t st;
+};
+// tokens a latent wave walks: 1 while every token can have a wave of its own in one round of the device (a decode step, a short prefill),
+// 4 for long prefills (gamma is loaded once per wave).  From T alone: never from device data
+inline int mla_append_tokens_per_wave(int T) { return T <= 2048 ? 1 : 4; }
+// The checks in the order that decides which status a doubly-bad call gets: NULL pointers (ARG), alignment, shape and strides (SHAPE), flags
+// and eps (ARG), the two widths (HEADDIM).  a: the run call's pointers (nullptr: the name call)
+int check_mla_append(const MlaAppendCall& c, const MlaAppendPtrs* a);   // tu_plan.hip
+void format_mla_append(const MlaAppendCall& c, char* buf, int buflen);   // "mla_append_paged_kernel<false>", "mla_append_paged_kv8_bf16_kernel<true>"
+int launch_mla_append(const MlaAppendCall& c, const MlaAppendPtrs& a);   // tu_mla_append.hip; checked arguments
+
 // What a caller of an append-to-cache entry states (lc_kv_append_paged_f16 / _kv8 and their name calls): the write side of the paged cache that
 // DecodeCall with paged = true reads.  There is nothing to plan: one kernel, kv_append_paged_kernel<D> or kv_append_paged_kv8_kernel<D>, on
 // B x Hkv x ceil(Nq / (2048 / D)) workgroups, no workspace.

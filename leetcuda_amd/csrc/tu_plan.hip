@@ -832,6 +832,38 @@ void format_attn_mla(const MlaPlan& p, char* buf, int buflen) {
   else snprintf(buf, buflen, "attn_mla_paged_%s%skernel", k8, bf);
 }
 
+// RMSNorm + rotary embedding + append to the latent cache (lc_plan.h MlaAppendCall).  The pool geometry — page size, the 2 GiB
+// span of one sequence's latent rows, T H rows in 32 bits — is check_attn_mla's, so that a cache this call accepts is one the attention call of
+// the same step accepts.  Strides are in elements, multiples of 8 (16-byte chunks), at least the width of what they step over.
+int check_mla_append(const MlaAppendCall& c, const MlaAppendPtrs* a) {
+  if (a && (!a->CKVnew || !a->KPEnew || !a->Qpe || !a->Qpe_out || !a->CKVpool || !a->KPEpool || !a->cos_sin || !a->cu_q || !a->block_table || !a->kv_len))
+    return LC_ERR_ARG;                                          // (gamma: NULL = no normalisation; ckv_scale: NULL = 1.0)
+  if (a && (!aligned16(a->CKVnew) || !aligned16(a->KPEnew) || !aligned16(a->Qpe) || !aligned16(a->Qpe_out) || !aligned16(a->CKVpool) || !aligned16(a->KPEpool)))
+    return LC_ERR_SHAPE;
+  if (a && ((((uintptr_t)a->gamma | (uintptr_t)a->cos_sin | (uintptr_t)a->ckv_scale) & 3) != 0)) return LC_ERR_SHAPE;
+  if (c.B <= 0 || c.H <= 0 || c.T <= 0 || c.max_nq <= 0 || c.num_pages <= 0 || c.max_pages <= 0 || c.Dc <= 0 || c.Dr <= 0 || c.max_pos <= 0) return LC_ERR_SHAPE;
+  if (c.max_nq > c.T) return LC_ERR_SHAPE;
+  if (c.page_size < 16 || (c.page_size & (c.page_size - 1)) != 0) return LC_ERR_SHAPE;
+  const long ncap = (long)c.max_pages * c.page_size;
+  if (ncap > 0x7fffffffL || (size_t)ncap * 512 * 2 >= 0x80000000ull) return LC_ERR_SHAPE;
+  if ((long)c.T * c.H > 0x7fffffffL) return LC_ERR_SHAPE;
+  // 1-D grid of ceil(T / (4 tpw)) + ceil(T H / 32) workgroups; a latent wave counts its tokens in 32 bits up to T + 4 tpw
+  if ((size_t)c.T / 4 + (size_t)c.T * c.H / 32 + 2 > 0x7fffffffull || c.T > 0x7fffffff - 64) return LC_ERR_SHAPE;
+  if (c.ckv_row_stride % 8 != 0 || c.ckv_row_stride < c.Dc || c.kpe_row_stride % 8 != 0 || c.kpe_row_stride < c.Dr) return LC_ERR_SHAPE;
+  if (c.q_head_stride % 8 != 0 || c.q_head_stride < c.Dr || c.q_row_stride % 8 != 0) return LC_ERR_SHAPE;
+  if (c.q_row_stride < (long long)(c.H - 1) * c.q_head_stride + c.Dr) return LC_ERR_SHAPE;
+  if (a && a->Qpe == a->Qpe_out && (c.q_head_stride != c.Dr || c.q_row_stride != (long long)c.H * c.Dr)) return LC_ERR_SHAPE;   // in place: the dense layout only
+  if (c.flags & ~LC_ROPE_INTERLEAVED) return LC_ERR_ARG;
+  // (decided on the bit pattern: this unit is compiled with -fno-honor-nans.)  eps finite and >= 0: exponent not all ones, sign clear unless -0
+  const uint32_t eb = __builtin_bit_cast(uint32_t, c.eps);
+  if ((eb & 0x7f800000u) == 0x7f800000u || ((eb >> 31) != 0 && (eb << 1) != 0)) return LC_ERR_ARG;
+  if (c.Dc != 512 || c.Dr != 64) return LC_ERR_HEADDIM;
+  return LC_OK;
+}
+void format_mla_append(const MlaAppendCall& c, char* buf, int buflen) {
+  snprintf(buf, buflen, "mla_append_paged_%s%skernel<%s>", c.kv8 ? "kv8_" : "", c.bf16 ? "bf16_" : "", c.flags & LC_ROPE_INTERLEAVED ? "true" : "false");
+}
+
 // Append to the paged cache (lc_plan.h AppendCall).  The page geometry and the span bound are check_attn_decode's, so that every pool an append
 // accepts is one the decode call of the same step accepts; Nq is not bounded by the decode kernel's row tiles: a prefill writes whole prompts.
 int check_kv_append(const AppendCall& c, const AppendPtrs* a) {
