@@ -801,7 +801,8 @@ int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob
  * or a refused shape); lc_attn_mla_paged_kernel_name: "attn_mla_paged_kernel" / "attn_mla_paged_bf16_kernel", S > 1:
  * "... + attn_mla_combine_kernel xS"; it returns the status the run call would give.
  * Writing the latent cache: lc_mla_append_paged_* below.  Not here: windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed prefill form (plain
- * attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512.  (An fp8 latent cache: lc_attn_mla_paged_kv8 below.) */
+ * attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512.  (An fp8 latent cache: lc_attn_mla_paged_kv8 below; per-token
+ * selected cache entries — DeepSeek-V3.2's sparse attention — : lc_attn_mla_sparse_* below.) */
 int lc_attn_mla_paged_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
                           const int* cu_q, const int* block_table, const int* kv_len,
                           int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
@@ -841,6 +842,39 @@ int lc_attn_mla_paged_kv8_bf16(const void* Qc, const void* Qpe, const void* CKVp
                                int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
 int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_size, int max_pages, int Dc, int Dr, int flags, int bf16,
                                       char* buf, int buflen);
+
+/* EXTENSION: SPARSE multi-head latent attention over per-token selected cache slots (attn_mla_sparse.hip): the attention
+ * of DeepSeek-V3.2 ("DSA"; FlashMLA's `indices`), where an indexer picks for every query token its own topk cache entries and the absorbed
+ * MQA-form attention of lc_attn_mla_paged_* runs over those entries only.
+ *   Qc, Qpe, O, lse   exactly as in lc_attn_mla_paged_*: [T,H,512], [T,H,64], [T,H,512] 16-bit (fp16, _bf16: bfloat16), 16-byte aligned; lse
+ *                device float32 [T H] or NULL
+ *   CKVpool, KPEpool   [num_slots, 512] and [num_slots, 64] in Q's element type: the paged pools of the dense entries viewed flat,
+ *                num_slots = num_pages x page_size.  The page size plays no part: any page size works
+ *   slots        device int32 [T, topk], dense rows, 4-byte aligned: slots[t, j] is the pool slot of the j-th key of query token t,
+ *                page x page_size + offset (FlashMLA's convention).  An entry outside [0, num_slots), -1 included, is not a key; a slot listed
+ *                twice is two keys.  Slot offsets into the pools are 64-bit
+ * Every head h of token t attends to exactly the valid entries of row t, in the dense entry's arithmetic: fp32 products and softmax state,
+ * sm_scale log2 e applied to the fp32 scores, P rounded to the element type for the value product while the row sum keeps the unrounded value,
+ * O rounded once, lse in natural units.  An invalid entry contributes exactly nothing whatever the pools hold (pool data of an invalid entry
+ * never reaches a product).  A token with no valid entry gets O = 0 and lse = -inf; all T tokens are written.  There is no causal flag — the
+ * indexer selected visible keys — and no flag at all: flags != 0 is LC_ERR_ARG.
+ * Status, in this order: an unknown flag, a NULL pointer other than lse, sm_scale not finite or <= 0: LC_ERR_ARG; non-positive T, H, topk or
+ * num_slots, T H > 2^31 - 1, the grid bound (T ceil(H / 64) 64 > 2^31 - 1), a 16-bit pointer off 16 bytes or slots off 4 bytes: LC_ERR_SHAPE;
+ * (Dc, Dr) != (512, 64): LC_ERR_HEADDIM; a non-NULL workspace that is too small or off 16 bytes: LC_ERR_ARG.
+ * attn_mla_sparse_kernel<BF16> on T x ceil(H / 64) x S workgroups; S > 1 ranges of the ceil(topk / 64) tiles (from T, H, topk and the CU count
+ * only; "attn_decode_split" forces it): S x T H x 513 floats of workspace — the caller's, which makes S > 1 legal under graph capture, else the
+ * stream's cached one; a captured stream or a failed lease runs S = 1 — and attn_mla_sparse_combine_kernel<BF16>.
+ * lc_attn_mla_sparse_workspace_bytes: those bytes (0: S = 1 or a refused shape); lc_attn_mla_sparse_kernel_name never launches:
+ * "attn_mla_sparse_kernel" / "attn_mla_sparse_bf16_kernel", S > 1: "... + attn_mla_sparse_combine_[bf16_]kernel xS", and the run call's status.
+ * Not here: an fp8 latent pool, per-token topk lengths (pad a shorter row with -1), the indexer itself, other (Dc, Dr). */
+int lc_attn_mla_sparse_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
+                           const int* slots, int T, int H, int topk, int num_slots, int Dc, int Dr,
+                           float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_mla_sparse_bf16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
+                            const int* slots, int T, int H, int topk, int num_slots, int Dc, int Dr,
+                            float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+size_t lc_attn_mla_sparse_workspace_bytes(int T, int H, int topk, int Dc, int Dr);
+int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen);
 
 /* EXTENSION: RMSNorm + rotary embedding + append for the paged LATENT cache (mla_append_paged.hip): the write side of
  * lc_attn_mla_paged_*.  ONE launch takes a step's projection outputs as they sit in memory and leaves what the attention entries read: the

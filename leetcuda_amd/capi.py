@@ -146,6 +146,12 @@ SYMBOLS = {
     "lc_attn_mla_paged_kv8": (_i, [_vp] * 10 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_paged_kv8_bf16": (_i, [_vp] * 10 + [_i] * 9 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_paged_kv8_kernel_name": (_i, [_i] * 10 + [_cp, _i]),
+    # sparse latent attention: Qc, Qpe, CKVpool, KPEpool, O, lse (or NULL), slots, T, H, topk, num_slots, Dc, Dr, sm_scale, flags, workspace,
+    # workspace_bytes, stream
+    "lc_attn_mla_sparse_f16": (_i, [_vp] * 7 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_sparse_bf16": (_i, [_vp] * 7 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_sparse_workspace_bytes": (C.c_size_t, [_i] * 5),
+    "lc_attn_mla_sparse_kernel_name": (_i, [_i] * 7 + [_cp, _i]),
     # RMSNorm + rope + append to the latent cache: CKVnew, KPEnew, Qpe, Qpe_out, CKVpool, KPEpool, gamma (or NULL), cos_sin, cu_q, block_table,
     # kv_len, [ckv_scale (or NULL),] B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, the four strides, flags, stream
     "lc_mla_append_paged_f16": (_i, [_vp] * 11 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
@@ -1609,6 +1615,51 @@ def attn_mla_paged_kv8_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc=512
     buf = C.create_string_buffer(128)
     check(load().lc_attn_mla_paged_kv8_kernel_name(B, H, T, max_nq, page_size, max_pages, Dc, Dr, ATTN_CAUSAL if causal else 0, int(bf16), buf, 128),
           "lc_attn_mla_paged_kv8_kernel_name")
+    return buf.value.decode()
+
+
+# ... over per-token selected pool slots (lc_attn_mla_sparse_f16 / _bf16)
+
+def attn_mla_sparse(q_c, q_pe, ckv_pool, kpe_pool, o, slots, sm_scale, lse=False, workspace=None):
+    """Sparse MLA attention (lc_attn_mla_sparse_f16 / _bf16, picked by q_c's dtype): q_c, o [T,H,512], q_pe [T,H,64]; ckv_pool, kpe_pool the
+    latent pools as [num_pages,page_size,D] or flat [num_slots,D], all float16 or all bfloat16; slots int32 [T,topk] on the DEVICE (read by the
+    kernel only): slots[t, j] = page x page_size + offset of key j of token t, an entry outside [0, num_slots) (-1 included) is not a key.
+    sm_scale, lse and workspace (attn_mla_sparse_workspace_bytes(...) bytes) as in attn_mla_paged; a token without a key: O = 0, lse = -inf."""
+    import torch
+    if q_c.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q_c must be float16 or bfloat16, got {q_c.dtype}")
+    if any(t.dtype != q_c.dtype for t in (q_pe, ckv_pool, kpe_pool, o)):
+        raise TypeError(f"q_c / q_pe / ckv_pool / kpe_pool / o must share one 16-bit dtype, got {q_c.dtype} / {q_pe.dtype} / {ckv_pool.dtype} / "
+                        f"{kpe_pool.dtype} / {o.dtype}")
+    if slots.dtype != torch.int32:
+        raise TypeError(f"slots must be int32, got {slots.dtype}")
+    if q_c.dim() != 3 or q_pe.dim() != 3 or ckv_pool.dim() not in (2, 3) or kpe_pool.dim() != ckv_pool.dim() or slots.dim() != 2:
+        _shape_err("[T,H,Dc] / [T,H,Dr] / pools [num_pages,page_size,D] or [num_slots,D] / slots [T,topk] expected")
+    T, H, Dc = q_c.shape
+    Dr = q_pe.shape[2]
+    num_slots = ckv_pool.numel() // ckv_pool.shape[-1]
+    if (tuple(q_pe.shape) != (T, H, Dr) or tuple(o.shape) != (T, H, Dc) or ckv_pool.shape[-1] != Dc or kpe_pool.shape[-1] != Dr
+            or tuple(kpe_pool.shape[:-1]) != tuple(ckv_pool.shape[:-1]) or slots.shape[0] != T):
+        _shape_err(f"q_c {tuple(q_c.shape)} q_pe {tuple(q_pe.shape)} ckv_pool {tuple(ckv_pool.shape)} kpe_pool {tuple(kpe_pool.shape)} o {tuple(o.shape)} "
+                   f"slots {tuple(slots.shape)}")
+    plain = lse is False
+    outs = () if plain else (_lse_out(q_c, lse),)
+    _need_gpu(q_c, q_pe, ckv_pool, kpe_pool, o, *outs, slots)
+    symbol = "lc_attn_mla_sparse_bf16" if q_c.dtype == torch.bfloat16 else "lc_attn_mla_sparse_f16"
+    check(getattr(load(), symbol)(_ptr(q_c), _ptr(q_pe), _ptr(ckv_pool), _ptr(kpe_pool), _ptr(o), _ptr(outs[0]) if outs else None, _ptr(slots), T, H,
+                                  slots.shape[1], num_slots, Dc, Dr, float(sm_scale), 0, *_workspace_args(workspace), _stream()), symbol)
+    return o if plain else (o, outs[0])
+
+
+def attn_mla_sparse_workspace_bytes(T, H, topk, Dc=512, Dr=64) -> int:
+    """Bytes of partials the current plan of this shape needs: S x T H x (Dc + 1) floats, 0 for one range or a refused shape."""
+    return int(load().lc_attn_mla_sparse_workspace_bytes(T, H, topk, Dc, Dr))
+
+
+def attn_mla_sparse_kernel_name(T, H, topk, Dc=512, Dr=64, bf16=False) -> str:
+    """"attn_mla_sparse_kernel" / "attn_mla_sparse_bf16_kernel", + " + attn_mla_sparse_combine_[bf16_]kernel xS" with S > 1 ranges."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_mla_sparse_kernel_name(T, H, topk, Dc, Dr, 0, int(bf16), buf, 128), "lc_attn_mla_sparse_kernel_name")
     return buf.value.decode()
 
 

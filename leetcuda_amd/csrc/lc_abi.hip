@@ -169,6 +169,19 @@ int mla_kv8_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool8
   return launch_attn_mla_kv8(p, a, workspace);
 }
 
+// ... and the two sparse ones: an MlaSparseCall, check_attn_mla_sparse, launch_attn_mla_sparse (tu_attn_mla_sparse.hip)
+int mla_sparse_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse, const int* slots, int T,
+                   int H, int topk, int num_slots, int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  const MlaSparseCall c{T, H, topk, num_slots, Dc, Dr, flags, sm_scale, bf16};
+  const MlaSparsePtrs a{static_cast<const half_t*>(Qc), static_cast<const half_t*>(Qpe), static_cast<const half_t*>(CKVpool),
+                        static_cast<const half_t*>(KPEpool), static_cast<half_t*>(O), lse, slots, static_cast<hipStream_t>(stream)};
+  MlaSparsePlan p;
+  if (int rc = check_attn_mla_sparse(c, &a, &p)) return rc;
+  if (workspace && (workspace_bytes < mla_sparse_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_mla_sparse(p, a, workspace);
+}
+
 // The four latent-cache append entries state an MlaAppendCall; check_mla_append (tu_plan.hip) checks it, launch_mla_append
 // (tu_mla_append.hip) runs it
 int mla_append_run(bool kv8, bool bf16, const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool,
@@ -786,6 +799,34 @@ int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_
   MlaPlan p;
   if (int rc = check_attn_mla(MlaCall{B, H, T, max_nq, 1, page_size, max_pages, Dc, Dr, flags, 1.f, bf16 != 0, true}, nullptr, &p)) return rc;
   format_attn_mla(p, buf, buflen);
+  return LC_OK;
+}
+
+// Sparse multi-head latent attention over per-token selected pool slots (attn_mla_sparse.hip): mla_sparse_run above
+int lc_attn_mla_sparse_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse, const int* slots, int T,
+                           int H, int topk, int num_slots, int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  return mla_sparse_run(false, Qc, Qpe, CKVpool, KPEpool, O, lse, slots, T, H, topk, num_slots, Dc, Dr, sm_scale, flags, workspace, workspace_bytes,
+                        stream);
+}
+
+int lc_attn_mla_sparse_bf16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse, const int* slots, int T,
+                            int H, int topk, int num_slots, int Dc, int Dr, float sm_scale, int flags, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  return mla_sparse_run(true, Qc, Qpe, CKVpool, KPEpool, O, lse, slots, T, H, topk, num_slots, Dc, Dr, sm_scale, flags, workspace, workspace_bytes,
+                        stream);
+}
+
+size_t lc_attn_mla_sparse_workspace_bytes(int T, int H, int topk, int Dc, int Dr) {
+  MlaSparsePlan p;
+  return check_attn_mla_sparse(MlaSparseCall{T, H, topk, 1, Dc, Dr, 0, 1.f, false}, nullptr, &p) == LC_OK ? mla_sparse_workspace_bytes(p) : 0;
+}
+
+int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaSparsePlan p;
+  if (int rc = check_attn_mla_sparse(MlaSparseCall{T, H, topk, 1, Dc, Dr, flags, 1.f, bf16 != 0}, nullptr, &p)) return rc;
+  format_attn_mla_sparse(p, buf, buflen);
   return LC_OK;
 }
 

@@ -295,6 +295,37 @@ inline size_t mla_workspace_bytes(const MlaPlan& p) {
 int launch_attn_mla(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla.hip; checked arguments
 int launch_attn_mla_kv8(const MlaPlan& p, const MlaPtrs& a, void* workspace);   // tu_attn_mla_kv8.hip; checked arguments, MlaCall::kv8
 
+// What a caller of a sparse latent attention entry states (lc_attn_mla_sparse_f16 / _bf16 and their two query calls): T query
+// tokens of H heads, each token with its own row of topk pool slots (slots [T, topk]; an entry outside [0, num_slots) is not a key) over the
+// flat pools [num_slots, Dc] and [num_slots, Dr].  The plan: attn_mla_sparse_kernel<BF16> on T x RB x S workgroups, RB = ceil(H / 64) row blocks
+// of one token's heads, S ranges of the ceil(topk / 64) tiles, S > 1 followed by attn_mla_sparse_combine_kernel<BF16>.  S is the decode rule on
+// T x RB groups: the smallest S that gives every CU a workgroup, at least 4 tiles a range, at most 64; forced by "attn_decode_split".
+struct MlaSparseCall {
+  int T, H, topk, num_slots, Dc, Dr, flags;   // (the query calls state num_slots = 1: it decides nothing)
+  float sm_scale;                             // the caller's softmax scale (the query calls: 1)
+  bool bf16;                                  // Q, O and the pools are bfloat16: picks the kernels (and their names) and nothing else
+};
+struct MlaSparsePtrs {
+  const half_t *Qc, *Qpe;                     // [T,H,Dc], [T,H,Dr] (16-bit lanes: fp16 or, MlaSparseCall::bf16, bfloat16)
+  const half_t *CKV, *KPE;                    // the pools
+  half_t* O;                                  // [T,H,Dc]
+  float* lse;                                 // device float[T H] or nullptr = none
+  const int* slots;                           // device int32 [T, topk]
+  hipStream_t st;
+};
+struct MlaSparsePlan {
+  MlaSparseCall call;   // what was planned
+  int RB, S;
+};
+// The checks in check_attn_mla's order, then the plan.  a: the run call's pointers (nullptr: a query call)
+int check_attn_mla_sparse(const MlaSparseCall& c, const MlaSparsePtrs* a, MlaSparsePlan* p);   // tu_plan.hip
+void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen);   // "attn_mla_sparse_kernel", "attn_mla_sparse_bf16_kernel + attn_mla_sparse_combine_bf16_kernel x3"
+// bytes of fp32 partials a plan with S > 1 needs: S x T H x (Dc + 1) floats; 0 for S = 1
+inline size_t mla_sparse_workspace_bytes(const MlaSparsePlan& p) {
+  return p.S > 1 ? (size_t)p.S * (size_t)p.call.T * p.call.H * (size_t)(p.call.Dc + 1) * sizeof(float) : 0;
+}
+int launch_attn_mla_sparse(const MlaSparsePlan& p, const MlaSparsePtrs& a, void* workspace);   // tu_attn_mla_sparse.hip; checked arguments
+
 // What a caller of a latent-cache append entry states (lc_mla_append_paged_f16 / _bf16 / _kv8 / _kv8_bf16 and their name call):
 // the write side of the cache MlaCall reads — RMSNorm of the latent row, rotation of k_pe and of the H q_pe rows, the append through the block
 // table, on a ragged batch.  Nothing to plan: one kernel, mla_append_paged_[kv8_][bf16_]kernel<INTERLEAVED>, on

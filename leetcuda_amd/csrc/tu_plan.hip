@@ -832,6 +832,37 @@ void format_attn_mla(const MlaPlan& p, char* buf, int buflen) {
   else snprintf(buf, buflen, "attn_mla_paged_%s%skernel", k8, bf);
 }
 
+// Sparse multi-head latent attention (lc_plan.h MlaSparseCall).  The statuses in check_attn_mla's order: flags, NULL pointers
+// (lse may be one) and the scale, the shape — dims, the 32-bit row count, the grid —, alignment, the head dims.  The plan: RB row blocks of 64
+// of ONE token's H heads, and the decode rule's S on T x RB groups over ceil(topk / 64) tiles: host quantities only.
+int check_attn_mla_sparse(const MlaSparseCall& c, const MlaSparsePtrs* a, MlaSparsePlan* p) {
+  if (c.flags != 0) return LC_ERR_ARG;   // (no causal flag: the indexer selected visible keys)
+  if (a && (!a->Qc || !a->Qpe || !a->CKV || !a->KPE || !a->O || !a->slots)) return LC_ERR_ARG;   // (lse: NULL = none)
+  // (decided on the bit pattern: this unit is compiled with -fno-honor-nans.)  Finite and > 0: exponent not all ones, sign clear, not zero
+  const uint32_t sb = __builtin_bit_cast(uint32_t, c.sm_scale);
+  if ((sb & 0x7f800000u) == 0x7f800000u || (sb >> 31) != 0 || sb == 0) return LC_ERR_ARG;
+  if (c.T <= 0 || c.H <= 0 || c.topk <= 0 || c.num_slots <= 0) return LC_ERR_SHAPE;
+  if ((long)c.T * c.H > 0x7fffffffL) return LC_ERR_SHAPE;                                    // rows are counted in 32 bits
+  const int RB = (c.H + 63) / 64;
+  if ((size_t)c.T * (size_t)RB * 64 > 0x7fffffffull) return LC_ERR_SHAPE;                    // 1-D grid of T x RB x S workgroups, S <= 64
+  if (a && (!aligned16(a->Qc) || !aligned16(a->Qpe) || !aligned16(a->CKV) || !aligned16(a->KPE) || !aligned16(a->O) || ((uintptr_t)a->slots & 3) != 0))
+    return LC_ERR_SHAPE;
+  if (c.Dc != 512 || c.Dr != 64) return LC_ERR_HEADDIM;
+  const Knobs k = read_knobs();
+  long S = k.attn_decode_split;
+  if (S <= 0) {
+    const long groups = (long)c.T * RB, tiles = ((long)c.topk + 63) / 64;
+    S = std::max(1L, std::min({(rule_cus(k) + groups - 1) / groups, tiles / 4, 64L}));
+  }
+  *p = MlaSparsePlan{c, RB, (int)S};
+  return LC_OK;
+}
+void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen) {
+  const char* bf = p.call.bf16 ? "bf16_" : "";
+  if (p.S > 1) snprintf(buf, buflen, "attn_mla_sparse_%skernel + attn_mla_sparse_combine_%skernel x%d", bf, bf, p.S);
+  else snprintf(buf, buflen, "attn_mla_sparse_%skernel", bf);
+}
+
 // RMSNorm + rotary embedding + append to the latent cache (lc_plan.h MlaAppendCall).  The pool geometry — page size, the 2 GiB
 // span of one sequence's latent rows, T H rows in 32 bits — is check_attn_mla's, so that a cache this call accepts is one the attention call of
 // the same step accepts.  Strides are in elements, multiples of 8 (16-byte chunks), at least the width of what they step over.
