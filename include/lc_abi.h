@@ -866,7 +866,8 @@ int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_
  * stream's cached one; a captured stream or a failed lease runs S = 1 — and attn_mla_sparse_combine_kernel<BF16>.
  * lc_attn_mla_sparse_workspace_bytes: those bytes (0: S = 1 or a refused shape); lc_attn_mla_sparse_kernel_name never launches:
  * "attn_mla_sparse_kernel" / "attn_mla_sparse_bf16_kernel", S > 1: "... + attn_mla_sparse_combine_[bf16_]kernel xS", and the run call's status.
- * Not here: an fp8 latent pool, per-token topk lengths (pad a shorter row with -1), the indexer itself, other (Dc, Dr). */
+ * Not here: an fp8 latent pool, per-token topk lengths (pad a shorter row with -1), other (Dc, Dr).  (The indexer that produces `slots`:
+ * lc_mla_index_logits_* and lc_mla_index_topk below.) */
 int lc_attn_mla_sparse_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
                            const int* slots, int T, int H, int topk, int num_slots, int Dc, int Dr,
                            float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
@@ -875,6 +876,58 @@ int lc_attn_mla_sparse_bf16(const void* Qc, const void* Qpe, const void* CKVpool
                             float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
 size_t lc_attn_mla_sparse_workspace_bytes(int T, int H, int topk, int Dc, int Dr);
 int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen);
+
+/* EXTENSION: the LIGHTNING INDEXER of DeepSeek-V3.2's sparse attention (mla_index_logits.hip, mla_index_topk.hip): what
+ * produces the `slots` lc_attn_mla_sparse_* reads.  Two entries on the ragged batch of lc_attn_mla_paged_*; [lc_mla_append_paged_* ->
+ * lc_mla_index_logits_* -> lc_mla_index_topk -> lc_attn_mla_sparse_*] is one captured graph (no workspace, nothing allocated).
+ *
+ * lc_mla_index_logits_f16 / _bf16: for query token t of sequence b and every visible key position j
+ *     logits[t, j] = sum_{h < Hi} w[t, h] max(0, sum_{d < Di} Qi[t, h, d] Ki[slot(b, j), d]),   (Hi, Di) = (64, 128)
+ *   Qi           [T, 64, 128] token-major, 16-bit (fp16, _bf16: bfloat16), 16-byte aligned
+ *   w            device float32 [T, 64]; the caller folds the softmax scale, Hi^-1/2 and any quantisation scale into it
+ *   Kipool       [num_pages, page_size, 128] in Qi's element type, 16-byte aligned: the paged layout at Hkv = 1
+ *   logits       device float32 [T, ld], ld >= max_pages x page_size, ld % 4 == 0; row offsets are 64-bit
+ *   cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages: exactly as in lc_attn_mla_paged_* — kv_len[b] is the length
+ *                after the step's append, clamped to max_pages x page_size; token i of sequence b sits at position L_b - Nq_b + i; page ids are
+ *                clamped into the pool; table entries behind ceil(L_b / page_size) are not read
+ * Visible keys are j < n_t: n_t = L_b, under LC_ATTN_CAUSAL (the only flag) clamp(position + 1, 0, L_b).  The kernel writes exactly columns
+ * [0, n_t) of row t; columns at and behind n_t and the rows of tokens no sequence owns are not written.  Arithmetic: fp32 MFMA accumulation of
+ * the 128 products, max(., 0) in fp32, ONE fp32 multiply by w[t, h], an fp32 sum over the heads; nothing is rounded to 16 bits.
+ * Status, in this order: an unknown flag, a NULL pointer: LC_ERR_ARG; a non-positive dim, max_nq > T, page_size not a power of two >= 16, a pool
+ * of more than 2^31 - 1 slots, ld < max_pages x page_size or ld % 4 != 0, the grid bound (B ceil(max_nq / 8) 64 > 2^31 - 1), Qi or Kipool off 16
+ * bytes, w, logits or an int array off 4 bytes: LC_ERR_SHAPE; (Hi, Di) != (64, 128): LC_ERR_HEADDIM.
+ * mla_index_logits_kernel<BF16> on B x ceil(max_nq / 8) x S workgroups; S key ranges from B, max_nq, max_pages x page_size and the CU count
+ * only — nothing is reduced over keys, so there is no combine kernel, no workspace, and S changes no bit.
+ * lc_mla_index_logits_kernel_name never launches: "mla_index_logits_kernel" / "mla_index_logits_bf16_kernel", and the run call's status.
+ *
+ * lc_mla_index_topk: slots int32 [T, topk] (4-byte aligned, T topk <= 2^31 - 1), the argument lc_attn_mla_sparse_* reads.  n_t is derived from
+ * cu_q / kv_len / flags exactly as above, never from the logits.  ALL topk entries of EVERY row t < T are written: the min(n_t, topk) columns
+ * j < n_t that come first when the columns are ordered by logit descending in the IEEE totalOrder of the fp32 bit patterns (-0 < +0; a NaN
+ * sorts by its sign and payload like any other pattern), lower j first among equal patterns; written in ASCENDING j, each as
+ * clamp(block_table[b, j / page_size], 0, num_pages - 1) x page_size + j % page_size; the rest of the row is -1; a token no sequence owns and a
+ * token with n_t = 0 get a row of -1.  The output is a pure function of the inputs: the same bits on every run and replay.
+ * Status: a flag, a NULL pointer: LC_ERR_ARG; a non-positive dim (topk included), max_nq > T, the page size, the pool and ld as above,
+ * T topk > 2^31 - 1, a pointer off 4 bytes: LC_ERR_SHAPE.  mla_index_topk_kernel, one workgroup of 1024 threads a row: a three-pass radix
+ * select (11, 11, 10 bits) and one ordered compaction pass; lc_mla_index_topk_kernel_name: "mla_index_topk_kernel" and the run call's status.
+ * Not here: fp8 index keys and queries with per-token scales, writing the index-key pool (lc_rope_append_varlen_* at Hkv = 1, D = 128 writes
+ * this layout; see DESIGN), logits and selection fused so that [T, L] never reaches memory, other (Hi, Di), per-token topk, a row spread
+ * over several workgroups. */
+int lc_mla_index_logits_f16(const void* Qi, const float* w, const void* Kipool, float* logits,
+                            const int* cu_q, const int* block_table, const int* kv_len,
+                            int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                            int Di, long long ld, int flags, void* stream);
+int lc_mla_index_logits_bf16(const void* Qi, const float* w, const void* Kipool, float* logits,
+                             const int* cu_q, const int* block_table, const int* kv_len,
+                             int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                             int Di, long long ld, int flags, void* stream);
+int lc_mla_index_logits_kernel_name(int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld,
+                                    int flags, int bf16, char* buf, int buflen);
+int lc_mla_index_topk(const float* logits, int* slots,
+                      const int* cu_q, const int* block_table, const int* kv_len,
+                      int B, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                      long long ld, int topk, int flags, void* stream);
+int lc_mla_index_topk_kernel_name(int B, int T, int max_nq, int num_pages, int page_size, int max_pages, long long ld, int topk, int flags,
+                                  char* buf, int buflen);
 
 /* EXTENSION: RMSNorm + rotary embedding + append for the paged LATENT cache (mla_append_paged.hip): the write side of
  * lc_attn_mla_paged_*.  ONE launch takes a step's projection outputs as they sit in memory and leaves what the attention entries read: the

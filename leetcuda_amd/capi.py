@@ -152,6 +152,13 @@ SYMBOLS = {
     "lc_attn_mla_sparse_bf16": (_i, [_vp] * 7 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_sparse_workspace_bytes": (C.c_size_t, [_i] * 5),
     "lc_attn_mla_sparse_kernel_name": (_i, [_i] * 7 + [_cp, _i]),
+    # the lightning indexer: Qi, w, Kipool, logits, cu_q, block_table, kv_len, B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, flags,
+    # stream; logits, slots, cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages, ld, topk, flags, stream
+    "lc_mla_index_logits_f16": (_i, [_vp] * 7 + [_i] * 8 + [C.c_longlong, _i, _vp]),
+    "lc_mla_index_logits_bf16": (_i, [_vp] * 7 + [_i] * 8 + [C.c_longlong, _i, _vp]),
+    "lc_mla_index_logits_kernel_name": (_i, [_i] * 8 + [C.c_longlong, _i, _i, _cp, _i]),
+    "lc_mla_index_topk": (_i, [_vp] * 5 + [_i] * 6 + [C.c_longlong, _i, _i, _vp]),
+    "lc_mla_index_topk_kernel_name": (_i, [_i] * 6 + [C.c_longlong, _i, _i, _cp, _i]),
     # RMSNorm + rope + append to the latent cache: CKVnew, KPEnew, Qpe, Qpe_out, CKVpool, KPEpool, gamma (or NULL), cos_sin, cu_q, block_table,
     # kv_len, [ckv_scale (or NULL),] B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, the four strides, flags, stream
     "lc_mla_append_paged_f16": (_i, [_vp] * 11 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
@@ -1660,6 +1667,93 @@ def attn_mla_sparse_kernel_name(T, H, topk, Dc=512, Dr=64, bf16=False) -> str:
     """"attn_mla_sparse_kernel" / "attn_mla_sparse_bf16_kernel", + " + attn_mla_sparse_combine_[bf16_]kernel xS" with S > 1 ranges."""
     buf = C.create_string_buffer(128)
     check(load().lc_attn_mla_sparse_kernel_name(T, H, topk, Dc, Dr, 0, int(bf16), buf, 128), "lc_attn_mla_sparse_kernel_name")
+    return buf.value.decode()
+
+
+# The lightning indexer that produces attn_mla_sparse's slots (lc_mla_index_logits_f16 / _bf16, lc_mla_index_topk; DESIGN.md section 4.3u)
+
+def _mla_index_logits_buf(logits, T, block_table, page_size):
+    import torch
+    if logits.dtype != torch.float32:
+        raise TypeError(f"logits must be float32, got {logits.dtype}")
+    if logits.dim() != 2 or logits.shape[0] != T or logits.stride(1) != 1 or logits.shape[1] < block_table.shape[1] * page_size:
+        _shape_err(f"logits {tuple(logits.shape)}: [T = {T}, >= max_pages x page_size = {block_table.shape[1] * page_size}] with dense rows expected")
+    return logits.stride(0) if T > 1 else logits.shape[1]
+
+
+def mla_index_logits(q_i, w, ki_pool, logits, cu_q, block_table, kv_len, max_nq, causal=True):
+    """Index logits (lc_mla_index_logits_f16 / _bf16, picked by q_i's dtype): q_i [T,64,128] and ki_pool [num_pages,page_size,128] both float16 or
+    both bfloat16, w float32 [T,64], logits float32 [T, >= max_pages x page_size] (rows may be strided); cu_q, block_table, kv_len, max_nq as in
+    attn_mla_paged.  Writes logits[t, j] = sum_h w[t, h] relu(q_i[t, h] . ki[slot(b, j)]) for the visible j < n_t only; returns logits."""
+    import torch
+    if q_i.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q_i must be float16 or bfloat16, got {q_i.dtype}")
+    if ki_pool.dtype != q_i.dtype:
+        raise TypeError(f"q_i / ki_pool must share one 16-bit dtype, got {q_i.dtype} / {ki_pool.dtype}")
+    if w.dtype != torch.float32:
+        raise TypeError(f"w must be float32, got {w.dtype}")
+    if q_i.dim() != 3 or ki_pool.dim() != 3 or w.dim() != 2:
+        _shape_err("[T,Hi,Di] / [num_pages,page_size,Di] / w [T,Hi] expected")
+    T, Hi, Di = q_i.shape
+    num_pages, page_size = ki_pool.shape[:2]
+    if ki_pool.shape[2] != Di or tuple(w.shape) != (T, Hi):
+        _shape_err(f"q_i {tuple(q_i.shape)} ki_pool {tuple(ki_pool.shape)} w {tuple(w.shape)}")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    ld = _mla_index_logits_buf(logits, T, block_table, page_size)
+    _need_gpu(q_i, w, ki_pool, cu_q, block_table, kv_len)
+    if not logits.is_cuda:
+        raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    symbol = "lc_mla_index_logits_bf16" if q_i.dtype == torch.bfloat16 else "lc_mla_index_logits_f16"
+    check(getattr(load(), symbol)(_ptr(q_i), _ptr(w), _ptr(ki_pool), _ptr(logits), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), B, Hi, T, max_nq,
+                                  num_pages, page_size, block_table.shape[1], Di, ld, ATTN_CAUSAL if causal else 0, _stream()), symbol)
+    return logits
+
+
+def mla_index_topk(logits, slots, cu_q, block_table, kv_len, max_nq, causal=True, *, page_size, num_pages):
+    """Slot selection (lc_mla_index_topk): logits float32 [T, >= max_pages x page_size] as mla_index_logits left it, slots int32 [T,topk] on the
+    device; page_size / num_pages (keywords, required): the geometry of the pool the slots index.  Every row of slots is written whole: the pool slots of the
+    min(n_t, topk) largest visible logits (totalOrder of the bit patterns, lower position first among equals) in ascending position, then
+    -1.  Returns slots."""
+    import torch
+    if slots.dtype != torch.int32:
+        raise TypeError(f"slots must be int32, got {slots.dtype}")
+    if slots.dim() != 2 or logits.dim() != 2 or slots.shape[0] != logits.shape[0]:
+        _shape_err(f"logits {tuple(logits.shape)} slots {tuple(slots.shape)}: [T,ld] / [T,topk] expected")
+    T, topk = slots.shape
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    ld = _mla_index_logits_buf(logits, T, block_table, page_size)
+    _need_gpu(slots, cu_q, block_table, kv_len)
+    if not logits.is_cuda:
+        raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    check(load().lc_mla_index_topk(_ptr(logits), _ptr(slots), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), B, T, max_nq, num_pages, page_size,
+                                   block_table.shape[1], ld, topk, ATTN_CAUSAL if causal else 0, _stream()), "lc_mla_index_topk")
+    return slots
+
+
+def mla_index_select(q_i, w, ki_pool, logits, slots, cu_q, block_table, kv_len, max_nq, causal=True):
+    """The indexer of one step on the current stream: mla_index_logits into the caller's `logits` buffer, then mla_index_topk into `slots`
+    (int32 [T,topk]), which is returned: the argument of attn_mla_sparse.  Nothing is allocated: legal under graph capture."""
+    mla_index_logits(q_i, w, ki_pool, logits, cu_q, block_table, kv_len, max_nq, causal=causal)
+    return mla_index_topk(logits, slots, cu_q, block_table, kv_len, max_nq, causal=causal, page_size=ki_pool.shape[1], num_pages=ki_pool.shape[0])
+
+
+def mla_index_logits_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, ld=None, Hi=64, Di=128, causal=True, bf16=False) -> str:
+    """"mla_index_logits_kernel" / "mla_index_logits_bf16_kernel" (ld: max_pages x page_size unless given)"""
+    buf = C.create_string_buffer(128)
+    check(load().lc_mla_index_logits_kernel_name(B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, max_pages * page_size if ld is None else ld,
+                                                 ATTN_CAUSAL if causal else 0, int(bf16), buf, 128), "lc_mla_index_logits_kernel_name")
+    return buf.value.decode()
+
+
+def mla_index_topk_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, topk, ld=None, causal=True) -> str:
+    """"mla_index_topk_kernel" """
+    buf = C.create_string_buffer(128)
+    check(load().lc_mla_index_topk_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, max_pages * page_size if ld is None else ld, topk,
+                                               ATTN_CAUSAL if causal else 0, buf, 128), "lc_mla_index_topk_kernel_name")
     return buf.value.decode()
 
 

@@ -830,6 +830,62 @@ int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int f
   return LC_OK;
 }
 
+// The lightning indexer (mla_index_logits.hip, mla_index_topk.hip): an MlaIndexCall, check_mla_index_* (tu_plan.hip),
+// launch_mla_index_* (tu_mla_index.hip)
+static int mla_index_logits_run(bool bf16, const void* Qi, const float* w, const void* Kipool, float* logits, const int* cu_q, const int* block_table,
+                                const int* kv_len, int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld,
+                                int flags, void* stream) {
+  const MlaIndexCall c{B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, 1, flags, bf16};
+  const MlaIndexPtrs a{static_cast<const half_t*>(Qi), w, static_cast<const half_t*>(Kipool), logits, nullptr, cu_q, block_table, kv_len,
+                       static_cast<hipStream_t>(stream)};
+  MlaIndexPlan p;
+  if (int rc = check_mla_index_logits(c, &a, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_mla_index_logits(p, a);
+}
+
+int lc_mla_index_logits_f16(const void* Qi, const float* w, const void* Kipool, float* logits, const int* cu_q, const int* block_table,
+                            const int* kv_len, int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld,
+                            int flags, void* stream) {
+  return mla_index_logits_run(false, Qi, w, Kipool, logits, cu_q, block_table, kv_len, B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, flags,
+                              stream);
+}
+
+int lc_mla_index_logits_bf16(const void* Qi, const float* w, const void* Kipool, float* logits, const int* cu_q, const int* block_table,
+                             const int* kv_len, int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld,
+                             int flags, void* stream) {
+  return mla_index_logits_run(true, Qi, w, Kipool, logits, cu_q, block_table, kv_len, B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, flags,
+                              stream);
+}
+
+int lc_mla_index_logits_kernel_name(int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld, int flags,
+                                    int bf16, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaIndexPlan p;
+  if (int rc = check_mla_index_logits(MlaIndexCall{B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, 1, flags, bf16 != 0}, nullptr, &p)) return rc;
+  snprintf(buf, buflen, "mla_index_logits_%skernel", bf16 ? "bf16_" : "");
+  return LC_OK;
+}
+
+int lc_mla_index_topk(const float* logits, int* slots, const int* cu_q, const int* block_table, const int* kv_len, int B, int T, int max_nq,
+                      int num_pages, int page_size, int max_pages, long long ld, int topk, int flags, void* stream) {
+  const MlaIndexCall c{B, 64, T, max_nq, num_pages, page_size, max_pages, 128, ld, topk, flags, false};
+  const MlaIndexPtrs a{nullptr, nullptr, nullptr, const_cast<float*>(logits), slots, cu_q, block_table, kv_len, static_cast<hipStream_t>(stream)};
+  MlaIndexPlan p;
+  if (int rc = check_mla_index_topk(c, &a, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_mla_index_topk(p, a);
+}
+
+int lc_mla_index_topk_kernel_name(int B, int T, int max_nq, int num_pages, int page_size, int max_pages, long long ld, int topk, int flags, char* buf,
+                                  int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaIndexPlan p;
+  if (int rc = check_mla_index_topk(MlaIndexCall{B, 64, T, max_nq, num_pages, page_size, max_pages, 128, ld, topk, flags, false}, nullptr, &p)) return rc;
+  snprintf(buf, buflen, "mla_index_topk_kernel");
+  return LC_OK;
+}
+
 // RMSNorm + rotary embedding + append to the paged latent cache (mla_append_paged.hip): mla_append_run above
 int lc_mla_append_paged_f16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool, const float* gamma,
                             const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int T, int max_nq,

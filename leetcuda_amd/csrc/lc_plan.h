@@ -326,6 +326,37 @@ inline size_t mla_sparse_workspace_bytes(const MlaSparsePlan& p) {
 }
 int launch_attn_mla_sparse(const MlaSparsePlan& p, const MlaSparsePtrs& a, void* workspace);   // tu_attn_mla_sparse.hip; checked arguments
 
+// What a caller of a lightning-indexer entry states (lc_mla_index_logits_f16 / _bf16, lc_mla_index_topk and their name calls):
+// the ragged batch of MlaCall over an index-key pool [num_pages, page_size, Di] (the paged layout at Hkv = 1), Hi index heads, fp32 logits
+// [T, ld].  The logits plan: mla_index_logits_kernel<BF16> on B x NB x S workgroups, NB = ceil(max_nq / 8) token blocks, S ranges of the 64-key
+// tiles: the smallest S that gives every CU four workgroups (two are resident at 240 registers), at least 4 tiles of ceil(Ncap / 64) a range, at
+// most 64 — host quantities only, never kv_len; no knob forces it: nothing is merged, so S changes no bit.  The top-k entry has nothing to
+// plan: mla_index_topk_kernel on T workgroups.
+struct MlaIndexCall {
+  int B, Hi, T, max_nq, num_pages, page_size, max_pages, Di;   // (the top-k entry states Hi = 64, Di = 128)
+  long long ld;                                                // floats between two rows of logits
+  int topk, flags;                                             // (the logits entries state topk = 1)
+  bool bf16;                                                   // Qi and the pool are bfloat16: picks the logits kernel (and its name)
+};
+struct MlaIndexPtrs {
+  const half_t* Qi;                          // [T,Hi,Di] (16-bit lanes); the top-k entry: unused
+  const float* w;                            // device float [T,Hi]; the top-k entry: unused
+  const half_t* Ki;                          // the index-key pool; the top-k entry: unused
+  float* logits;                             // device float [T,ld]: written by the logits entries, read by the top-k entry
+  int* slots;                                // device int32 [T,topk]: the top-k entry only
+  const int *cu_q, *block_table, *kv_len;    // device int32 [B + 1], [B,max_pages], [B]
+  hipStream_t st;
+};
+struct MlaIndexPlan {
+  MlaIndexCall call;   // what was planned
+  int NB, S;
+};
+// The checks in check_attn_mla's order, then the plan.  a: the run call's pointers (nullptr: a name call)
+int check_mla_index_logits(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p);   // tu_plan.hip
+int check_mla_index_topk(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p);     // tu_plan.hip
+int launch_mla_index_logits(const MlaIndexPlan& p, const MlaIndexPtrs& a);   // tu_mla_index.hip; checked arguments
+int launch_mla_index_topk(const MlaIndexPlan& p, const MlaIndexPtrs& a);     // tu_mla_index.hip; checked arguments
+
 // What a caller of a latent-cache append entry states (lc_mla_append_paged_f16 / _bf16 / _kv8 / _kv8_bf16 and their name call):
 // the write side of the cache MlaCall reads — RMSNorm of the latent row, rotation of k_pe and of the H q_pe rows, the append through the block
 // table, on a ragged batch.  Nothing to plan: one kernel, mla_append_paged_[kv8_][bf16_]kernel<INTERLEAVED>, on

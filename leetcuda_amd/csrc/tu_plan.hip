@@ -863,6 +863,45 @@ void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen) {
   else snprintf(buf, buflen, "attn_mla_sparse_%skernel", bf);
 }
 
+// The lightning indexer (lc_plan.h MlaIndexCall).  Both entries: flags and NULL pointers, then the shape — dims, max_nq, the
+// page size, the pool capacity in 32 bits, ld —, the entry's own bound, alignment; the logits entries then the head dims.
+namespace {
+int check_mla_index_shape(const MlaIndexCall& c) {
+  if (c.B <= 0 || c.Hi <= 0 || c.T <= 0 || c.max_nq <= 0 || c.num_pages <= 0 || c.max_pages <= 0 || c.Di <= 0 || c.topk <= 0) return LC_ERR_SHAPE;
+  if (c.max_nq > c.T) return LC_ERR_SHAPE;
+  if (c.page_size < 16 || (c.page_size & (c.page_size - 1)) != 0) return LC_ERR_SHAPE;   // a power of two >= 16: a 16-key block never straddles a page
+  const long ncap = (long)c.max_pages * c.page_size;
+  if (ncap > 0x7fffffffL || (long)c.num_pages * c.page_size > 0x7fffffffL) return LC_ERR_SHAPE;   // positions and slots are 32-bit
+  if (c.ld < ncap || (c.ld & 3) != 0) return LC_ERR_SHAPE;
+  return LC_OK;
+}
+bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+}  // namespace
+int check_mla_index_logits(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p) {
+  if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (a && (!a->Qi || !a->w || !a->Ki || !a->logits || !a->cu_q || !a->block_table || !a->kv_len)) return LC_ERR_ARG;
+  if (int rc = check_mla_index_shape(c)) return rc;
+  const long NB = ((long)c.max_nq + 7) / 8;
+  if ((size_t)c.B * (size_t)NB * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x NB x S workgroups, S <= 64
+  if (a && (!aligned16(a->Qi) || !aligned16(a->Ki) || !aligned4(a->w) || !aligned4(a->logits) || !aligned4(a->cu_q) || !aligned4(a->block_table) ||
+            !aligned4(a->kv_len)))
+    return LC_ERR_SHAPE;
+  if (c.Hi != 64 || c.Di != 128) return LC_ERR_HEADDIM;
+  const long groups = (long)c.B * NB, tiles = ((long)c.max_pages * c.page_size + 63) / 64;
+  const long S = std::max(1L, std::min({(4L * rule_cus(read_knobs()) + groups - 1) / groups, tiles / 4, 64L}));
+  *p = MlaIndexPlan{c, (int)NB, (int)S};
+  return LC_OK;
+}
+int check_mla_index_topk(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p) {
+  if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (a && (!a->logits || !a->slots || !a->cu_q || !a->block_table || !a->kv_len)) return LC_ERR_ARG;
+  if (int rc = check_mla_index_shape(c)) return rc;
+  if ((long)c.T * c.topk > 0x7fffffffL) return LC_ERR_SHAPE;   // entries of slots are counted in 32 bits
+  if (a && (!aligned4(a->logits) || !aligned4(a->slots) || !aligned4(a->cu_q) || !aligned4(a->block_table) || !aligned4(a->kv_len))) return LC_ERR_SHAPE;
+  *p = MlaIndexPlan{c, 0, 1};
+  return LC_OK;
+}
+
 // RMSNorm + rotary embedding + append to the latent cache (lc_plan.h MlaAppendCall).  The pool geometry — page size, the 2 GiB
 // span of one sequence's latent rows, T H rows in 32 bits — is check_attn_mla's, so that a cache this call accepts is one the attention call of
 // the same step accepts.  Strides are in elements, multiples of 8 (16-byte chunks), at least the width of what they step over.
