@@ -831,7 +831,7 @@ int lc_attn_mla_paged_kernel_name(int B, int H, int T, int max_nq, int page_size
  * the shape.  lc_attn_mla_paged_workspace_bytes serves both element widths (the plan — RB, S, the grid — is the 16-bit call's).
  * lc_attn_mla_paged_kv8_kernel_name: "attn_mla_paged_kv8_kernel" / "attn_mla_paged_kv8_bf16_kernel", S > 1: "... + attn_mla_combine_[bf16_]kernel xS".
  * Writing the latent cache: lc_mla_append_paged_kv8 / _kv8_bf16 below.  Not here: an fp8 rope pool (an all-fp8 row of 576 bytes), per-block
- * scales, and what the 16-bit entry lacks. */
+ * scales, and what the 16-bit entry lacks.  (Per-token selected slots of this pool: lc_attn_mla_sparse_kv8 below.) */
 int lc_attn_mla_paged_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
                           const int* cu_q, const int* block_table, const int* kv_len, const float* ckv_scale,
                           int B, int H, int T, int max_nq, int num_pages, int page_size, int max_pages,
@@ -866,8 +866,8 @@ int lc_attn_mla_paged_kv8_kernel_name(int B, int H, int T, int max_nq, int page_
  * stream's cached one; a captured stream or a failed lease runs S = 1 — and attn_mla_sparse_combine_kernel<BF16>.
  * lc_attn_mla_sparse_workspace_bytes: those bytes (0: S = 1 or a refused shape); lc_attn_mla_sparse_kernel_name never launches:
  * "attn_mla_sparse_kernel" / "attn_mla_sparse_bf16_kernel", S > 1: "... + attn_mla_sparse_combine_[bf16_]kernel xS", and the run call's status.
- * Not here: an fp8 latent pool, per-token topk lengths (pad a shorter row with -1), other (Dc, Dr).  (The indexer that produces `slots`:
- * lc_mla_index_logits_* and lc_mla_index_topk below.) */
+ * Not here: per-token topk lengths (pad a shorter row with -1), other (Dc, Dr).  (An fp8 latent pool: lc_attn_mla_sparse_kv8 below; the
+ * indexer that produces `slots`: lc_mla_index_logits_* and lc_mla_index_topk below.) */
 int lc_attn_mla_sparse_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
                            const int* slots, int T, int H, int topk, int num_slots, int Dc, int Dr,
                            float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
@@ -876,6 +876,28 @@ int lc_attn_mla_sparse_bf16(const void* Qc, const void* Qpe, const void* CKVpool
                             float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
 size_t lc_attn_mla_sparse_workspace_bytes(int T, int H, int topk, int Dc, int Dr);
 int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen);
+
+/* EXTENSION: SPARSE MLA attention over an fp8 (e4m3) latent pool (attn_mla_sparse_kv8.hip): DeepSeek-V3.2-style serving
+ * keeps the latent cache in fp8 and attends sparsely over it.  lc_attn_mla_sparse_kv8 / _kv8_bf16 are lc_attn_mla_sparse_f16 / _bf16, argument
+ * for argument and rule for rule (the statuses and their order, `slots` and what is not a key, the token without a key, Dc = 512 / Dr = 64
+ * only, the workspace and capture behaviour, "attn_decode_split"), with two differences:
+ *   CKVpool8    [num_slots, 512] OCP e4m3fn BYTES, 16-byte aligned: the pool lc_mla_append_paged_kv8 writes and lc_attn_mla_paged_kv8 reads,
+ *               viewed flat; the value of an element is code x ckv_scale[0].  KPEpool stays 16-bit [num_slots, 64] in Q's element type
+ *   ckv_scale   lc_attn_mla_paged_kv8's argument, right behind slots: DEVICE float[1], 4-byte aligned, or NULL = 1.0, read by the kernel alone
+ *               and once per workgroup, so a replayed graph sees a new scale.  Off 4 bytes: LC_ERR_ARG, with the NULL pointers
+ * A key is 640 gathered bytes instead of 1152.  Codes are converted to the element type exactly and the scale is applied in fp32 where the dense
+ * fp8 entry applies it, so that under a power-of-two scale O and lse equal, bit for bit, lc_attn_mla_sparse_*'s on the dequantised pool (as
+ * long as code x scale is a normal number of the element type).  Codes 0x7f / 0xff are NaN; those of an invalid entry reach no product.
+ * lc_attn_mla_sparse_workspace_bytes serves both element widths (the plan — RB, S, the grid — is the 16-bit call's).  The name query:
+ * "attn_mla_sparse_kv8_kernel" / "attn_mla_sparse_kv8_bf16_kernel", S > 1: "... + attn_mla_sparse_combine_[bf16_]kernel xS".
+ * Not here: an fp8 rope pool, per-row or per-128-column scales (FlashMLA's 656-byte rows), fp8 index keys for the indexer. */
+int lc_attn_mla_sparse_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
+                           const int* slots, const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr,
+                           float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_mla_sparse_kv8_bf16(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
+                                const int* slots, const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr,
+                                float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
+int lc_attn_mla_sparse_kv8_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen);
 
 /* EXTENSION: the LIGHTNING INDEXER of DeepSeek-V3.2's sparse attention (mla_index_logits.hip, mla_index_topk.hip): what
  * produces the `slots` lc_attn_mla_sparse_* reads.  Two entries on the ragged batch of lc_attn_mla_paged_*; [lc_mla_append_paged_* ->

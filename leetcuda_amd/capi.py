@@ -152,6 +152,9 @@ SYMBOLS = {
     "lc_attn_mla_sparse_bf16": (_i, [_vp] * 7 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_sparse_workspace_bytes": (C.c_size_t, [_i] * 5),
     "lc_attn_mla_sparse_kernel_name": (_i, [_i] * 7 + [_cp, _i]),
+    "lc_attn_mla_sparse_kv8": (_i, [_vp] * 8 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_sparse_kv8_bf16": (_i, [_vp] * 8 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
+    "lc_attn_mla_sparse_kv8_kernel_name": (_i, [_i] * 7 + [_cp, _i]),
     # the lightning indexer: Qi, w, Kipool, logits, cu_q, block_table, kv_len, B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, flags,
     # stream; logits, slots, cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages, ld, topk, flags, stream
     "lc_mla_index_logits_f16": (_i, [_vp] * 7 + [_i] * 8 + [C.c_longlong, _i, _vp]),
@@ -1667,6 +1670,50 @@ def attn_mla_sparse_kernel_name(T, H, topk, Dc=512, Dr=64, bf16=False) -> str:
     """"attn_mla_sparse_kernel" / "attn_mla_sparse_bf16_kernel", + " + attn_mla_sparse_combine_[bf16_]kernel xS" with S > 1 ranges."""
     buf = C.create_string_buffer(128)
     check(load().lc_attn_mla_sparse_kernel_name(T, H, topk, Dc, Dr, 0, int(bf16), buf, 128), "lc_attn_mla_sparse_kernel_name")
+    return buf.value.decode()
+
+
+# ... and over an fp8 (e4m3) latent pool (lc_attn_mla_sparse_kv8 / _kv8_bf16; DESIGN.md section 4.3v)
+
+def attn_mla_sparse_kv8(q_c, q_pe, ckv_pool_u8, kpe_pool, o, slots, sm_scale, ckv_scale=None, lse=False, workspace=None):
+    """attn_mla_sparse over an fp8 latent pool (lc_attn_mla_sparse_kv8 / _kv8_bf16, picked by q_c's dtype): ckv_pool_u8 [num_pages,page_size,512]
+    or flat [num_slots,512] torch.uint8 holding e4m3fn codes — the pool mla_append_paged_kv8 writes —, an element's value is code x ckv_scale[0];
+    ckv_scale a 1-element float32 DEVICE tensor (read by the kernel only) or None = 1.0; kpe_pool stays 16-bit in q_c's dtype.  Every other
+    argument and the result: attn_mla_sparse (the workspace too: attn_mla_sparse_workspace_bytes serves both)."""
+    import torch
+    if q_c.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q_c must be float16 or bfloat16, got {q_c.dtype}")
+    if any(t.dtype != q_c.dtype for t in (q_pe, kpe_pool, o)) or ckv_pool_u8.dtype != torch.uint8:
+        raise TypeError(f"q_c / q_pe / kpe_pool / o must share one 16-bit dtype and ckv_pool_u8 be uint8, got {q_c.dtype} / {q_pe.dtype} / "
+                        f"{kpe_pool.dtype} / {o.dtype} and {ckv_pool_u8.dtype}")
+    if ckv_scale is not None and (ckv_scale.dtype != torch.float32 or ckv_scale.numel() != 1):
+        raise TypeError("ckv_scale must be None or a 1-element float32 tensor")
+    if slots.dtype != torch.int32:
+        raise TypeError(f"slots must be int32, got {slots.dtype}")
+    if q_c.dim() != 3 or q_pe.dim() != 3 or ckv_pool_u8.dim() not in (2, 3) or kpe_pool.dim() != ckv_pool_u8.dim() or slots.dim() != 2:
+        _shape_err("[T,H,Dc] / [T,H,Dr] / pools [num_pages,page_size,D] or [num_slots,D] / slots [T,topk] expected")
+    T, H, Dc = q_c.shape
+    Dr = q_pe.shape[2]
+    num_slots = ckv_pool_u8.numel() // ckv_pool_u8.shape[-1]
+    if (tuple(q_pe.shape) != (T, H, Dr) or tuple(o.shape) != (T, H, Dc) or ckv_pool_u8.shape[-1] != Dc or kpe_pool.shape[-1] != Dr
+            or tuple(kpe_pool.shape[:-1]) != tuple(ckv_pool_u8.shape[:-1]) or slots.shape[0] != T):
+        _shape_err(f"q_c {tuple(q_c.shape)} q_pe {tuple(q_pe.shape)} ckv_pool_u8 {tuple(ckv_pool_u8.shape)} kpe_pool {tuple(kpe_pool.shape)} "
+                   f"o {tuple(o.shape)} slots {tuple(slots.shape)}")
+    plain = lse is False
+    outs = () if plain else (_lse_out(q_c, lse),)
+    scales = () if ckv_scale is None else (ckv_scale,)
+    _need_gpu(q_c, q_pe, ckv_pool_u8, kpe_pool, o, *outs, slots, *scales)
+    symbol = "lc_attn_mla_sparse_kv8_bf16" if q_c.dtype == torch.bfloat16 else "lc_attn_mla_sparse_kv8"
+    check(getattr(load(), symbol)(_ptr(q_c), _ptr(q_pe), _ptr(ckv_pool_u8), _ptr(kpe_pool), _ptr(o), _ptr(outs[0]) if outs else None, _ptr(slots),
+                                  _ptr(ckv_scale) if scales else None, T, H, slots.shape[1], num_slots, Dc, Dr, float(sm_scale), 0,
+                                  *_workspace_args(workspace), _stream()), symbol)
+    return o if plain else (o, outs[0])
+
+
+def attn_mla_sparse_kv8_kernel_name(T, H, topk, Dc=512, Dr=64, bf16=False) -> str:
+    """"attn_mla_sparse_kv8_kernel" / "attn_mla_sparse_kv8_bf16_kernel", + " + attn_mla_sparse_combine_[bf16_]kernel xS" with S > 1 ranges."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_mla_sparse_kv8_kernel_name(T, H, topk, Dc, Dr, 0, int(bf16), buf, 128), "lc_attn_mla_sparse_kv8_kernel_name")
     return buf.value.decode()
 
 

@@ -182,6 +182,20 @@ int mla_sparse_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpo
   return launch_attn_mla_sparse(p, a, workspace);
 }
 
+// ... and the two over an fp8 latent pool: the same MlaSparseCall with kv8 = true and the scale pointer, launch_attn_mla_sparse_kv8
+int mla_sparse_kv8_run(bool bf16, const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse, const int* slots,
+                       const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr, float sm_scale, int flags, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  const MlaSparseCall c{T, H, topk, num_slots, Dc, Dr, flags, sm_scale, bf16, true};
+  const MlaSparsePtrs a{static_cast<const half_t*>(Qc), static_cast<const half_t*>(Qpe), static_cast<const half_t*>(CKVpool8),
+                        static_cast<const half_t*>(KPEpool), static_cast<half_t*>(O), lse, slots, static_cast<hipStream_t>(stream), ckv_scale};
+  MlaSparsePlan p;
+  if (int rc = check_attn_mla_sparse(c, &a, &p)) return rc;
+  if (workspace && (workspace_bytes < mla_sparse_workspace_bytes(p) || !aligned16(workspace))) return LC_ERR_ARG;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_mla_sparse_kv8(p, a, workspace);
+}
+
 // The four latent-cache append entries state an MlaAppendCall; check_mla_append (tu_plan.hip) checks it, launch_mla_append
 // (tu_mla_append.hip) runs it
 int mla_append_run(bool kv8, bool bf16, const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool,
@@ -826,6 +840,29 @@ int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int f
   if (!buf || buflen < 8) return LC_ERR_ARG;
   MlaSparsePlan p;
   if (int rc = check_attn_mla_sparse(MlaSparseCall{T, H, topk, 1, Dc, Dr, flags, 1.f, bf16 != 0}, nullptr, &p)) return rc;
+  format_attn_mla_sparse(p, buf, buflen);
+  return LC_OK;
+}
+
+// ... over an fp8 (e4m3) latent pool (attn_mla_sparse_kv8.hip): mla_sparse_kv8_run above
+int lc_attn_mla_sparse_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse, const int* slots,
+                           const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr, float sm_scale, int flags, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  return mla_sparse_kv8_run(false, Qc, Qpe, CKVpool8, KPEpool, O, lse, slots, ckv_scale, T, H, topk, num_slots, Dc, Dr, sm_scale, flags, workspace,
+                            workspace_bytes, stream);
+}
+
+int lc_attn_mla_sparse_kv8_bf16(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse, const int* slots,
+                                const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr, float sm_scale, int flags,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  return mla_sparse_kv8_run(true, Qc, Qpe, CKVpool8, KPEpool, O, lse, slots, ckv_scale, T, H, topk, num_slots, Dc, Dr, sm_scale, flags, workspace,
+                            workspace_bytes, stream);
+}
+
+int lc_attn_mla_sparse_kv8_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaSparsePlan p;
+  if (int rc = check_attn_mla_sparse(MlaSparseCall{T, H, topk, 1, Dc, Dr, flags, 1.f, bf16 != 0, true}, nullptr, &p)) return rc;
   format_attn_mla_sparse(p, buf, buflen);
   return LC_OK;
 }

@@ -304,6 +304,7 @@ struct MlaSparseCall {
   int T, H, topk, num_slots, Dc, Dr, flags;   // (the query calls state num_slots = 1: it decides nothing)
   float sm_scale;                             // the caller's softmax scale (the query calls: 1)
   bool bf16;                                  // Q, O and the pools are bfloat16: picks the kernels (and their names) and nothing else
+  bool kv8 = false;                           // the latent pool is e4m3fn bytes (§4.3v): attn_mla_sparse_kv8_kernel<BF16>; the plan is the 16-bit call's
 };
 struct MlaSparsePtrs {
   const half_t *Qc, *Qpe;                     // [T,H,Dc], [T,H,Dr] (16-bit lanes: fp16 or, MlaSparseCall::bf16, bfloat16)
@@ -312,6 +313,7 @@ struct MlaSparsePtrs {
   float* lse;                                 // device float[T H] or nullptr = none
   const int* slots;                           // device int32 [T, topk]
   hipStream_t st;
+  const float* ckv_scale = nullptr;           // MlaSparseCall::kv8: device float[1] read by the kernel only, or nullptr = 1.0
 };
 struct MlaSparsePlan {
   MlaSparseCall call;   // what was planned
@@ -319,12 +321,13 @@ struct MlaSparsePlan {
 };
 // The checks in check_attn_mla's order, then the plan.  a: the run call's pointers (nullptr: a query call)
 int check_attn_mla_sparse(const MlaSparseCall& c, const MlaSparsePtrs* a, MlaSparsePlan* p);   // tu_plan.hip
-void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen);   // "attn_mla_sparse_kernel", "attn_mla_sparse_bf16_kernel + attn_mla_sparse_combine_bf16_kernel x3"
+void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen);   // "attn_mla_sparse_kernel", "attn_mla_sparse_kv8_bf16_kernel + attn_mla_sparse_combine_bf16_kernel x3"
 // bytes of fp32 partials a plan with S > 1 needs: S x T H x (Dc + 1) floats; 0 for S = 1
 inline size_t mla_sparse_workspace_bytes(const MlaSparsePlan& p) {
   return p.S > 1 ? (size_t)p.S * (size_t)p.call.T * p.call.H * (size_t)(p.call.Dc + 1) * sizeof(float) : 0;
 }
 int launch_attn_mla_sparse(const MlaSparsePlan& p, const MlaSparsePtrs& a, void* workspace);   // tu_attn_mla_sparse.hip; checked arguments
+int launch_attn_mla_sparse_kv8(const MlaSparsePlan& p, const MlaSparsePtrs& a, void* workspace);   // tu_attn_mla_sparse_kv8.hip; checked arguments, MlaSparseCall::kv8
 
 // What a caller of a lightning-indexer entry states (lc_mla_index_logits_f16 / _bf16, lc_mla_index_topk and their name calls):
 // the ragged batch of MlaCall over an index-key pool [num_pages, page_size, Di] (the paged layout at Hkv = 1), Hi index heads, fp32 logits

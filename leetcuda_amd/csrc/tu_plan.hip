@@ -838,6 +838,7 @@ void format_attn_mla(const MlaPlan& p, char* buf, int buflen) {
 int check_attn_mla_sparse(const MlaSparseCall& c, const MlaSparsePtrs* a, MlaSparsePlan* p) {
   if (c.flags != 0) return LC_ERR_ARG;   // (no causal flag: the indexer selected visible keys)
   if (a && (!a->Qc || !a->Qpe || !a->CKV || !a->KPE || !a->O || !a->slots)) return LC_ERR_ARG;   // (lse: NULL = none)
+  if (a && ((uintptr_t)a->ckv_scale & 3) != 0) return LC_ERR_ARG;   // (kv8; NULL = 1.0)
   // (decided on the bit pattern: this unit is compiled with -fno-honor-nans.)  Finite and > 0: exponent not all ones, sign clear, not zero
   const uint32_t sb = __builtin_bit_cast(uint32_t, c.sm_scale);
   if ((sb & 0x7f800000u) == 0x7f800000u || (sb >> 31) != 0 || sb == 0) return LC_ERR_ARG;
@@ -858,9 +859,9 @@ int check_attn_mla_sparse(const MlaSparseCall& c, const MlaSparsePtrs* a, MlaSpa
   return LC_OK;
 }
 void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen) {
-  const char* bf = p.call.bf16 ? "bf16_" : "";
-  if (p.S > 1) snprintf(buf, buflen, "attn_mla_sparse_%skernel + attn_mla_sparse_combine_%skernel x%d", bf, bf, p.S);
-  else snprintf(buf, buflen, "attn_mla_sparse_%skernel", bf);
+  const char *bf = p.call.bf16 ? "bf16_" : "", *k8 = p.call.kv8 ? "kv8_" : "";
+  if (p.S > 1) snprintf(buf, buflen, "attn_mla_sparse_%s%skernel + attn_mla_sparse_combine_%skernel x%d", k8, bf, bf, p.S);
+  else snprintf(buf, buflen, "attn_mla_sparse_%s%skernel", k8, bf);
 }
 
 // The lightning indexer (lc_plan.h MlaIndexCall).  Both entries: flags and NULL pointers, then the shape — dims, max_nq, the

@@ -81,6 +81,8 @@ OWNED_AGPRS = [
     (re.compile(r"mla_append_paged_(kv8_)?(bf16_)?kernel"), []),
     # ... and the sparse latent attention kernels (attn_mla_sparse.hip: builtins only; its one asm statement is empty)
     (re.compile(r"attn_mla_sparse_kernel|attn_mla_sparse_combine_kernel"), []),
+    # ... and the one over an fp8 latent pool (attn_mla_sparse_kv8.hip: the same)
+    (re.compile(r"attn_mla_sparse_kv8_kernel"), []),
     # ... and the lightning-indexer kernels (mla_index_logits.hip, mla_index_topk.hip: builtins only)
     (re.compile(r"mla_index_logits_kernel|mla_index_topk_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
