@@ -890,7 +890,7 @@ int lc_attn_mla_sparse_kernel_name(int T, int H, int topk, int Dc, int Dr, int f
  * long as code x scale is a normal number of the element type).  Codes 0x7f / 0xff are NaN; those of an invalid entry reach no product.
  * lc_attn_mla_sparse_workspace_bytes serves both element widths (the plan — RB, S, the grid — is the 16-bit call's).  The name query:
  * "attn_mla_sparse_kv8_kernel" / "attn_mla_sparse_kv8_bf16_kernel", S > 1: "... + attn_mla_sparse_combine_[bf16_]kernel xS".
- * Not here: an fp8 rope pool, per-row or per-128-column scales (FlashMLA's 656-byte rows), fp8 index keys for the indexer. */
+ * Not here: an fp8 rope pool, per-row or per-128-column scales (FlashMLA's 656-byte rows). */
 int lc_attn_mla_sparse_kv8(const void* Qc, const void* Qpe, const void* CKVpool8, const void* KPEpool, void* O, float* lse,
                            const int* slots, const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr,
                            float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
@@ -931,9 +931,9 @@ int lc_attn_mla_sparse_kv8_kernel_name(int T, int H, int topk, int Dc, int Dr, i
  * Status: a flag, a NULL pointer: LC_ERR_ARG; a non-positive dim (topk included), max_nq > T, the page size, the pool and ld as above,
  * T topk > 2^31 - 1, a pointer off 4 bytes: LC_ERR_SHAPE.  mla_index_topk_kernel, one workgroup of 1024 threads a row: a three-pass radix
  * select (11, 11, 10 bits) and one ordered compaction pass; lc_mla_index_topk_kernel_name: "mla_index_topk_kernel" and the run call's status.
- * Not here: fp8 index keys and queries with per-token scales, writing the index-key pool (lc_rope_append_varlen_* at Hkv = 1, D = 128 writes
- * this layout; see DESIGN), logits and selection fused so that [T, L] never reaches memory, other (Hi, Di), per-token topk, a row spread
- * over several workgroups. */
+ * Not here: writing the 16-bit index-key pool (lc_rope_append_varlen_* at Hkv = 1, D = 128 writes this layout; see DESIGN), logits and
+ * selection fused so that [T, L] never reaches memory, other (Hi, Di), per-token topk, a row spread over several workgroups.  (fp8 index
+ * keys and queries with per-token scales: lc_mla_index_logits_fp8 and lc_mla_index_append_fp8_* below.) */
 int lc_mla_index_logits_f16(const void* Qi, const float* w, const void* Kipool, float* logits,
                             const int* cu_q, const int* block_table, const int* kv_len,
                             int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages,
@@ -950,6 +950,56 @@ int lc_mla_index_topk(const float* logits, int* slots,
                       long long ld, int topk, int flags, void* stream);
 int lc_mla_index_topk_kernel_name(int B, int T, int max_nq, int num_pages, int page_size, int max_pages, long long ld, int topk, int flags,
                                   char* buf, int buflen);
+
+/* EXTENSION: the lightning indexer over an fp8 (OCP e4m3fn) index-key pool with per-row scales (mla_index_logits_fp8.hip,
+ * mla_index_append_fp8.hip): DeepSeek-V3.2's shipped format.  [lc_mla_index_append_fp8_* -> lc_mla_index_logits_fp8 ->
+ * lc_mla_index_topk -> lc_attn_mla_sparse_*] is one captured graph (no workspace, nothing allocated).
+ *
+ * lc_mla_index_logits_fp8: lc_mla_index_logits_f16, argument for argument and rule for rule (the ragged batch, visible keys, exactly the
+ * columns [0, n_t) written, clamped page ids and source rows, ld), with
+ *   Q8           [T, 64, 128] e4m3fn BYTES, 16-byte aligned
+ *   Kipool8      [num_pages, page_size, 128] e4m3fn BYTES, 16-byte aligned
+ *   Kiscale      device float32 [num_pages, page_size], 4-byte aligned, right behind the pool: the scale of every key row, in a pool of its
+ *                own (a packed 132-byte row would cost key rows their 16-byte alignment)
+ *   w            device float32 [T, 64]: the caller folds the per-(token, head) QUERY scale, the softmax scale and Hi^-1/2 into it
+ * and, with s = slot(b, j),
+ *     logits[t, j] = Kiscale[s] x sum_{h < 64} w[t, h] x max(0, sum_{d < 128} Q8[t, h, d] x Kipool8[s, d])
+ * computed in THIS order: the 128 products of the unscaled code values summed to fp32 by the matrix instruction, max(., 0) on that sum, ONE
+ * fp32 multiply by w[t, h] accumulated over the heads in fp32, then ONE fp32 multiply by Kiscale[s].  Codes 0x7f / 0xff are NaN.  Neither
+ * operand has a 16-bit form: one symbol, no _f16 / _bf16 pair.
+ * Status, in lc_mla_index_logits_f16's order: an unknown flag, a NULL pointer (Kiscale included): LC_ERR_ARG; the shape faults of that entry,
+ * with the grid bound on the kernel's token block (B ceil(max_nq / TB) 64 > 2^31 - 1, TB = 8 for max_nq <= 8, else 16), Q8 or Kipool8 off 16
+ * bytes, w, Kiscale, logits or an int array off 4 bytes: LC_ERR_SHAPE; (Hi, Di) != (64, 128): LC_ERR_HEADDIM.
+ * mla_index_logits_fp8_kernel<TPW> (TPW = TB / 4 tokens a wave) on B x ceil(max_nq / TB) x S workgroups over 128-key tiles.
+ * lc_mla_index_logits_fp8_kernel_name never launches: "mla_index_logits_fp8_kernel" and the run call's status.
+ *
+ * lc_mla_index_append_fp8_f16 / _bf16: the write side.  Kinew [T, 128] 16-bit rows (fp16, _bf16: bfloat16; behind the caller's norm, RoPE and
+ * Hadamard), row_stride elements apart (even, >= 128; 4-byte aligned), are quantised per row and scattered to Kipool8 and Kiscale at
+ * lc_mla_append_paged_*'s position p = L_b - Nq_b + i under its clamps; p < 0, a page id outside [0, num_pages) and a token no sequence owns
+ * write nothing.  Per row, in fp32: amax = max(max_d |x_d|, 1e-4) (a NaN element does not enter it); s = amax / 448, the correctly rounded
+ * division; pow2 != 0: s = 2^ceil(log2 s) exactly (ue8m0); code_d = e4m3fn(x_d / s), the correctly rounded quotient clamped to +-448 and
+ * rounded to nearest even, a NaN element or quotient giving 0x7f (lc_kv_append_paged_kv8's rule); Kiscale[slot] = s.
+ * Status: a NULL pointer: LC_ERR_ARG; a non-positive dim, max_nq > T, the page size and the pool as above, row_stride < Di or odd, Kipool8
+ * off 16 bytes, another pointer off 4: LC_ERR_SHAPE; Di != 128: LC_ERR_HEADDIM.  mla_index_append_fp8_kernel<BF16>, a wave a row, on
+ * ceil(T / 4) workgroups; lc_mla_index_append_fp8_kernel_name: "mla_index_append_fp8_kernel" / "mla_index_append_fp8_bf16_kernel".
+ * Not here: a kernel that quantises Q (a few torch ops on [T, 64, 128]), logits fused with the selection, scales through the matrix
+ * instruction's E8M0 operands, the packed 132-byte row. */
+int lc_mla_index_logits_fp8(const void* Q8, const float* w, const void* Kipool8, const float* Kiscale, float* logits,
+                            const int* cu_q, const int* block_table, const int* kv_len,
+                            int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                            int Di, long long ld, int flags, void* stream);
+int lc_mla_index_logits_fp8_kernel_name(int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld,
+                                        int flags, char* buf, int buflen);
+int lc_mla_index_append_fp8_f16(const void* Kinew, void* Kipool8, float* Kiscale,
+                                const int* cu_q, const int* block_table, const int* kv_len,
+                                int B, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                                int Di, long long row_stride, int pow2, void* stream);
+int lc_mla_index_append_fp8_bf16(const void* Kinew, void* Kipool8, float* Kiscale,
+                                 const int* cu_q, const int* block_table, const int* kv_len,
+                                 int B, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                                 int Di, long long row_stride, int pow2, void* stream);
+int lc_mla_index_append_fp8_kernel_name(int B, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long row_stride,
+                                        int pow2, int bf16, char* buf, int buflen);
 
 /* EXTENSION: RMSNorm + rotary embedding + append for the paged LATENT cache (mla_append_paged.hip): the write side of
  * lc_attn_mla_paged_*.  ONE launch takes a step's projection outputs as they sit in memory and leaves what the attention entries read: the

@@ -162,6 +162,13 @@ SYMBOLS = {
     "lc_mla_index_logits_kernel_name": (_i, [_i] * 8 + [C.c_longlong, _i, _i, _cp, _i]),
     "lc_mla_index_topk": (_i, [_vp] * 5 + [_i] * 6 + [C.c_longlong, _i, _i, _vp]),
     "lc_mla_index_topk_kernel_name": (_i, [_i] * 6 + [C.c_longlong, _i, _i, _cp, _i]),
+    # ... over an fp8 index-key pool: Q8, w, Kipool8, Kiscale, logits, cu_q, block_table, kv_len, then as above; the append: Kinew, Kipool8,
+    # Kiscale, cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages, Di, row_stride, pow2, stream
+    "lc_mla_index_logits_fp8": (_i, [_vp] * 8 + [_i] * 8 + [C.c_longlong, _i, _vp]),
+    "lc_mla_index_logits_fp8_kernel_name": (_i, [_i] * 8 + [C.c_longlong, _i, _cp, _i]),
+    "lc_mla_index_append_fp8_f16": (_i, [_vp] * 6 + [_i] * 7 + [C.c_longlong, _i, _vp]),
+    "lc_mla_index_append_fp8_bf16": (_i, [_vp] * 6 + [_i] * 7 + [C.c_longlong, _i, _vp]),
+    "lc_mla_index_append_fp8_kernel_name": (_i, [_i] * 7 + [C.c_longlong, _i, _i, _cp, _i]),
     # RMSNorm + rope + append to the latent cache: CKVnew, KPEnew, Qpe, Qpe_out, CKVpool, KPEpool, gamma (or NULL), cos_sin, cu_q, block_table,
     # kv_len, [ckv_scale (or NULL),] B, H, T, max_nq, num_pages, page_size, max_pages, Dc, Dr, max_pos, eps, the four strides, flags, stream
     "lc_mla_append_paged_f16": (_i, [_vp] * 11 + [_i] * 10 + [C.c_float] + [C.c_longlong] * 4 + [_i, _vp]),
@@ -1801,6 +1808,94 @@ def mla_index_topk_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, to
     buf = C.create_string_buffer(128)
     check(load().lc_mla_index_topk_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, max_pages * page_size if ld is None else ld, topk,
                                                ATTN_CAUSAL if causal else 0, buf, 128), "lc_mla_index_topk_kernel_name")
+    return buf.value.decode()
+
+
+# ... over an fp8 (e4m3) index-key pool with per-row scales (lc_mla_index_logits_fp8, lc_mla_index_append_fp8_f16 / _bf16)
+
+def _mla_index_fp8_pool(ki_pool_u8, ki_scale):
+    import torch
+    if ki_pool_u8.dtype != torch.uint8 or ki_scale.dtype != torch.float32:
+        raise TypeError(f"ki_pool_u8 must be uint8 and ki_scale float32, got {ki_pool_u8.dtype} / {ki_scale.dtype}")
+    if ki_pool_u8.dim() != 3 or tuple(ki_scale.shape) != tuple(ki_pool_u8.shape[:2]):
+        _shape_err(f"ki_pool_u8 {tuple(ki_pool_u8.shape)} ki_scale {tuple(ki_scale.shape)}: [num_pages,page_size,Di] / [num_pages,page_size] expected")
+    return ki_pool_u8.shape
+
+
+def mla_index_logits_fp8(q8, w, ki_pool_u8, ki_scale, logits, cu_q, block_table, kv_len, max_nq, causal=True):
+    """mla_index_logits over the fp8 format (lc_mla_index_logits_fp8): q8 [T,64,128] and ki_pool_u8 [num_pages,page_size,128] torch.uint8 holding
+    e4m3fn codes, ki_scale float32 [num_pages,page_size] (the pool mla_index_append_fp8 writes), w float32 [T,64] with the per-(token, head)
+    query scale folded in.  Writes logits[t, j] = ki_scale[s] x sum_h w[t, h] relu(q8[t, h] . k8[s]), s = slot(b, j), for the visible j < n_t
+    only; every other argument and the result: mla_index_logits."""
+    import torch
+    if q8.dtype != torch.uint8:
+        raise TypeError(f"q8 must be uint8 (e4m3fn codes), got {q8.dtype}")
+    if w.dtype != torch.float32:
+        raise TypeError(f"w must be float32, got {w.dtype}")
+    num_pages, page_size, Di = _mla_index_fp8_pool(ki_pool_u8, ki_scale)
+    if q8.dim() != 3 or w.dim() != 2:
+        _shape_err("q8 [T,Hi,Di] / w [T,Hi] expected")
+    T, Hi = q8.shape[:2]
+    if q8.shape[2] != Di or tuple(w.shape) != (T, Hi):
+        _shape_err(f"q8 {tuple(q8.shape)} ki_pool_u8 {tuple(ki_pool_u8.shape)} w {tuple(w.shape)}")
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    ld = _mla_index_logits_buf(logits, T, block_table, page_size)
+    _need_gpu(q8, w, ki_pool_u8, ki_scale, cu_q, block_table, kv_len)
+    if not logits.is_cuda:
+        raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    check(load().lc_mla_index_logits_fp8(_ptr(q8), _ptr(w), _ptr(ki_pool_u8), _ptr(ki_scale), _ptr(logits), _ptr(cu_q), _ptr(block_table),
+                                         _ptr(kv_len), B, Hi, T, max_nq, num_pages, page_size, block_table.shape[1], Di, ld,
+                                         ATTN_CAUSAL if causal else 0, _stream()), "lc_mla_index_logits_fp8")
+    return logits
+
+
+def mla_index_append_fp8(ki_new, ki_pool_u8, ki_scale, cu_q, block_table, kv_len, max_nq, pow2=True):
+    """Quantise and append a step's index keys (lc_mla_index_append_fp8_f16 / _bf16, picked by ki_new's dtype): ki_new [T,128] float16 or
+    bfloat16 with dense rows (a view with a row stride serves), into ki_pool_u8 / ki_scale at position kv_len[b] - Nq_b + i of each token's
+    sequence.  Per row s = max(amax, 1e-4) / 448, with pow2 rounded up to a power of two; code = e4m3fn(x / s).  Returns ki_pool_u8."""
+    import torch
+    if ki_new.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"ki_new must be float16 or bfloat16, got {ki_new.dtype}")
+    num_pages, page_size, Di = _mla_index_fp8_pool(ki_pool_u8, ki_scale)
+    if ki_new.dim() != 2 or ki_new.shape[1] != Di or ki_new.stride(1) != 1:
+        _shape_err(f"ki_new {tuple(ki_new.shape)} strides {ki_new.stride()}: [T, {Di}] with dense rows expected")
+    T = ki_new.shape[0]
+    B = _varlen_batch(cu_q, block_table, kv_len)
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > T:
+        raise ValueError(f"max_nq must be an int in [1, T = {T}], got {max_nq!r}")
+    _need_gpu(ki_pool_u8, ki_scale, cu_q, block_table, kv_len)
+    if not ki_new.is_cuda:
+        raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    symbol = "lc_mla_index_append_fp8_bf16" if ki_new.dtype == torch.bfloat16 else "lc_mla_index_append_fp8_f16"
+    check(getattr(load(), symbol)(_ptr(ki_new), _ptr(ki_pool_u8), _ptr(ki_scale), _ptr(cu_q), _ptr(block_table), _ptr(kv_len), B, T, max_nq,
+                                  num_pages, page_size, block_table.shape[1], Di, ki_new.stride(0) if T > 1 else Di, int(bool(pow2)), _stream()),
+          symbol)
+    return ki_pool_u8
+
+
+def mla_index_select_fp8(q8, w, ki_pool_u8, ki_scale, logits, slots, cu_q, block_table, kv_len, max_nq, causal=True):
+    """mla_index_select over the fp8 format: mla_index_logits_fp8 into `logits`, then the unchanged mla_index_topk into `slots`, which is
+    returned.  Nothing is allocated: legal under graph capture."""
+    mla_index_logits_fp8(q8, w, ki_pool_u8, ki_scale, logits, cu_q, block_table, kv_len, max_nq, causal=causal)
+    return mla_index_topk(logits, slots, cu_q, block_table, kv_len, max_nq, causal=causal, page_size=ki_pool_u8.shape[1],
+                          num_pages=ki_pool_u8.shape[0])
+
+
+def mla_index_logits_fp8_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, ld=None, Hi=64, Di=128, causal=True) -> str:
+    """"mla_index_logits_fp8_kernel" (ld: max_pages x page_size unless given)"""
+    buf = C.create_string_buffer(128)
+    check(load().lc_mla_index_logits_fp8_kernel_name(B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, max_pages * page_size if ld is None else ld,
+                                                     ATTN_CAUSAL if causal else 0, buf, 128), "lc_mla_index_logits_fp8_kernel_name")
+    return buf.value.decode()
+
+
+def mla_index_append_fp8_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, row_stride=128, Di=128, pow2=True, bf16=False) -> str:
+    """"mla_index_append_fp8_kernel" / "mla_index_append_fp8_bf16_kernel" """
+    buf = C.create_string_buffer(128)
+    check(load().lc_mla_index_append_fp8_kernel_name(B, T, max_nq, num_pages, page_size, max_pages, Di, row_stride, int(bool(pow2)), int(bf16), buf,
+                                                     128), "lc_mla_index_append_fp8_kernel_name")
     return buf.value.decode()
 
 

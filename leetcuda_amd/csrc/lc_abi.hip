@@ -923,6 +923,61 @@ int lc_mla_index_topk_kernel_name(int B, int T, int max_nq, int num_pages, int p
   return LC_OK;
 }
 
+// The fp8 lightning indexer (mla_index_logits_fp8.hip, mla_index_append_fp8.hip): the MlaIndexCall with fp8 set and the
+// scales behind the pool, check_mla_index_logits (tu_plan.hip), launch_mla_index_logits_fp8 (tu_mla_index_fp8.hip); an MlaIndexAppendCall
+int lc_mla_index_logits_fp8(const void* Q8, const float* w, const void* Kipool8, const float* Kiscale, float* logits, const int* cu_q,
+                            const int* block_table, const int* kv_len, int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages,
+                            int Di, long long ld, int flags, void* stream) {
+  const MlaIndexCall c{B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, 1, flags, false, true};
+  const MlaIndexPtrs a{static_cast<const half_t*>(Q8), w, static_cast<const half_t*>(Kipool8), logits, nullptr, cu_q, block_table, kv_len,
+                       static_cast<hipStream_t>(stream), Kiscale};
+  MlaIndexPlan p;
+  if (int rc = check_mla_index_logits(c, &a, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_mla_index_logits_fp8(p, a);
+}
+
+int lc_mla_index_logits_fp8_kernel_name(int B, int Hi, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long ld, int flags,
+                                        char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaIndexPlan p;
+  if (int rc = check_mla_index_logits(MlaIndexCall{B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, 1, flags, false, true}, nullptr, &p)) return rc;
+  snprintf(buf, buflen, "mla_index_logits_fp8_kernel");
+  return LC_OK;
+}
+
+static int mla_index_append_fp8_run(bool bf16, const void* Kinew, void* Kipool8, float* Kiscale, const int* cu_q, const int* block_table,
+                                    const int* kv_len, int B, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di,
+                                    long long row_stride, int pow2, void* stream) {
+  const MlaIndexAppendCall c{B, T, max_nq, num_pages, page_size, max_pages, Di, row_stride, pow2, bf16};
+  const MlaIndexAppendPtrs a{static_cast<const half_t*>(Kinew), static_cast<uint8_t*>(Kipool8), Kiscale, cu_q, block_table, kv_len,
+                             static_cast<hipStream_t>(stream)};
+  if (int rc = check_mla_index_append_fp8(c, &a)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_mla_index_append_fp8(c, a);
+}
+
+int lc_mla_index_append_fp8_f16(const void* Kinew, void* Kipool8, float* Kiscale, const int* cu_q, const int* block_table, const int* kv_len, int B,
+                                int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long row_stride, int pow2, void* stream) {
+  return mla_index_append_fp8_run(false, Kinew, Kipool8, Kiscale, cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages, Di,
+                                  row_stride, pow2, stream);
+}
+
+int lc_mla_index_append_fp8_bf16(const void* Kinew, void* Kipool8, float* Kiscale, const int* cu_q, const int* block_table, const int* kv_len, int B,
+                                 int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long row_stride, int pow2, void* stream) {
+  return mla_index_append_fp8_run(true, Kinew, Kipool8, Kiscale, cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages, Di,
+                                  row_stride, pow2, stream);
+}
+
+int lc_mla_index_append_fp8_kernel_name(int B, int T, int max_nq, int num_pages, int page_size, int max_pages, int Di, long long row_stride, int pow2,
+                                        int bf16, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  if (int rc = check_mla_index_append_fp8(MlaIndexAppendCall{B, T, max_nq, num_pages, page_size, max_pages, Di, row_stride, pow2, bf16 != 0}, nullptr))
+    return rc;
+  snprintf(buf, buflen, "mla_index_append_fp8_%skernel", bf16 ? "bf16_" : "");
+  return LC_OK;
+}
+
 // RMSNorm + rotary embedding + append to the paged latent cache (mla_append_paged.hip): mla_append_run above
 int lc_mla_append_paged_f16(const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool, const float* gamma,
                             const float* cos_sin, const int* cu_q, const int* block_table, const int* kv_len, int B, int H, int T, int max_nq,

@@ -340,6 +340,7 @@ struct MlaIndexCall {
   long long ld;                                                // floats between two rows of logits
   int topk, flags;                                             // (the logits entries state topk = 1)
   bool bf16;                                                   // Qi and the pool are bfloat16: picks the logits kernel (and its name)
+  bool fp8 = false;                                            // Qi and the pool are e4m3fn bytes, MlaIndexPtrs::ks their row scales (§4.3w)
 };
 struct MlaIndexPtrs {
   const half_t* Qi;                          // [T,Hi,Di] (16-bit lanes); the top-k entry: unused
@@ -349,16 +350,40 @@ struct MlaIndexPtrs {
   int* slots;                                // device int32 [T,topk]: the top-k entry only
   const int *cu_q, *block_table, *kv_len;    // device int32 [B + 1], [B,max_pages], [B]
   hipStream_t st;
+  const float* ks = nullptr;                 // MlaIndexCall::fp8: device float [num_pages, page_size], the scale of every key row
 };
 struct MlaIndexPlan {
   MlaIndexCall call;   // what was planned
   int NB, S;
+  int TB = 8;          // query tokens per workgroup (fp8: 8 or 16, see mla_index_fp8_token_block)
 };
+// The fp8 logits kernel's token block (mla_index_logits_fp8.hip): a wave owns 2 tokens while no block can hold more than 8, else 4.  Host
+// quantities only.  Its 128-key tiles replace the 64-key ones in the S rule above.
+inline int mla_index_fp8_token_block(int max_nq) { return max_nq <= 8 ? 8 : 16; }
 // The checks in check_attn_mla's order, then the plan.  a: the run call's pointers (nullptr: a name call)
 int check_mla_index_logits(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p);   // tu_plan.hip
 int check_mla_index_topk(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p);     // tu_plan.hip
 int launch_mla_index_logits(const MlaIndexPlan& p, const MlaIndexPtrs& a);   // tu_mla_index.hip; checked arguments
 int launch_mla_index_topk(const MlaIndexPlan& p, const MlaIndexPtrs& a);     // tu_mla_index.hip; checked arguments
+int launch_mla_index_logits_fp8(const MlaIndexPlan& p, const MlaIndexPtrs& a);   // tu_mla_index_fp8.hip; checked arguments, MlaIndexCall::fp8
+
+// What a caller of the fp8 index-key append states (lc_mla_index_append_fp8_f16 / _bf16 and their name call): the write side
+// of the pool MlaIndexCall::fp8 reads, on the same ragged batch.  Nothing to plan: mla_index_append_fp8_kernel<BF16> on ceil(T / 4) workgroups.
+struct MlaIndexAppendCall {
+  int B, T, max_nq, num_pages, page_size, max_pages, Di;
+  long long row_stride;                      // elements between two rows of Kinew
+  int pow2;                                  // != 0: scales rounded up to a power of two
+  bool bf16;                                 // Kinew is bfloat16
+};
+struct MlaIndexAppendPtrs {
+  const half_t* Kinew;                       // [T,Di] 16-bit rows
+  uint8_t* K8;                               // [num_pages, page_size, Di] e4m3fn bytes
+  float* ks;                                 // [num_pages, page_size]
+  const int *cu_q, *block_table, *kv_len;
+  hipStream_t st;
+};
+int check_mla_index_append_fp8(const MlaIndexAppendCall& c, const MlaIndexAppendPtrs* a);   // tu_plan.hip; a = nullptr: the name call
+int launch_mla_index_append_fp8(const MlaIndexAppendCall& c, const MlaIndexAppendPtrs& a);  // tu_mla_index_fp8.hip; checked arguments
 
 // What a caller of a latent-cache append entry states (lc_mla_append_paged_f16 / _bf16 / _kv8 / _kv8_bf16 and their name call):
 // the write side of the cache MlaCall reads — RMSNorm of the latent row, rotation of k_pe and of the H q_pe rows, the append through the block

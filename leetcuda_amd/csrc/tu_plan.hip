@@ -881,16 +881,33 @@ bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 int check_mla_index_logits(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p) {
   if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
   if (a && (!a->Qi || !a->w || !a->Ki || !a->logits || !a->cu_q || !a->block_table || !a->kv_len)) return LC_ERR_ARG;
+  if (a && c.fp8 && !a->ks) return LC_ERR_ARG;
   if (int rc = check_mla_index_shape(c)) return rc;
-  const long NB = ((long)c.max_nq + 7) / 8;
+  const int TB = c.fp8 ? mla_index_fp8_token_block(c.max_nq) : 8, KT = c.fp8 ? 128 : 64;   // the kernel's token block and key tile
+  const long NB = ((long)c.max_nq + TB - 1) / TB;
   if ((size_t)c.B * (size_t)NB * 64 > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of B x NB x S workgroups, S <= 64
   if (a && (!aligned16(a->Qi) || !aligned16(a->Ki) || !aligned4(a->w) || !aligned4(a->logits) || !aligned4(a->cu_q) || !aligned4(a->block_table) ||
-            !aligned4(a->kv_len)))
+            !aligned4(a->kv_len) || !aligned4(a->ks)))
     return LC_ERR_SHAPE;
   if (c.Hi != 64 || c.Di != 128) return LC_ERR_HEADDIM;
-  const long groups = (long)c.B * NB, tiles = ((long)c.max_pages * c.page_size + 63) / 64;
+  const long groups = (long)c.B * NB, tiles = ((long)c.max_pages * c.page_size + KT - 1) / KT;
   const long S = std::max(1L, std::min({(4L * rule_cus(read_knobs()) + groups - 1) / groups, tiles / 4, 64L}));
-  *p = MlaIndexPlan{c, (int)NB, (int)S};
+  *p = MlaIndexPlan{c, (int)NB, (int)S, TB};
+  return LC_OK;
+}
+// The fp8 index-key append (lc_plan.h MlaIndexAppendCall): NULL pointers, then the shape in check_mla_index_shape's order,
+// the row stride (even: a lane loads a dword; at least Di), alignment — the pool 16 bytes, as the logits entry wants it, Kinew, the scales and
+// the int arrays 4 —, then the head dim.
+int check_mla_index_append_fp8(const MlaIndexAppendCall& c, const MlaIndexAppendPtrs* a) {
+  if (a && (!a->Kinew || !a->K8 || !a->ks || !a->cu_q || !a->block_table || !a->kv_len)) return LC_ERR_ARG;
+  const long ncap = (long)c.max_pages * c.page_size;
+  if (int rc = check_mla_index_shape(MlaIndexCall{c.B, 64, c.T, c.max_nq, c.num_pages, c.page_size, c.max_pages, c.Di, (ncap + 3) & ~3L, 1, 0, c.bf16}))
+    return rc;
+  if (c.row_stride < c.Di || (c.row_stride & 1) != 0) return LC_ERR_SHAPE;
+  if ((long)c.T + 3 > 0x7fffffffL) return LC_ERR_SHAPE;   // tokens are counted in 32 bits by the grid of ceil(T / 4) workgroups
+  if (a && (!aligned16(a->K8) || !aligned4(a->Kinew) || !aligned4(a->ks) || !aligned4(a->cu_q) || !aligned4(a->block_table) || !aligned4(a->kv_len)))
+    return LC_ERR_SHAPE;
+  if (c.Di != 128) return LC_ERR_HEADDIM;
   return LC_OK;
 }
 int check_mla_index_topk(const MlaIndexCall& c, const MlaIndexPtrs* a, MlaIndexPlan* p) {

@@ -85,6 +85,8 @@ OWNED_AGPRS = [
     (re.compile(r"attn_mla_sparse_kv8_kernel"), []),
     # ... and the lightning-indexer kernels (mla_index_logits.hip, mla_index_topk.hip: builtins only)
     (re.compile(r"mla_index_logits_kernel|mla_index_topk_kernel"), []),
+    # ... and the ones over an fp8 index-key pool (mla_index_logits_fp8.hip, mla_index_append_fp8.hip: builtins only)
+    (re.compile(r"mla_index_logits_fp8_kernel|mla_index_append_fp8_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
 ]
 
