@@ -800,8 +800,8 @@ int lc_attn_merge_states_bf16(const void* Oa, const float* lse_a, const void* Ob
  * captured stream or a failed lease runs S = 1 — and attn_mla_combine_kernel<BF16>.  lc_attn_mla_paged_workspace_bytes: those bytes (0: S = 1
  * or a refused shape); lc_attn_mla_paged_kernel_name: "attn_mla_paged_kernel" / "attn_mla_paged_bf16_kernel", S > 1:
  * "... + attn_mla_combine_kernel xS"; it returns the status the run call would give.
- * Writing the latent cache: lc_mla_append_paged_* below.  Not here: windows / sinks / tree masks, page_size < 16, other (Dc, Dr), the non-absorbed prefill form (plain
- * attention at D = 192 / 128: lc_attn_fwd_*), lc_attn_merge_states at D = 512.  (An fp8 latent cache: lc_attn_mla_paged_kv8 below; per-token
+ * Writing the latent cache: lc_mla_append_paged_* below.  Not here: windows / sinks / tree masks, page_size < 16, other (Dc, Dr), lc_attn_merge_states at D = 512.  (The
+ * non-absorbed prefill form — plain attention at D = 192 / 128 over the expanded keys — : lc_attn_mla_prefill_* below.)  (An fp8 latent cache: lc_attn_mla_paged_kv8 below; per-token
  * selected cache entries — DeepSeek-V3.2's sparse attention — : lc_attn_mla_sparse_* below.) */
 int lc_attn_mla_paged_f16(const void* Qc, const void* Qpe, const void* CKVpool, const void* KPEpool, void* O, float* lse,
                           const int* cu_q, const int* block_table, const int* kv_len,
@@ -898,6 +898,44 @@ int lc_attn_mla_sparse_kv8_bf16(const void* Qc, const void* Qpe, const void* CKV
                                 const int* slots, const float* ckv_scale, int T, int H, int topk, int num_slots, int Dc, int Dr,
                                 float sm_scale, int flags, void* workspace, size_t workspace_bytes, void* stream);
 int lc_attn_mla_sparse_kv8_kernel_name(int T, int H, int topk, int Dc, int Dr, int flags, int bf16, char* buf, int buflen);
+
+/* EXTENSION: the NON-ABSORBED PREFILL form of multi-head latent attention (attn_mla_prefill.hip): what fills the latent
+ * cache for a prompt.  kv_b_proj has expanded the latent rows into per-head Knope and V; the rotated Kpe row is ONE row a token, read by every
+ * head and never expanded.  Plain attention with scores over Dn + Dr = 192 dims and values over Dv = 128, on a ragged batch: for sequence b the
+ * queries are tokens cu_q[b] .. cu_q[b+1] - 1 and the keys are rows cu_k[b] .. cu_k[b+1] - 1 (device int32 [B + 1] each, read and clamped by the
+ * kernel only — offsets into [0, Tq] / [0, Tk], Nq_b <= max_nq — so a captured graph replays on changed arrays).  Query i of b sits at
+ * position p = Lk_b - Nq_b + i (bottom-right); with LC_ATTN_CAUSAL it sees keys j <= p, without it all Lk_b keys:
+ *   s_j = sm_scale (sum_{d < 128} Q[t,h,d] Knope[j,h,d] + sum_{d < 64} Q[t,h,128 + d] Kpe[j,d]),   O[t,h,:] = sum_j softmax_j(s) V[j,h,:],
+ *   lse[t,h] = ln sum_j exp(s_j)   (natural units; -inf, and O = 0, for a row that sees no key: p < 0 or Lk_b = 0)
+ *   Q       [Tq,H,192] at t q_row_stride + h q_head_stride: e.g. the q_b_proj output after lc_mla_append_paged_* rotated its rope part in place
+ *   Knope   [Tk,H,128] at j kn_row_stride + h kn_head_stride: e.g. the kv_b_proj output [Tk,H,256] at offset 0 (head 256, row 256 H)
+ *   V       [Tk,H,128] at j v_row_stride + h v_head_stride: e.g. the same buffer at offset 128
+ *   Kpe     [Tk,64] at j kpe_row_stride
+ *   O, lse  [Tq,H,128] dense in the element type, and device float32 [Tq H] dense or NULL for none.  Rows no sequence owns are not written
+ * Elements are 16-bit (fp16, _bf16: bfloat16), pointers 16-byte aligned; strides are in elements, multiples of 8, a head stride at least the
+ * width it steps over and a row stride at least (H - 1) head + width; offsets are 64-bit.  The result never depends on key / value rows outside
+ * [cu_k[b], cu_k[b+1]) or on the elements between strided rows, NaN included (source rows are clamped, never zero-filled; a masked score is a
+ * select on the key index).  Products accumulate in fp32, sm_scale multiplies the fp32 scores, P is rounded to the element type for the value
+ * product while the row sum keeps the unrounded value, O is rounded once (nearest even).
+ * Status, in this order: an unknown flag (only LC_ATTN_CAUSAL is defined), a NULL pointer other than lse, sm_scale not finite or <= 0:
+ * LC_ERR_ARG; a non-positive dim, max_nq > Tq, Tq H > 2^31 - 1, the grid bound (ceil(max_nq / 128) B H > 2^31 - 1), a 16-bit pointer off 16
+ * bytes or lse / cu_q / cu_k off 4, a bad stride: LC_ERR_SHAPE; (Dn, Dr, Dv) != (128, 64, 128): LC_ERR_HEADDIM.
+ * attn_mla_prefill_kernel<BF16, RS> on ceil(max_nq / (64 RS)) x B x H workgroups of 64 RS query tokens of one head; RS = 1 for max_nq <= 64,
+ * else 2.  No workspace and no split over the keys: every call is legal under graph capture.  With the lse, chunked prefill is two calls — the
+ * chunk over the expanded cached context (no flag) and over its own keys (LC_ATTN_CAUSAL) — merged by lc_attn_merge_states_* (D = 128).
+ * lc_attn_mla_prefill_kernel_name never launches: "attn_mla_prefill_kernel<RS>" / "attn_mla_prefill_bf16_kernel<RS>", and the run call's status
+ * (it sees no pointer and no stride).  Not here: other head dims, windows / sinks, an fp8 K / V, the backward pass. */
+int lc_attn_mla_prefill_f16(const void* Q, const void* Knope, const void* Kpe, const void* V, void* O, float* lse,
+                            const int* cu_q, const int* cu_k, int B, int H, int Tq, int Tk, int max_nq,
+                            int Dn, int Dr, int Dv, float sm_scale, int flags,
+                            long long q_row_stride, long long q_head_stride, long long kn_row_stride, long long kn_head_stride,
+                            long long kpe_row_stride, long long v_row_stride, long long v_head_stride, void* stream);
+int lc_attn_mla_prefill_bf16(const void* Q, const void* Knope, const void* Kpe, const void* V, void* O, float* lse,
+                             const int* cu_q, const int* cu_k, int B, int H, int Tq, int Tk, int max_nq,
+                             int Dn, int Dr, int Dv, float sm_scale, int flags,
+                             long long q_row_stride, long long q_head_stride, long long kn_row_stride, long long kn_head_stride,
+                             long long kpe_row_stride, long long v_row_stride, long long v_head_stride, void* stream);
+int lc_attn_mla_prefill_kernel_name(int B, int H, int Tq, int max_nq, int Dn, int Dr, int Dv, int flags, int bf16, char* buf, int buflen);
 
 /* EXTENSION: the LIGHTNING INDEXER of DeepSeek-V3.2's sparse attention (mla_index_logits.hip, mla_index_topk.hip): what
  * produces the `slots` lc_attn_mla_sparse_* reads.  Two entries on the ragged batch of lc_attn_mla_paged_*; [lc_mla_append_paged_* ->

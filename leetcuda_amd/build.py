@@ -46,15 +46,16 @@ AUDIT_OWN_REPORT = {"tu_attn_decode_paged": "isa_audit_decode_paged.json", "tu_a
                     "tu_rope_append_varlen_pos": "isa_audit_rope_append_varlen_pos.json", "tu_attn_mla": "isa_audit_mla.json",
                     "tu_attn_mla_kv8": "isa_audit_mla_kv8.json", "tu_mla_append": "isa_audit_mla_append.json",
                     "tu_attn_mla_sparse": "isa_audit_mla_sparse.json", "tu_mla_index": "isa_audit_mla_index.json",
-                    "tu_attn_mla_sparse_kv8": "isa_audit_mla_sparse_kv8.json", "tu_mla_index_fp8": "isa_audit_mla_index_fp8.json"}
+                    "tu_attn_mla_sparse_kv8": "isa_audit_mla_sparse_kv8.json", "tu_mla_index_fp8": "isa_audit_mla_index_fp8.json",
+                    "tu_attn_mla_prefill": "isa_audit_mla_prefill.json"}
 
 # Extra compiler flags of single translation units (object and audit assembly alike; part of the unit's digest).  tu_attn_mla,
-# tu_attn_mla_kv8, tu_mla_append, tu_attn_mla_sparse, tu_mla_index, tu_attn_mla_sparse_kv8 and tu_mla_index_fp8: no packed fp32 VALU instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) from the compiler; the older
+# tu_attn_mla_kv8, tu_mla_append, tu_attn_mla_sparse, tu_mla_index, tu_attn_mla_sparse_kv8, tu_mla_index_fp8 and tu_attn_mla_prefill: no packed fp32 VALU instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) from the compiler; the older
 # units keep the flags their assembly was compared under.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"tu_attn_mla": NO_PACKED_FP32, "tu_attn_mla_kv8": NO_PACKED_FP32, "tu_mla_append": NO_PACKED_FP32,
               "tu_attn_mla_sparse": NO_PACKED_FP32, "tu_mla_index": NO_PACKED_FP32, "tu_attn_mla_sparse_kv8": NO_PACKED_FP32,
-              "tu_mla_index_fp8": NO_PACKED_FP32}
+              "tu_mla_index_fp8": NO_PACKED_FP32, "tu_attn_mla_prefill": NO_PACKED_FP32}
 
 
 def _newer(target: Path, sources) -> bool:

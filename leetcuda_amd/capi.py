@@ -155,6 +155,11 @@ SYMBOLS = {
     "lc_attn_mla_sparse_kv8": (_i, [_vp] * 8 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_sparse_kv8_bf16": (_i, [_vp] * 8 + [_i] * 6 + [C.c_float, _i, _vp, C.c_size_t, _vp]),
     "lc_attn_mla_sparse_kv8_kernel_name": (_i, [_i] * 7 + [_cp, _i]),
+    # the non-absorbed prefill form: Q, Knope, Kpe, V, O, lse (or NULL), cu_q, cu_k, B, H, Tq, Tk, max_nq, Dn, Dr, Dv, sm_scale, flags, the seven
+    # strides (q row / head, kn row / head, kpe row, v row / head), stream
+    "lc_attn_mla_prefill_f16": (_i, [_vp] * 8 + [_i] * 8 + [C.c_float, _i] + [C.c_longlong] * 7 + [_vp]),
+    "lc_attn_mla_prefill_bf16": (_i, [_vp] * 8 + [_i] * 8 + [C.c_float, _i] + [C.c_longlong] * 7 + [_vp]),
+    "lc_attn_mla_prefill_kernel_name": (_i, [_i] * 9 + [_cp, _i]),
     # the lightning indexer: Qi, w, Kipool, logits, cu_q, block_table, kv_len, B, Hi, T, max_nq, num_pages, page_size, max_pages, Di, ld, flags,
     # stream; logits, slots, cu_q, block_table, kv_len, B, T, max_nq, num_pages, page_size, max_pages, ld, topk, flags, stream
     "lc_mla_index_logits_f16": (_i, [_vp] * 7 + [_i] * 8 + [C.c_longlong, _i, _vp]),
@@ -1721,6 +1726,57 @@ def attn_mla_sparse_kv8_kernel_name(T, H, topk, Dc=512, Dr=64, bf16=False) -> st
     """"attn_mla_sparse_kv8_kernel" / "attn_mla_sparse_kv8_bf16_kernel", + " + attn_mla_sparse_combine_[bf16_]kernel xS" with S > 1 ranges."""
     buf = C.create_string_buffer(128)
     check(load().lc_attn_mla_sparse_kv8_kernel_name(T, H, topk, Dc, Dr, 0, int(bf16), buf, 128), "lc_attn_mla_sparse_kv8_kernel_name")
+    return buf.value.decode()
+
+
+# The non-absorbed prefill form (lc_attn_mla_prefill_f16 / _bf16; DESIGN.md section 4.3x): plain ragged attention at D = 192 / 128 over the keys
+# and values kv_b_proj expanded, the rotated k_pe row shared by every head.
+
+def attn_mla_prefill(q, k_nope, k_pe, v, o, cu_q, cu_k, max_nq, sm_scale, lse=None, causal=True, stream=None):
+    """MLA prefill attention on a ragged batch (lc_attn_mla_prefill_f16 / _bf16, picked by q's dtype): q [Tq,H,192], k_nope and v [Tk,H,128],
+    k_pe [Tk,64] — dense or strided VIEWS with a contiguous last dim, e.g. kv.view(Tk, H, 256)[:, :, :128] and [:, :, 128:] of the kv_b_proj
+    output; the strides are read off the tensors —, o [Tq,H,128] dense, all float16 or all bfloat16.  cu_q, cu_k int32 [B + 1] DEVICE tensors
+    read by the kernel only: sequence b owns query tokens cu_q[b] .. cu_q[b+1] - 1 and key rows cu_k[b] .. cu_k[b+1] - 1; 1 <= max_nq <= Tq
+    bounds every Nq_b.  causal: query i of b sees keys j <= Lk_b - Nq_b + i; else all.  sm_scale the model's softmax scale (a float > 0).
+    lse None: returns o; True or a float32 [Tq,H] tensor: returns (o, lse), lse the natural log of the row's softmax denominator (-inf: no
+    visible key, O = 0) — what attn_merge_states takes.  stream: None = torch's current stream, or a raw stream handle."""
+    import torch
+    if q.dtype not in (torch.half, torch.bfloat16):
+        raise TypeError(f"q must be float16 or bfloat16, got {q.dtype}")
+    if any(t.dtype != q.dtype for t in (k_nope, k_pe, v, o)):
+        raise TypeError(f"q / k_nope / k_pe / v / o must share one 16-bit dtype, got {q.dtype} / {k_nope.dtype} / {k_pe.dtype} / {v.dtype} / {o.dtype}")
+    if cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32:
+        raise TypeError(f"cu_q / cu_k must be int32, got {cu_q.dtype} / {cu_k.dtype}")
+    if q.dim() != 3 or k_nope.dim() != 3 or v.dim() != 3 or k_pe.dim() != 2 or o.dim() != 3:
+        _shape_err("q [Tq,H,Dn+Dr] / k_nope [Tk,H,Dn] / k_pe [Tk,Dr] / v [Tk,H,Dv] / o [Tq,H,Dv] expected")
+    Tq, H, Dq = q.shape
+    Tk, _, Dn = k_nope.shape
+    Dr, Dv = k_pe.shape[1], v.shape[2]
+    if (Dq != Dn + Dr or k_nope.shape[1] != H or tuple(v.shape[:2]) != (Tk, H) or k_pe.shape[0] != Tk or tuple(o.shape) != (Tq, H, Dv)
+            or cu_q.dim() != 1 or cu_q.shape[0] < 2 or tuple(cu_k.shape) != tuple(cu_q.shape)):
+        _shape_err(f"q {tuple(q.shape)} k_nope {tuple(k_nope.shape)} k_pe {tuple(k_pe.shape)} v {tuple(v.shape)} o {tuple(o.shape)} "
+                   f"cu_q {tuple(cu_q.shape)} cu_k {tuple(cu_k.shape)}")
+    if any(t.stride(-1) != 1 for t in (q, k_nope, k_pe, v)):
+        _shape_err("q / k_nope / k_pe / v must have a contiguous last dim")
+    if not isinstance(max_nq, int) or max_nq < 1 or max_nq > Tq:
+        raise ValueError(f"max_nq must be an int in [1, Tq = {Tq}], got {max_nq!r}")
+    outs = () if lse is None else (_lse_out(q, None if lse is True else lse),)
+    if not all(t.is_cuda for t in (q, k_nope, k_pe, v)):
+        raise RuntimeError("leetcuda_amd: tensor must live on the MI355X (no CPU path)")
+    _need_gpu(o, *outs, cu_q, cu_k)
+    symbol = "lc_attn_mla_prefill_bf16" if q.dtype == torch.bfloat16 else "lc_attn_mla_prefill_f16"
+    check(getattr(load(), symbol)(_ptr(q), _ptr(k_nope), _ptr(k_pe), _ptr(v), _ptr(o), _ptr(outs[0]) if outs else None, _ptr(cu_q), _ptr(cu_k),
+                                  cu_q.shape[0] - 1, H, Tq, Tk, max_nq, Dn, Dr, Dv, float(sm_scale), ATTN_CAUSAL if causal else 0,
+                                  q.stride(0), q.stride(1), k_nope.stride(0), k_nope.stride(1), k_pe.stride(0), v.stride(0), v.stride(1),
+                                  _stream() if stream is None else stream), symbol)
+    return (o, outs[0]) if outs else o
+
+
+def attn_mla_prefill_kernel_name(B, H, Tq, max_nq, Dn=128, Dr=64, Dv=128, causal=True, bf16=False) -> str:
+    """"attn_mla_prefill_kernel<RS>" / "attn_mla_prefill_bf16_kernel<RS>": RS = 1 (64-token blocks) for max_nq <= 64, else 2."""
+    buf = C.create_string_buffer(128)
+    check(load().lc_attn_mla_prefill_kernel_name(B, H, Tq, max_nq, Dn, Dr, Dv, ATTN_CAUSAL if causal else 0, int(bf16), buf, 128),
+          "lc_attn_mla_prefill_kernel_name")
     return buf.value.decode()
 
 

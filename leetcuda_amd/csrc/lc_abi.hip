@@ -196,6 +196,21 @@ int mla_sparse_kv8_run(bool bf16, const void* Qc, const void* Qpe, const void* C
   return launch_attn_mla_sparse_kv8(p, a, workspace);
 }
 
+// The two prefill entries: an MlaPrefillCall, check_attn_mla_prefill, launch_attn_mla_prefill (tu_attn_mla_prefill.hip)
+int mla_prefill_run(bool bf16, const void* Q, const void* Knope, const void* Kpe, const void* V, void* O, float* lse, const int* cu_q, const int* cu_k,
+                    int B, int H, int Tq, int Tk, int max_nq, int Dn, int Dr, int Dv, float sm_scale, int flags, long long q_row_stride,
+                    long long q_head_stride, long long kn_row_stride, long long kn_head_stride, long long kpe_row_stride, long long v_row_stride,
+                    long long v_head_stride, void* stream) {
+  const MlaPrefillCall c{B, H, Tq, Tk, max_nq, Dn, Dr, Dv, flags, sm_scale, q_row_stride, q_head_stride, kn_row_stride, kn_head_stride,
+                         kpe_row_stride, v_row_stride, v_head_stride, bf16};
+  const MlaPrefillPtrs a{static_cast<const half_t*>(Q), static_cast<const half_t*>(Knope), static_cast<const half_t*>(Kpe),
+                         static_cast<const half_t*>(V), static_cast<half_t*>(O), lse, cu_q, cu_k, static_cast<hipStream_t>(stream)};
+  MlaPrefillPlan p;
+  if (int rc = check_attn_mla_prefill(c, &a, &p)) return rc;
+  if (int rc = launch_guard()) return rc;
+  return launch_attn_mla_prefill(p, a);
+}
+
 // The four latent-cache append entries state an MlaAppendCall; check_mla_append (tu_plan.hip) checks it, launch_mla_append
 // (tu_mla_append.hip) runs it
 int mla_append_run(bool kv8, bool bf16, const void* CKVnew, const void* KPEnew, const void* Qpe, void* Qpe_out, void* CKVpool, void* KPEpool,
@@ -975,6 +990,31 @@ int lc_mla_index_append_fp8_kernel_name(int B, int T, int max_nq, int num_pages,
   if (int rc = check_mla_index_append_fp8(MlaIndexAppendCall{B, T, max_nq, num_pages, page_size, max_pages, Di, row_stride, pow2, bf16 != 0}, nullptr))
     return rc;
   snprintf(buf, buflen, "mla_index_append_fp8_%skernel", bf16 ? "bf16_" : "");
+  return LC_OK;
+}
+
+// The non-absorbed prefill form of latent attention, D = 192 / 128 on a ragged batch (attn_mla_prefill.hip): mla_prefill_run above
+int lc_attn_mla_prefill_f16(const void* Q, const void* Knope, const void* Kpe, const void* V, void* O, float* lse, const int* cu_q, const int* cu_k,
+                            int B, int H, int Tq, int Tk, int max_nq, int Dn, int Dr, int Dv, float sm_scale, int flags, long long q_row_stride,
+                            long long q_head_stride, long long kn_row_stride, long long kn_head_stride, long long kpe_row_stride,
+                            long long v_row_stride, long long v_head_stride, void* stream) {
+  return mla_prefill_run(false, Q, Knope, Kpe, V, O, lse, cu_q, cu_k, B, H, Tq, Tk, max_nq, Dn, Dr, Dv, sm_scale, flags, q_row_stride, q_head_stride,
+                         kn_row_stride, kn_head_stride, kpe_row_stride, v_row_stride, v_head_stride, stream);
+}
+
+int lc_attn_mla_prefill_bf16(const void* Q, const void* Knope, const void* Kpe, const void* V, void* O, float* lse, const int* cu_q, const int* cu_k,
+                             int B, int H, int Tq, int Tk, int max_nq, int Dn, int Dr, int Dv, float sm_scale, int flags, long long q_row_stride,
+                             long long q_head_stride, long long kn_row_stride, long long kn_head_stride, long long kpe_row_stride,
+                             long long v_row_stride, long long v_head_stride, void* stream) {
+  return mla_prefill_run(true, Q, Knope, Kpe, V, O, lse, cu_q, cu_k, B, H, Tq, Tk, max_nq, Dn, Dr, Dv, sm_scale, flags, q_row_stride, q_head_stride,
+                         kn_row_stride, kn_head_stride, kpe_row_stride, v_row_stride, v_head_stride, stream);
+}
+
+int lc_attn_mla_prefill_kernel_name(int B, int H, int Tq, int max_nq, int Dn, int Dr, int Dv, int flags, int bf16, char* buf, int buflen) {
+  if (!buf || buflen < 8) return LC_ERR_ARG;
+  MlaPrefillPlan p;
+  if (int rc = check_attn_mla_prefill(MlaPrefillCall{B, H, Tq, 1, max_nq, Dn, Dr, Dv, flags, 1.f, 0, 0, 0, 0, 0, 0, 0, bf16 != 0}, nullptr, &p)) return rc;
+  format_attn_mla_prefill(p, buf, buflen);
   return LC_OK;
 }
 

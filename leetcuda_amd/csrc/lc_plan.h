@@ -329,6 +329,33 @@ inline size_t mla_sparse_workspace_bytes(const MlaSparsePlan& p) {
 int launch_attn_mla_sparse(const MlaSparsePlan& p, const MlaSparsePtrs& a, void* workspace);   // tu_attn_mla_sparse.hip; checked arguments
 int launch_attn_mla_sparse_kv8(const MlaSparsePlan& p, const MlaSparsePtrs& a, void* workspace);   // tu_attn_mla_sparse_kv8.hip; checked arguments, MlaSparseCall::kv8
 
+// What a caller of a prefill latent attention entry states (lc_attn_mla_prefill_f16 / _bf16 and their name call): the
+// NON-ABSORBED form — plain attention of H heads with scores over Dn + Dr = 192 dims and values over Dv = 128 — on a ragged batch of B sequences,
+// queries cu_q [B + 1] into Tq token rows, keys cu_k [B + 1] into Tk key rows, every operand a strided view (strides in elements).  The plan:
+// attn_mla_prefill_kernel<BF16, RS> on NB x B x H workgroups of 64 RS query tokens of one head, NB = ceil(max_nq / (64 RS)); RS = 1 for
+// max_nq <= 64, else 2: a host quantity.  No split over the keys, no workspace: every call is legal under graph capture.
+struct MlaPrefillCall {
+  int B, H, Tq, Tk, max_nq, Dn, Dr, Dv, flags;   // (the name call states Tk = 1: it decides nothing)
+  float sm_scale;                                // the caller's softmax scale (the name call: 1)
+  long long q_row_stride, q_head_stride, kn_row_stride, kn_head_stride, kpe_row_stride, v_row_stride, v_head_stride;   // (checked with the pointers)
+  bool bf16;                                     // every 16-bit operand is bfloat16: picks the kernel (and its name) and nothing else
+};
+struct MlaPrefillPtrs {
+  const half_t *Q, *Kn, *Kpe, *V;                // [Tq,H,Dn+Dr], [Tk,H,Dn], [Tk,Dr], [Tk,H,Dv] (16-bit lanes: fp16 or, MlaPrefillCall::bf16, bfloat16)
+  half_t* O;                                     // [Tq,H,Dv] dense
+  float* lse;                                    // device float[Tq H] or nullptr = none
+  const int *cu_q, *cu_k;                        // device int32 [B + 1] each
+  hipStream_t st;
+};
+struct MlaPrefillPlan {
+  MlaPrefillCall call;   // what was planned
+  int RS, NB;
+};
+// The checks in check_attn_mla_sparse's order, then the plan.  a: the run call's pointers (nullptr: the name call — no pointer, no stride)
+int check_attn_mla_prefill(const MlaPrefillCall& c, const MlaPrefillPtrs* a, MlaPrefillPlan* p);   // tu_plan.hip
+void format_attn_mla_prefill(const MlaPrefillPlan& p, char* buf, int buflen);   // "attn_mla_prefill_kernel<2>", "attn_mla_prefill_bf16_kernel<1>"
+int launch_attn_mla_prefill(const MlaPrefillPlan& p, const MlaPrefillPtrs& a);   // tu_attn_mla_prefill.hip; checked arguments
+
 // What a caller of a lightning-indexer entry states (lc_mla_index_logits_f16 / _bf16, lc_mla_index_topk and their name calls):
 // the ragged batch of MlaCall over an index-key pool [num_pages, page_size, Di] (the paged layout at Hkv = 1), Hi index heads, fp32 logits
 // [T, ld].  The logits plan: mla_index_logits_kernel<BF16> on B x NB x S workgroups, NB = ceil(max_nq / 8) token blocks, S ranges of the 64-key

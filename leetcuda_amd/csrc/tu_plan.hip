@@ -864,6 +864,43 @@ void format_attn_mla_sparse(const MlaSparsePlan& p, char* buf, int buflen) {
   else snprintf(buf, buflen, "attn_mla_sparse_%s%skernel", k8, bf);
 }
 
+// The non-absorbed prefill form of latent attention (lc_plan.h MlaPrefillCall).  The statuses in check_attn_mla_sparse's
+// order: flags, NULL pointers (lse may be one) and the scale, the shape — dims, max_nq, the 32-bit row count, the grid, alignment, the strides
+// (elements; multiples of 8, at least what they step over) —, the head dims.  The plan: RS = 1 for max_nq <= 64, else 2 — by tile reuse, from a
+// host quantity alone.
+int check_attn_mla_prefill(const MlaPrefillCall& c, const MlaPrefillPtrs* a, MlaPrefillPlan* p) {
+  if (c.flags & ~LC_ATTN_CAUSAL) return LC_ERR_ARG;
+  if (a && (!a->Q || !a->Kn || !a->Kpe || !a->V || !a->O || !a->cu_q || !a->cu_k)) return LC_ERR_ARG;   // (lse: NULL = none)
+  // (decided on the bit pattern: this unit is compiled with -fno-honor-nans.)  Finite and > 0: exponent not all ones, sign clear, not zero
+  const uint32_t sb = __builtin_bit_cast(uint32_t, c.sm_scale);
+  if ((sb & 0x7f800000u) == 0x7f800000u || (sb >> 31) != 0 || sb == 0) return LC_ERR_ARG;
+  if (c.B <= 0 || c.H <= 0 || c.Tq <= 0 || c.Tk <= 0 || c.max_nq <= 0 || c.Dn <= 0 || c.Dr <= 0 || c.Dv <= 0) return LC_ERR_SHAPE;
+  if (c.max_nq > c.Tq) return LC_ERR_SHAPE;
+  if ((long)c.Tq * c.H > 0x7fffffffL) return LC_ERR_SHAPE;                                   // rows of O and lse are counted in 32 bits
+  const int RS = c.max_nq <= 64 ? 1 : 2;
+  const int NB = (int)(((long)c.max_nq + 64 * RS - 1) / (64 * RS));
+  if ((size_t)NB * (size_t)c.B > 0x7fffffffull || (size_t)NB * (size_t)c.B * (size_t)c.H > 0x7fffffffull) return LC_ERR_SHAPE;   // 1-D grid of NB x B x H workgroups
+  if (a) {
+    if (!aligned16(a->Q) || !aligned16(a->Kn) || !aligned16(a->Kpe) || !aligned16(a->V) || !aligned16(a->O)) return LC_ERR_SHAPE;
+    if ((((uintptr_t)a->lse | (uintptr_t)a->cu_q | (uintptr_t)a->cu_k) & 3) != 0) return LC_ERR_SHAPE;
+    // a [rows, H, D] view: head >= D, row >= (H - 1) head + D (stated by division: no product of a caller's stride can overflow)
+    auto heads_fit = [&](long long row, long long head, long long D) {
+      if (row % 8 != 0 || head % 8 != 0 || head < D || row < D) return false;
+      return c.H == 1 || (row - D) / (c.H - 1) >= head;
+    };
+    if (!heads_fit(c.q_row_stride, c.q_head_stride, (long long)c.Dn + c.Dr) || !heads_fit(c.kn_row_stride, c.kn_head_stride, c.Dn) ||
+        !heads_fit(c.v_row_stride, c.v_head_stride, c.Dv))
+      return LC_ERR_SHAPE;
+    if (c.kpe_row_stride % 8 != 0 || c.kpe_row_stride < c.Dr) return LC_ERR_SHAPE;
+  }
+  if (c.Dn != 128 || c.Dr != 64 || c.Dv != 128) return LC_ERR_HEADDIM;
+  *p = MlaPrefillPlan{c, RS, NB};
+  return LC_OK;
+}
+void format_attn_mla_prefill(const MlaPrefillPlan& p, char* buf, int buflen) {
+  snprintf(buf, buflen, "attn_mla_prefill_%skernel<%d>", p.call.bf16 ? "bf16_" : "", p.RS);
+}
+
 // The lightning indexer (lc_plan.h MlaIndexCall).  Both entries: flags and NULL pointers, then the shape — dims, max_nq, the
 // page size, the pool capacity in 32 bits, ld —, the entry's own bound, alignment; the logits entries then the head dims.
 namespace {

@@ -87,6 +87,8 @@ OWNED_AGPRS = [
     (re.compile(r"mla_index_logits_kernel|mla_index_topk_kernel"), []),
     # ... and the ones over an fp8 index-key pool (mla_index_logits_fp8.hip, mla_index_append_fp8.hip: builtins only)
     (re.compile(r"mla_index_logits_fp8_kernel|mla_index_append_fp8_kernel"), []),
+    # ... and the non-absorbed prefill form of latent attention (attn_mla_prefill.hip: builtins only)
+    (re.compile(r"attn_mla_prefill_kernel"), []),
     (re.compile(r"attn_fwd_w4u_kernel|attn_fwd_w4u_causal_kernel|attn_fwd_w4i_kernel|attn_fwd_w4u_gqa_kernel|attn_fwd_w4u_causal_gqa_kernel|attn_fwd_w4i_gqa_kernel|attn_fwd_bigd2_kernel|attn_fwd_bigd3_kernel|attn_fwd_bigd4_kernel|attn_fwd_bigd6_kernel|attn_fwd_bigd7_kernel"), [(0, 255)]),
 ]
 
